@@ -2,7 +2,7 @@
 """Headline benchmark: TARGET-VAE training images/sec (fwd + bwd + Adam [+ RCCL all-reduce]) on synthetic
 64x64 particle stacks, P8 (R=8), z=2, batch 256 per GPU  (BASELINE.json metric / configs[3], SURVEY 8d "S64").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +11,11 @@ training minibatch: encoder fwd, attention head, decoder fwd, likelihood, full b
 (N>1) and the fused Adam update; inputs are resident in HBM before the timed region (like the reference, which
 keeps the dataset on the device, train_mnist.py:495).  Noise (Exp(1), N(0,1)) is drawn on the device inside the
 step, as the reference does.
+
+A plain run prints the headline fields only (metric, value, unit, ms_per_step, dtype, config, ...).  `--full` adds the
+per-entry-point roofline block and every companion measurement.  `--dump-outputs DIR` writes the ELBO terms of the last timed
+step and the parameters after it as .npy files; with the same arguments the inputs (data, initial parameters, noise seeds) are
+the same from run to run.
 """
 import argparse
 import json
@@ -114,7 +119,7 @@ def parse_args():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=None, help='images per GPU per step (BASELINE: 256; S128G: 8)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU oracle baseline')
     ap.add_argument('--no-f32-companion', action='store_true',
                     help="skip the extra measurements of the same steps in the all-fp32-MFMA mode (TVAE_GEMM=f32) and in "
                          "the opt-in bf16 throughput mode")
@@ -129,7 +134,18 @@ def parse_args():
                          'timed loop; without the flag the 28x28 workloads report it as a companion measurement')
     ap.add_argument('--workload', choices=['S128G', 'S28', 'S28F', 'S64'], default='S64',
                     help='S64 = the BASELINE.json metric configuration (default); others are extra measurements')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: per-entry-point kernel events in the timed loop and the roofline block, the '
+                         'companion measurements (other arithmetic modes, small batches, other workloads, encoder forward, '
+                         'strong scaling), the per-rank diagnostics and the CPU baseline; the --no-* switches above act only '
+                         'here.  Without it a run sets up, warms up, times --steps steps and prints the headline fields')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (elbo, log_p, kl) and the parameters '
+                         'it left behind as DIR/<name>.npy (rank 0)')
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return a
 
 
 if __name__ == '__main__' and 'WORLD_SIZE' not in os.environ:
@@ -274,6 +290,21 @@ def cpu_baseline(batch=32, steps=4):
                                  'sample': f'oracle encoder forward, {batch} images, 1 warm-up + 2 timed, min'})
 
 
+def dump_outputs(d, terms, gen, enc):
+    """--dump-outputs: what a caller of the timed training step receives from its last call -- the ELBO terms elbo, log_p,
+    kl in the dtypes the step returns them (float64 / float32) and the parameters Adam left behind (float32) -- as
+    d/<name>.npy.  Whole tensors, no sampling: the largest workload's parameters (S128G) are 11 MB."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {nm: t.detach().cpu().numpy() for nm, t in zip(('elbo', 'log_p', 'kl'), terms)}
+    for pre, m in (('gen', gen), ('enc', enc)):
+        for k_, p in m.named_parameters():
+            arrs['param.%s.%s' % (pre, k_)] = p.detach().float().cpu().numpy()
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+    for nm, a in arrs.items():
+        np.save(os.path.join(d, nm + '.npy'), a)
+
+
 def measure_extra_workload(name, dev, steps, warmup=2):
     """One of the other BASELINE.json workloads (configs[1], [2], [4]) inside the default, driver-timed run: the same
     training step (fwd + bwd + Adam, noise drawn on the device, data resident in HBM) at that workload's own batch, timed with
@@ -352,6 +383,7 @@ def main():
     step.pixel_spacing(x)                           # cached once (the reference syncs for it every step)
 
     gs_box = [None]
+    terms_box = [None]                              # --dump-outputs: (elbo, log_p, kl) of the latest step
     if args.graph:
         from tvae import graph as _graph
         gs_box[0] = _graph.GraphedStep(x, gen, enc, opt, c['lik'], B, (c['cin'], c['n'], c['n']), dev)
@@ -365,11 +397,15 @@ def main():
             opt.step()
             e_ = terms[0].clone()
             opt.zero_grad()
+            if args.dump_outputs:
+                terms_box[0] = terms             # the replay's output buffer (elbo, log_p, kl): read before the next replay
             return e_
         elbo, log_p, kl = step.elbo_terms(x, y, gen, enc, c['lik'])
         step.backward_neg_elbo(elbo)         # = (-elbo).backward() of the training loop (tvae/step.py)
         opt.step()
         opt.zero_grad(set_to_none=True)      # as the training loop (tvae/step.py): gradients gathered by one multi-tensor copy
+        if args.dump_outputs:
+            terms_box[0] = (elbo.detach(), log_p.detach(), kl.detach())
         return elbo.detach()
 
     def barrier():
@@ -381,7 +417,7 @@ def main():
     for i in range(args.warmup):
         one_step(i)
     barrier()
-    ops.KERNEL_EVENTS = {}
+    ops.KERNEL_EVENTS = {} if args.full else None  # per-entry-point events (the --full roofline block) only when asked for
     t0 = time.perf_counter()
     last = None
     for i in range(args.steps):
@@ -391,7 +427,9 @@ def main():
     early_posted_main = reducer.posted_early if reducer is not None else 0      # (warm-up + timed steps; diagnostics below)
     kev = ops.kernel_event_ms()
     ops.KERNEL_EVENTS = None
-    if gs_box[0] is not None:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, terms_box[0], gen, enc)
+    if args.full and gs_box[0] is not None:
         # --graph: the replayed launches carry no per-entry-point events; the roofline block comes from the same number of EAGER
         # steps timed right after (the headline `value` stays the graph-replay run)
         g_saved, gs_box[0] = gs_box[0], None
@@ -408,7 +446,7 @@ def main():
     # N > 1: the same number of steps again with the GLOBAL batch fixed at the per-GPU batch of the weak run (strong
     # scaling, SURVEY 8d: "B=256 per GPU (weak) and global-B=256 (strong) separately and label them")
     strong = None
-    if world > 1 and not args.no_strong and B >= world:
+    if args.full and world > 1 and not args.no_strong and B >= world:
         bs = B // world
         for i in range(2):
             one_step(i, bs)
@@ -431,7 +469,8 @@ def main():
     # driver's to measure).  If 32 images per GPU run well under 75 % of the B = 256 rate, 6x at 8 GPUs is out of reach for
     # the strong-scaling line whatever the collective costs.
     small_batch = None
-    if world == 1 and args.workload == 'S64' and not (args.no_small_batch or args.no_f32_companion) and gs_box[0] is None:
+    if args.full and world == 1 and args.workload == 'S64' and not (args.no_small_batch or args.no_f32_companion) and \
+            gs_box[0] is None:
         small_batch = {'per_image_rate_at_full_batch': B * args.steps / dt, 'full_batch': B, 'points': []}
         for bs in (12, 32, 64, 100, 128):
             if bs >= B:
@@ -506,7 +545,7 @@ def main():
             small_batch['allreduce_one_rank'] = {'error': repr(ex)[:200]}
     # companion measurement: the same number of steps with every matrix product on the exact fp32 MFMA
     companion = None
-    if world == 1 and mode in ('x6', 'h3') and not args.no_f32_companion:
+    if args.full and world == 1 and mode in ('x6', 'h3') and not args.no_f32_companion:
         _lib.set_gemm_mode('f32')
         for i in range(2):
             one_step(i)
@@ -530,7 +569,7 @@ def main():
                          if 'tvae_conv1_wgrad' in kev1 else None}
     # companion: the exact three-part bf16 split (six products per block; the default arithmetic of rounds 1-2)
     companion_x6 = None
-    if world == 1 and mode == 'h3' and not args.no_f32_companion:
+    if args.full and world == 1 and mode == 'h3' and not args.no_f32_companion:
         _lib.set_gemm_mode('x6')
         for i in range(2):
             one_step(i)
@@ -553,7 +592,7 @@ def main():
                                             if k_.startswith('tvae_linear') or k_.startswith('tvae_conv1')}}
     # second companion: the opt-in bf16 throughput mode (one bf16 MFMA per product block; never the headline)
     companion_bf16 = None
-    if world == 1 and mode in ('x6', 'h3') and not args.no_f32_companion:
+    if args.full and world == 1 and mode in ('x6', 'h3') and not args.no_f32_companion:
         _lib.set_gemm_mode('bf16')
         for i in range(2):
             one_step(i)
@@ -581,7 +620,8 @@ def main():
     # third companion (28x28 workloads, where ~70 launches per 4 ms step make the host's launch cost visible): the same steps
     # with forward + backward replayed from a hipGraph (tvae/graph.py; bitwise the eager result)
     companion_graph = None
-    if world == 1 and mode in ('x6', 'h3') and not args.graph and not args.no_f32_companion and args.workload in ('S28', 'S28F'):
+    if args.full and world == 1 and mode in ('x6', 'h3') and not args.graph and not args.no_f32_companion and \
+            args.workload in ('S28', 'S28F'):
         from tvae import graph as _graph
         gs_box[0] = _graph.GraphedStep(x, gen, enc, opt, c['lik'], B, (c['cin'], c['n'], c['n']), dev)
         for i in range(2):
@@ -600,7 +640,7 @@ def main():
     # images through conv1 -> conv2 -> heads -> attention head in training mode (the two activations a backward needs are
     # written), timed with events on the launch stream
     enc_fwd = enc_inf = None
-    if world == 1 and args.workload == 'S64':
+    if args.full and world == 1 and args.workload == 'S64':
         ho = c['n'] + 2 * c['pad'] - c['k'] + 1
         yb = data[:B]
         P = c['R'] * ho * ho
@@ -654,7 +694,7 @@ def main():
     # the other BASELINE.json workloads in the same driver-timed line: S28 (configs[1]), S28F (configs[2]),
     # S128G (configs[4]) at their own batch, default arithmetic
     workloads = None
-    if world == 1 and args.workload == 'S64' and not args.no_workloads and gs_box[0] is None:
+    if args.full and world == 1 and args.workload == 'S64' and not args.no_workloads and gs_box[0] is None:
         workloads = {}
         for wn in ('S28', 'S28F', 'S128G', 'S128G@32'):
             try:
@@ -663,7 +703,7 @@ def main():
                 workloads[wn] = {'error': repr(ex)[:300]}
             torch.cuda.empty_cache()
     dp_diag = None
-    if world > 1:
+    if args.full and world > 1:
         # self-diagnosis of the first multi-GPU run: every rank's own wall time of the timed region, the
         # early buckets it posted from inside a backward, the collectives it issued -- gathered, so that a straggler, a rank
         # that never posted the early bucket or a group of the wrong size is visible in the one JSON line
@@ -680,6 +720,7 @@ def main():
                    'world_size_seen_per_rank': [int(p_[2]) for p_ in per],
                    'device_index_per_rank': [int(p_[3]) for p_ in per],
                    'note': 'steps of the warm-up and the timed region both post the early (decoder) bucket'}
+    if world > 1:                                   # the headline: the slowest rank's timed region
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
@@ -691,64 +732,106 @@ def main():
         Nt = B * c['n'] * c['n']
         dense_flops = 2.0 * c['hidden'] * c['hidden'] * Nt
         info = MODE_INFO[mode]
-        # every timed entry point: (algorithmic FLOPs per launch, kernel, note)
         conv_dft = mode in ('x6', 'h3', 'bf16') and bool(int(os.environ.get('TVAE_CONV_DFT', '1')))
-        entries = {
-            'tvae_conv1_fwd': (conv_flops, 'dft_spectra_x_kernel + batched dense_x6_xres_kernel (other frames: _plain4_kernel) + dft_out_ring_kernel'
-                               if conv_dft else info['kernels']['tvae_conv1_fwd']),
-            'tvae_conv1_wgrad': (conv_flops, 'dft_dy_ring_kernel + batched dense_wgrad_x6_dma_kernel (512 x 128 tile) + dft_dbank_x_kernel'
-                                 if conv_dft else info['kernels']['tvae_conv1_wgrad']),
-            'tvae_linear_fwd_x6': (dense_flops, 'dense_x6_kernel'),
-            'tvae_linear_dgrad_x6': (dense_flops, 'dense_x6_kernel'),
-            'tvae_linear_wgrad_x6': (dense_flops, 'dense_wgrad_x6_dma_kernel'),
-        }
-        # fused encoder tail (conv2 + head projection; csrc/enc_tail_x6_kernels.hpp): HBM-bound side kernels
-        ho_ = c['n'] + 2 * c['pad'] - c['k'] + 1
-        ncol = B * c['R'] * ho_ * ho_
-        nh_ = 3 + 2 * c['zd']
-        tail_flops = 2.0 * c['C'] * (c['C'] + nh_) * ncol
-        entries['tvae_enc_tail_fwd_x6'] = (tail_flops, 'enc_tail_fwd_x6_kernel')
-        entries['tvae_enc_tail_dgrad_x6'] = (tail_flops, 'enc_tail_dgrad_x6_kernel')
-        entries['tvae_enc_tail_wgrad_x6'] = (2.0 * c['C'] * c['C'] * ncol, 'enc_tail_wgrad_x6_kernel')
-        tail_bytes = {'tvae_enc_tail_fwd_x6': (2 * 4 * c['C'] + 4 * nh_ + 32) * ncol,       # A1 in, H out, heads, sign words
-                      'tvae_enc_tail_dgrad_x6': (4 * c['C'] + 4 * nh_ + 32) * ncol,         # dA1 out, head gradients, sign words
-                      'tvae_enc_tail_wgrad_x6': (4 * c['C'] + 4 * nh_ + 16) * ncol}         # A1 in, head gradients, sign words of H
-        timed = {k_: v for k_, v in kev.items() if k_ in entries}
-        enc_tail = {k_: {'ms': round(kev[k_]['mean_ms'], 3), 'bound': 'hbm',
-                         'algorithmic_bytes_per_launch': float(tail_bytes[k_]),
-                         'achieved_GBps': tail_bytes[k_] / (kev[k_]['mean_ms'] * 1e-3) / 1e9,
-                         'frac_of_8TBps': tail_bytes[k_] / (kev[k_]['mean_ms'] * 1e-3) / 8.0e12,
-                         'mfma_per_block_as_launched': kev[k_].get('mfma_per_block_seen'),
-                         'executed_bf16_pflops': (kev[k_].get('mfma_per_block') or {'bf16': 1, 'h3': 3}.get(mode, 6)) *
-                         entries[k_][0] / (kev[k_]['mean_ms'] * 1e-3) / 1e15}
-                    for k_ in tail_bytes if k_ in kev}
-        # the roofline object describes the dominant KERNEL FAMILY of the step, the split-pipe dense GEMM (decoder layers
-        # and the spectral contraction of the convolution), on its LARGEST decoder launch (not its best one), with the
-        # call-weighted aggregate over the three decoder launches beside it.  bf16 MFMAs per product block: 6 in the
-        # exact-split arithmetic, 3 where the streamed operand is the exact 0 / 1 matrix [H > 0] (two-valued implicit
-        # LeakyReLU gradient: data / weight gradient of the last hidden layer).  In fp32 mode the dominant kernel is the
-        # direct lifting-convolution weight gradient.
-        two_val = c['layers'] >= 2 and c['n_out'] == 1          # ops.DecoderFn: virt + LeakyReLU (bench models)
-        products = {'tvae_linear_fwd_x6': 6, 'tvae_linear_dgrad_x6': 3 if two_val else 6,
-                    'tvae_linear_wgrad_x6': 3 if two_val else 6}
-        if mode == 'h3':        # two fp16 parts: 3 products, 2 against the exact 0 / 1 operand (the general forms stay x6)
-            products = {'tvae_linear_fwd_x6': 3, 'tvae_linear_dgrad_x6': 2 if two_val else 6,
-                        'tvae_linear_wgrad_x6': 2 if two_val else 6}
-        if mode == 'bf16':
-            products = {k_: 1 for k_ in products}
-        # ... as the MODE suggests; what counts is what was LAUNCHED: tvae.ops records the `parts` it passed to every entry
-        # point and the matrix instructions per product block that follow from them (ops._timed / mfma_per_block); a launch
-        # that fell back to the three-part split is then priced as six products, not three
-        products_by_mode = dict(products)
-        products = {k_: (kev.get(k_, {}).get('mfma_per_block') or products[k_]) for k_ in products}
-        dense = [k_ for k_ in products if k_ in timed]
-        if mode in ('x6', 'h3', 'bf16') and dense:
-            dom = max(dense, key=lambda k_: kev[k_]['total_ms'])
-        else:
-            dom = max(('tvae_conv1_fwd', 'tvae_conv1_wgrad'), key=lambda k_: kev.get(k_, {}).get('total_ms', 0.0))
-        flops = entries[dom][0]
-        ach = flops / (kev[dom]['mean_ms'] * 1e-3) / 1e12
-        peak = PEAK_BF16_MFMA_TFLOPS / products[dom] if (mode in ('x6', 'h3', 'bf16') and dom in products) else info['peak']
+        roofline = enc_tail = None
+        if args.full:             # per-entry-point figures from the events recorded in the timed loop
+            # every timed entry point: (algorithmic FLOPs per launch, kernel, note)
+            entries = {
+                'tvae_conv1_fwd': (conv_flops, 'dft_spectra_x_kernel + batched dense_x6_xres_kernel (other frames: _plain4_kernel) + dft_out_ring_kernel'
+                                   if conv_dft else info['kernels']['tvae_conv1_fwd']),
+                'tvae_conv1_wgrad': (conv_flops, 'dft_dy_ring_kernel + batched dense_wgrad_x6_dma_kernel (512 x 128 tile) + dft_dbank_x_kernel'
+                                     if conv_dft else info['kernels']['tvae_conv1_wgrad']),
+                'tvae_linear_fwd_x6': (dense_flops, 'dense_x6_kernel'),
+                'tvae_linear_dgrad_x6': (dense_flops, 'dense_x6_kernel'),
+                'tvae_linear_wgrad_x6': (dense_flops, 'dense_wgrad_x6_dma_kernel'),
+            }
+            # fused encoder tail (conv2 + head projection; csrc/enc_tail_x6_kernels.hpp): HBM-bound side kernels
+            ho_ = c['n'] + 2 * c['pad'] - c['k'] + 1
+            ncol = B * c['R'] * ho_ * ho_
+            nh_ = 3 + 2 * c['zd']
+            tail_flops = 2.0 * c['C'] * (c['C'] + nh_) * ncol
+            entries['tvae_enc_tail_fwd_x6'] = (tail_flops, 'enc_tail_fwd_x6_kernel')
+            entries['tvae_enc_tail_dgrad_x6'] = (tail_flops, 'enc_tail_dgrad_x6_kernel')
+            entries['tvae_enc_tail_wgrad_x6'] = (2.0 * c['C'] * c['C'] * ncol, 'enc_tail_wgrad_x6_kernel')
+            tail_bytes = {'tvae_enc_tail_fwd_x6': (2 * 4 * c['C'] + 4 * nh_ + 32) * ncol,       # A1 in, H out, heads, sign words
+                          'tvae_enc_tail_dgrad_x6': (4 * c['C'] + 4 * nh_ + 32) * ncol,         # dA1 out, head gradients, sign words
+                          'tvae_enc_tail_wgrad_x6': (4 * c['C'] + 4 * nh_ + 16) * ncol}         # A1 in, head gradients, sign words of H
+            timed = {k_: v for k_, v in kev.items() if k_ in entries}
+            enc_tail = {k_: {'ms': round(kev[k_]['mean_ms'], 3), 'bound': 'hbm',
+                             'algorithmic_bytes_per_launch': float(tail_bytes[k_]),
+                             'achieved_GBps': tail_bytes[k_] / (kev[k_]['mean_ms'] * 1e-3) / 1e9,
+                             'frac_of_8TBps': tail_bytes[k_] / (kev[k_]['mean_ms'] * 1e-3) / 8.0e12,
+                             'mfma_per_block_as_launched': kev[k_].get('mfma_per_block_seen'),
+                             'executed_bf16_pflops': (kev[k_].get('mfma_per_block') or {'bf16': 1, 'h3': 3}.get(mode, 6)) *
+                             entries[k_][0] / (kev[k_]['mean_ms'] * 1e-3) / 1e15}
+                        for k_ in tail_bytes if k_ in kev}
+            # the roofline object describes the dominant KERNEL FAMILY of the step, the split-pipe dense GEMM (decoder layers
+            # and the spectral contraction of the convolution), on its LARGEST decoder launch (not its best one), with the
+            # call-weighted aggregate over the three decoder launches beside it.  bf16 MFMAs per product block: 6 in the
+            # exact-split arithmetic, 3 where the streamed operand is the exact 0 / 1 matrix [H > 0] (two-valued implicit
+            # LeakyReLU gradient: data / weight gradient of the last hidden layer).  In fp32 mode the dominant kernel is the
+            # direct lifting-convolution weight gradient.
+            two_val = c['layers'] >= 2 and c['n_out'] == 1          # ops.DecoderFn: virt + LeakyReLU (bench models)
+            products = {'tvae_linear_fwd_x6': 6, 'tvae_linear_dgrad_x6': 3 if two_val else 6,
+                        'tvae_linear_wgrad_x6': 3 if two_val else 6}
+            if mode == 'h3':        # two fp16 parts: 3 products, 2 against the exact 0 / 1 operand (the general forms stay x6)
+                products = {'tvae_linear_fwd_x6': 3, 'tvae_linear_dgrad_x6': 2 if two_val else 6,
+                            'tvae_linear_wgrad_x6': 2 if two_val else 6}
+            if mode == 'bf16':
+                products = {k_: 1 for k_ in products}
+            # ... as the MODE suggests; what counts is what was LAUNCHED: tvae.ops records the `parts` it passed to every entry
+            # point and the matrix instructions per product block that follow from them (ops._timed / mfma_per_block); a launch
+            # that fell back to the three-part split is then priced as six products, not three
+            products_by_mode = dict(products)
+            products = {k_: (kev.get(k_, {}).get('mfma_per_block') or products[k_]) for k_ in products}
+            dense = [k_ for k_ in products if k_ in timed]
+            if mode in ('x6', 'h3', 'bf16') and dense:
+                dom = max(dense, key=lambda k_: kev[k_]['total_ms'])
+            else:
+                dom = max(('tvae_conv1_fwd', 'tvae_conv1_wgrad'), key=lambda k_: kev.get(k_, {}).get('total_ms', 0.0))
+            flops = entries[dom][0]
+            ach = flops / (kev[dom]['mean_ms'] * 1e-3) / 1e12
+            peak = PEAK_BF16_MFMA_TFLOPS / products[dom] if (mode in ('x6', 'h3', 'bf16') and dom in products) else info['peak']
+            roofline = {'kernel': dom + ' (' + entries[dom][1] + ', ' + info['insn'] + ')', 'bound': 'mfma',
+                        'achieved': ach, 'peak': peak, 'unit': 'TFLOP/s',
+                        'frac': ach / peak,
+                        'peak_note': 'algorithmic (fp32-equivalent) FLOP/s; peak = 2500 TFLOP/s dense bf16 / bf16 MFMAs per '
+                                     'product block of this launch (dense_launches)' if mode in ('x6', 'h3', 'bf16') else
+                                     'dense f32 MFMA peak',
+                        'frac_of_f32_mfma_peak': ach / PEAK_F32_MFMA_TFLOPS,
+                        # dense_x6_kernel is launched with several shapes: pick the decoder-layer launch by its grid
+                        # (512 threads x 8*ceil(tiles_n/8) workgroups; forward and data-gradient launches averaged)
+                        'traffic': pmc_traffic(dom, 512 * 8 * ((Nt // 128 + 7) // 8) * ((c['hidden'] + 511) // 512)
+                                               if dom.startswith('tvae_linear') else None,
+                                               kernel=entries[dom][1].split()[0] if dom.startswith('tvae_linear') else None)
+                        if args.workload == 'S64' else None,
+                        'algorithmic_flops_per_launch': flops, 'mean_launch_ms': kev[dom]['mean_ms'],
+                        'launches_timed': kev[dom]['launches'],
+                        'entry_points_ms': {k_: round(v['mean_ms'], 3) for k_, v in sorted(timed.items())},
+                        'dense_launches': {k_: {'ms_per_step': round(kev[k_]['total_ms'] / args.steps, 3),
+                                                'launches_per_step': kev[k_]['launches'] / args.steps,
+                                                'bf16_mfma_per_product_block': products[k_],
+                                                'mfma_per_block_as_launched': kev[k_].get('mfma_per_block_seen'),
+                                                'mfma_per_block_expected_for_mode': products_by_mode[k_],
+                                                'algorithmic_tflops': dense_flops * kev[k_]['launches'] /
+                                                (kev[k_]['total_ms'] * 1e-3) / 1e12,
+                                                'executed_bf16_pflops': products[k_] * dense_flops * kev[k_]['launches'] /
+                                                (kev[k_]['total_ms'] * 1e-3) / 1e15,
+                                                'frac_of_bf16_peak': products[k_] * dense_flops * kev[k_]['launches'] /
+                                                (kev[k_]['total_ms'] * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS}
+                                           for k_ in dense} if mode in ('x6', 'h3', 'bf16') else None,
+                        'dense_aggregate': ({'algorithmic_tflops': sum(dense_flops * kev[k_]['launches'] for k_ in dense) /
+                                             (sum(kev[k_]['total_ms'] for k_ in dense) * 1e-3) / 1e12,
+                                             'executed_bf16_pflops':
+                                             sum(products[k_] * dense_flops * kev[k_]['launches'] for k_ in dense) /
+                                             (sum(kev[k_]['total_ms'] for k_ in dense) * 1e-3) / 1e15,
+                                             'frac_of_bf16_peak':
+                                             sum(products[k_] * dense_flops * kev[k_]['launches'] for k_ in dense) /
+                                             (sum(kev[k_]['total_ms'] for k_ in dense) * 1e-3) / 1e12 /
+                                             PEAK_BF16_MFMA_TFLOPS}
+                                            if (mode in ('x6', 'h3', 'bf16') and dense) else None),
+                        'conv_direct_form_tflops': {k_: conv_flops / (kev[k_]['mean_ms'] * 1e-3) / 1e12
+                                                    for k_ in ('tvae_conv1_fwd', 'tvae_conv1_wgrad') if k_ in kev}}
         out = {
             'metric': ('training images/sec (fwd+bwd+Adam), P8 z=2 64x64 bs=256/GPU' if args.workload == 'S64' else
                        'training images/sec (fwd+bwd+Adam), extra workload ' + args.workload) +
@@ -778,47 +861,9 @@ def main():
                                          * 2 * c['C'] * c['R'] * 2 * c['k'] * c['cin'] * B * (c['n'] + 2 * c['pad'] - c['k'] + 1) / 1e9,
                                          conv_flops / 1e9)
                                         if conv_dft else 'direct implicit GEMM')},
-            'roofline': {'kernel': dom + ' (' + entries[dom][1] + ', ' + info['insn'] + ')', 'bound': 'mfma',
-                         'achieved': ach, 'peak': peak, 'unit': 'TFLOP/s',
-                         'frac': ach / peak,
-                         'peak_note': 'algorithmic (fp32-equivalent) FLOP/s; peak = 2500 TFLOP/s dense bf16 / bf16 MFMAs per '
-                                      'product block of this launch (dense_launches)' if mode in ('x6', 'h3', 'bf16') else
-                                      'dense f32 MFMA peak',
-                         'frac_of_f32_mfma_peak': ach / PEAK_F32_MFMA_TFLOPS,
-                         # dense_x6_kernel is launched with several shapes: pick the decoder-layer launch by its grid
-                         # (512 threads x 8*ceil(tiles_n/8) workgroups; forward and data-gradient launches averaged)
-                         'traffic': pmc_traffic(dom, 512 * 8 * ((Nt // 128 + 7) // 8) * ((c['hidden'] + 511) // 512)
-                                                if dom.startswith('tvae_linear') else None,
-                                                kernel=entries[dom][1].split()[0] if dom.startswith('tvae_linear') else None)
-                         if args.workload == 'S64' else None,
-                         'algorithmic_flops_per_launch': flops, 'mean_launch_ms': kev[dom]['mean_ms'],
-                         'launches_timed': kev[dom]['launches'],
-                         'entry_points_ms': {k_: round(v['mean_ms'], 3) for k_, v in sorted(timed.items())},
-                         'dense_launches': {k_: {'ms_per_step': round(kev[k_]['total_ms'] / args.steps, 3),
-                                                 'launches_per_step': kev[k_]['launches'] / args.steps,
-                                                 'bf16_mfma_per_product_block': products[k_],
-                                                 'mfma_per_block_as_launched': kev[k_].get('mfma_per_block_seen'),
-                                                 'mfma_per_block_expected_for_mode': products_by_mode[k_],
-                                                 'algorithmic_tflops': dense_flops * kev[k_]['launches'] /
-                                                 (kev[k_]['total_ms'] * 1e-3) / 1e12,
-                                                 'executed_bf16_pflops': products[k_] * dense_flops * kev[k_]['launches'] /
-                                                 (kev[k_]['total_ms'] * 1e-3) / 1e15,
-                                                 'frac_of_bf16_peak': products[k_] * dense_flops * kev[k_]['launches'] /
-                                                 (kev[k_]['total_ms'] * 1e-3) / 1e12 / PEAK_BF16_MFMA_TFLOPS}
-                                            for k_ in dense} if mode in ('x6', 'h3', 'bf16') else None,
-                         'dense_aggregate': ({'algorithmic_tflops': sum(dense_flops * kev[k_]['launches'] for k_ in dense) /
-                                              (sum(kev[k_]['total_ms'] for k_ in dense) * 1e-3) / 1e12,
-                                              'executed_bf16_pflops':
-                                              sum(products[k_] * dense_flops * kev[k_]['launches'] for k_ in dense) /
-                                              (sum(kev[k_]['total_ms'] for k_ in dense) * 1e-3) / 1e15,
-                                              'frac_of_bf16_peak':
-                                              sum(products[k_] * dense_flops * kev[k_]['launches'] for k_ in dense) /
-                                              (sum(kev[k_]['total_ms'] for k_ in dense) * 1e-3) / 1e12 /
-                                              PEAK_BF16_MFMA_TFLOPS}
-                                             if (mode in ('x6', 'h3', 'bf16') and dense) else None),
-                         'conv_direct_form_tflops': {k_: conv_flops / (kev[k_]['mean_ms'] * 1e-3) / 1e12
-                                                     for k_ in ('tvae_conv1_fwd', 'tvae_conv1_wgrad') if k_ in kev}},
         }
+        if roofline is not None:
+            out['roofline'] = roofline
         if strong is not None:
             out['strong_scaling'] = strong
         if small_batch is not None:
@@ -839,7 +884,7 @@ def main():
             out['bf16_throughput_mode'] = companion_bf16
         if companion_graph is not None:
             out['graph_replay_mode'] = companion_graph
-        if world == 1 and not args.no_cpu_baseline and args.workload == 'S64':
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == 'S64':
             out['cpu_baseline'] = cpu_baseline()
         else:
             out['cpu_baseline'] = None

@@ -16,7 +16,8 @@ PY
 done
 for r in $(seq $R); do
   for t in $A $B; do
-    (cd $ROOT/$t && python3 bench.py --no-cpu-baseline --no-f32-companion --steps 10 --warmup 3 2>/dev/null | python3 -c "
+    FULL=$(grep -q "'--full'" $ROOT/$t/bench.py && echo --full)    # trees older than the option print the roofline by default
+    (cd $ROOT/$t && python3 bench.py $FULL --no-cpu-baseline --no-f32-companion --steps 10 --warmup 3 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$t', '%.3f ms/step' % d['ms_per_step'], {k: round(v,3) for k,v in d['roofline']['entry_points_ms'].items()})")

@@ -12,6 +12,7 @@ Noise replay: the reference draws, per step, `empty(B,P).exponential_()` (models
 we pre-draw the same three tensors under the same seed and store them.
 
 Usage:  python tests/golden/make_goldens.py        (writes next to this file)
+        MKL_CBWR=COMPATIBLE python tests/golden/make_goldens.py mkl_generic    (the *_mklgeneric.npz overlays)
 """
 import os
 import sys
@@ -706,9 +707,39 @@ def gen_cli():
     print('wrote', path, {k: len(v) for k, v in out.items()})
 
 
+MKL_GENERIC = ('step_particles64_P8', 'trajectory_20steps')
+
+
+def gen_mkl_generic():
+    """The outputs of MKL_GENERIC recomputed on MKL's generic float32 path, the one MKL takes on non-Intel CPUs (and on Intel
+    under MKL_CBWR=COMPATIBLE, which this mode requires): written as <name>_mklgeneric.npz with only the arrays that differ
+    from <name>.npz (the inputs are identical); tests/test_oracle_golden.py overlays them where MKL runs that path.  For
+    these two fixtures the two paths differ by more than the tests' tolerances (conv1.weight gradient 2.6e-4, trajectory
+    KL 4.3e-4); every other fixture holds on both."""
+    assert os.environ.get('MKL_CBWR', '').upper().startswith('COMPATIBLE'), 'run with MKL_CBWR=COMPATIBLE'
+    global save
+    base_save = save
+
+    def save_diff(name, **arrs):
+        if name not in MKL_GENERIC:
+            return
+        base = np.load(os.path.join(HERE, name + '.npz'))
+        new = npd(arrs)
+        assert sorted(new) == sorted(base.files), name
+        diff = {k: v for k, v in new.items() if not np.array_equal(v, base[k])}
+        base_save(name + '_mklgeneric', **diff)
+
+    save = save_diff
+    try:
+        gen_steps()
+        gen_trajectory()
+    finally:
+        save = base_save
+
+
 if __name__ == '__main__':
     which = sys.argv[1:] or ['bank', 'groupconv', 'encoder', 'decoder', 'steps', 'epoch', 'cli', 'particles_tail', 'get_latent', 'mrc', 'secondary', 'hotpath', 'trajectory', 'wide']
     which = [w for w in which if not w.startswith('hot_')]
     for w in which:
         {'bank': gen_bank, 'groupconv': gen_groupconv, 'encoder': gen_encoder, 'decoder': gen_decoder,
-         'steps': gen_steps, 'epoch': gen_epoch, 'cli': gen_cli, 'particles_tail': gen_particles_tail, 'get_latent': gen_get_latent, 'mrc': gen_mrc, 'secondary': gen_secondary, 'hotpath': gen_hotpath, 'trajectory': gen_trajectory, 'wide': gen_wide}[w]()
+         'steps': gen_steps, 'epoch': gen_epoch, 'cli': gen_cli, 'particles_tail': gen_particles_tail, 'get_latent': gen_get_latent, 'mrc': gen_mrc, 'secondary': gen_secondary, 'hotpath': gen_hotpath, 'trajectory': gen_trajectory, 'wide': gen_wide, 'mkl_generic': gen_mkl_generic}[w]()

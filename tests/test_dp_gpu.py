@@ -295,8 +295,8 @@ def test_bench_two_rank_rehearsal_on_one_gpu():
     env = {k_: v for k_, v in os.environ.items() if k_ not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
     env['TVAE_BENCH_REHEARSE'] = '1'
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                        '--workload', 'S28', '--batch', '32', '--no-cpu-baseline'], capture_output=True, text=True, timeout=800,
-                       env=env)
+                        '--workload', 'S28', '--batch', '32', '--no-cpu-baseline', '--full'], capture_output=True, text=True,
+                       timeout=800, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
     assert line['n_gpus'] == 2 and line['config']['global_batch'] == 64 and line['value'] > 0

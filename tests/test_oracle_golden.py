@@ -13,6 +13,30 @@ from oracle import tvae_oracle as O
 TOL = 2e-5   # oracle restates the same ATen CPU ops; only summation order differs
 
 
+def mkl_generic_path():
+    """True where MKL runs its generic float32 kernels: on every non-Intel CPU (MKL takes its AVX2 / AVX-512 paths on Intel
+    only) and on Intel under MKL_CBWR=COMPATIBLE."""
+    if os.environ.get('MKL_CBWR', '').upper().startswith('COMPATIBLE'):
+        return True
+    try:
+        with open('/proc/cpuinfo') as f:
+            vendor = next((ln.split(':', 1)[1].strip() for ln in f if ln.startswith('vendor_id')), '')
+    except OSError:
+        vendor = ''
+    return vendor != 'GenuineIntel'
+
+
+def load_golden_for_host(name):
+    """load_golden, with the reference's outputs on the MKL code path this host runs.  On MKL's generic path the reference
+    itself moves step_particles64_P8's conv1.weight gradient by 2.6e-4 and the trajectory's KL by up to 4.3e-4 (ELBO
+    1.6e-5) -- past the 2e-4 / 1e-4 / 1e-5 these tests hold the oracle to -- so those outputs are also stored as recomputed
+    on that path (<name>_mklgeneric.npz: the arrays that differ; make_goldens.py mkl_generic) and used there."""
+    fx = load_golden(name)
+    if mkl_generic_path() and os.path.exists(os.path.join(GOLDEN, name + '_mklgeneric.npz')):
+        fx.update(load_golden(name + '_mklgeneric'))
+    return fx
+
+
 @pytest.mark.parametrize('path', sorted(glob.glob(os.path.join(GOLDEN, 'bank_*.npz'))))
 def test_bank(path):
     fx = load_golden(os.path.basename(path)[:-4])
@@ -122,7 +146,7 @@ def step_cfg(fx):
 
 @pytest.mark.parametrize('name', sorted(STEP_LIK))
 def test_step(name):
-    fx = load_golden(name)
+    fx = load_golden_for_host(name)
     cfg, n = step_cfg(fx)
     enc = tdict(fx, 'e.', requires_grad=True)
     gen = tdict(fx, 'd.', requires_grad=True)
@@ -208,7 +232,7 @@ def test_trajectory_20_steps():
     of its gradient, so elements whose gradient is rounding noise (dead hidden units, filter corners) walk +-lr per step
     in a direction no two fp32 evaluations agree on -- measured between the reference and this oracle, both on the CPU:
     relative L2 error of the update up to 9.4e-3 (decoder first layers), cosine >= 0.99995.  Gate: 2e-2 / cosine 0.999."""
-    fx = load_golden('trajectory_20steps')
+    fx = load_golden_for_host('trajectory_20steps')
     cfg, n = step_cfg(fx)
     enc = tdict(fx, 'e.', requires_grad=True)
     gen = tdict(fx, 'd.', requires_grad=True)
