@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -331,17 +331,15 @@ def _scratch(device, key, floats: int) -> torch.Tensor:
     return t
 
 
-# Routing switches.  Two can be set from the environment (each is kept alive by a test): TVAE_CONV_DFT=0 -- the direct split-pipe
-# convolution instead of the frequency-domain one (bench.py's conv_direct_form line; tests/test_hip_modules.py runs the direct
-# kernels through geometries the DFT plan rejects); TVAE_DEC_PAD=0 -- no padding of 28 x 28 / 50 x 50 pixel ranges to the GEMM
-# tile (test_decoder_pads_pixel_ranges_to_the_gemm_tile flips it).  The FUSE_* names below were environment switches while
-# their fusions were being A/B'd (rounds 2-5; profiles/README.md has every measurement); all of them won and are plain
-# constants now -- the unfused branches they guard remain as the paths of shapes the fused kernels do not cover, and
-# FUSE_ENC_TAIL is still flipped by tests/test_hip_modules.py::test_encoder_tail_paths_agree.
+# Routing switches, each kept alive by a test: TVAE_CONV_DFT=0 -- the direct split-pipe convolution instead of the
+# frequency-domain one (bench.py's conv_direct_form line; tests/test_hip_modules.py runs the direct kernels through
+# geometries the DFT plan rejects); FUSE_ENC_TAIL = False -- the unfused encoder tail (test_encoder_tail_paths_agree); at the
+# decoder, TVAE_DEC_PAD=0 -- no padding of 28 x 28 / 50 x 50 pixel ranges to the GEMM tile
+# (test_decoder_pads_pixel_ranges_to_the_gemm_tile) and TVAE_DEC_LD_PAD (test_decoder_padded_row_stride_is_layout_only).
+# Every other fusion of rounds 2-6 won its A/B (profiles/README.md has every measurement) and is unconditional; the unfused
+# branches remain as the paths of shapes the fused kernels do not cover.
 CONV_DFT = os.environ.get('TVAE_CONV_DFT', '1') != '0'
-FUSE_COLDOT = FUSE_IN_TAIL = FUSE_VIRT_GRAD = FUSE_VIRT_ACT = FUSE_SIGN_BITS = FUSE_ENC_TAIL = True
-FUSE_ROW_SUMS = FUSE_ENC_WGRAD = FUSE_NO_H = True
-H3_DEEP = True           # round 6: measured bounds -> h3 for every hidden decoder layer (test_deep_decoder_runs_h3_on_measured_bounds)
+FUSE_ENC_TAIL = True
 
 
 def _use_dft(B, Cin, n, k, pad, C, R) -> bool:
@@ -603,7 +601,7 @@ class EncoderFn(torch.autograd.Function):
                      LRELU_SLOPE, p_e)
         # conv2's weight gradient in one pass from A1, the head gradients and the sign words of H (dH is formed inside the
         # GEMM's operand build and never written); dWh / db2 from a sums-only pass over H
-        fuse_w = ctx.bits is not None and FUSE_ENC_WGRAD and nh <= SKINNY_MAX and N % 32 == 0 and not wide_bw
+        fuse_w = ctx.bits is not None and nh <= SKINNY_MAX and N % 32 == 0 and not wide_bw
         if not fuse_w and dH is None:
             dH = torch.empty(C2, N, dtype=torch.float32, device=y.device)
         # wide tail in h3: both weight gradients as cooperative reductions over two stored operands (enc_tail_wgrad_plain_kernel)
@@ -882,6 +880,45 @@ class CoordFn(torch.autograd.Function):
 
 
 DEC_PAD = os.environ.get('TVAE_DEC_PAD', '1') != '0'
+DEC_LD_PAD = int(os.environ.get('TVAE_DEC_LD_PAD', '64'))
+
+
+class DecoderRoute(NamedTuple):
+    """Every structural decision of DecoderFn, taken once by decoder_route() in the forward and kept on ctx: the backward
+    routes by it, so the two passes cannot disagree about what was stored, and with which row stride."""
+    ldn: int             # row stride (floats) of every stored [features][B*Np] tensor
+    split: bool          # hidden layers on the split pipe (tvae_linear_*_x6)
+    four_x6: bool        # Fourier first layer on the split pipe, latent rows z[img(n)] joining the reduction
+    four_dgrad_x6: bool  # its data gradient on the split pipe (Ff rows wide)
+    virt_act: bool       # coordinate layer recomputed by its consumers, never stored; its backward in the first dgrad
+    fused_out: bool      # the single-output Linear applied by the last hidden layer's launch
+    virt_grad: bool      # last hidden layer's gradient Wo[f] gy[n] act'(h) re-formed by its consumers, never stored
+    sign_bits: bool      # ... and [h > 0] kept as bits for it (two-valued form)
+    no_h: bool           # last hidden activation neither stored nor read; its row sums come from the data gradient
+    h3: bool             # two-part arithmetic with bound words for the operands streamed from memory
+    infer: bool          # inference-mode forward: nothing is kept for a backward
+
+
+def decoder_route(B: int, Np: int, F_: int, n_hidden: int, n_out: int, act: int, resid: bool, Ff: int,
+                  infer: bool) -> DecoderRoute:
+    """The route of DecoderFn for B images of Np pixels, F_ hidden units, Ff Fourier features (0: none) in the current
+    arithmetic.  Pure: no tensor, no launch."""
+    Nt = B * Np
+    split = _dense_x6_ok(F_, Nt)
+    virt_grad = n_hidden >= 1 and n_out == 1 and not resid and split
+    sign_bits = virt_grad and act == ACT_LRELU
+    # Row stride: the decoders that STORE activations and gradients (Fourier first layer, two or more hidden layers) stream
+    # them again as the panels of their weight gradients; with a power-of-two column count (galaxy: 8 x 128^2 = 2^17) the 512
+    # rows of a panel sit 2^19 bytes apart, every one in the same sets of the L2, and the four workgroups that share a panel
+    # each fetch it again (1.88 GB fetched for 0.54 GB, profiles/r06_wgrad_probe.txt).  DEC_LD_PAD floats of padding per row
+    # take the rows off that spacing.
+    ld_pad = DEC_LD_PAD and (Ff or n_hidden >= 2) and Nt % 16384 == 0 and split      # (rows >= 64 KB x k apart)
+    return DecoderRoute(
+        ldn=Nt + DEC_LD_PAD if ld_pad else Nt, split=split, four_x6=bool(Ff) and split,
+        four_dgrad_x6=bool(Ff) and _dense_x6_ok(Ff, Nt),
+        virt_act=not Ff and n_hidden >= 1 and not resid and F_ <= 512 and Np % 128 == 0 and split,
+        fused_out=n_hidden >= 1 and n_out == 1 and F_ <= 512 and split, virt_grad=virt_grad, sign_bits=sign_bits,
+        no_h=sign_bits and F_ <= 512, h3=parts() == 2 and split, infer=infer)
 
 
 def decoder_padded_pixels(Np: int, B: int, F_: int, n_hidden: int, n_out: int, resid: bool, fourier: bool, act: int) -> int:
@@ -893,24 +930,10 @@ def decoder_padded_pixels(Np: int, B: int, F_: int, n_hidden: int, n_out: int, r
     pixel count, or 0 when the decoder should run as it is (src/models.py: SpatialGenerator.forward pads around DecoderFn, so
     autograd differentiates the padding)."""
     Np_p = (Np + 127) // 128 * 128
-    if (not DEC_PAD or Np % 128 == 0 or fourier or resid or n_hidden < 1 or n_out != 1 or act != ACT_LRELU or
-            not (256 <= F_ <= 512) or Np_p > 1.15 * Np or not (FUSE_VIRT_ACT and FUSE_IN_TAIL) or not _dense_x6_ok(F_, B * Np_p)):
+    if (not DEC_PAD or Np % 128 == 0 or n_out != 1 or act != ACT_LRELU or Np_p > 1.15 * Np or
+            not decoder_route(B, Np_p, F_, n_hidden, n_out, act, resid, int(fourier), False).virt_act):
         return 0
     return Np_p
-
-
-DEC_LD_PAD = int(os.environ.get('TVAE_DEC_LD_PAD', '64'))
-
-
-def _dec_ld(Nt: int, F_: int, n_hidden: int, fourier: bool) -> int:
-    """Row stride (floats) of the decoder's stored [features][B*Np] tensors.  The decoders that STORE activations and gradients
-    (Fourier first layer, two or more hidden layers) stream them again as the panels of their weight gradients; with a
-    power-of-two column count (galaxy: 8 x 128^2 = 2^17) the 512 rows of a panel sit 2^19 bytes apart, every one in the same
-    sets of the L2, and the four workgroups that share a panel each fetch it again (1.88 GB fetched for 0.54 GB,
-    profiles/r06_wgrad_probe.txt).  64 floats of padding per row take the rows off that spacing."""
-    if DEC_LD_PAD and (fourier or n_hidden >= 2) and Nt % 16384 == 0 and _dense_x6_ok(F_, Nt):      # (rows >= 64 KB x k apart)
-        return Nt + DEC_LD_PAD
-    return Nt
 
 
 class DecoderFn(torch.autograd.Function):
@@ -935,17 +958,16 @@ class DecoderFn(torch.autograd.Function):
                 all(tuple(W.shape) == (F_, F_) for W, _ in hidden), 'decoder parameter shapes are inconsistent')
         _expect(Wl is None or (z is not None and tuple(z.shape) == (B, Wl.shape[1])), 'latent z does not match latent_linear')
         dev = xr.device
-        infer = _INFER
+        rt = decoder_route(B, Np, F_, n_hidden, n_out, act, resid, Wf.shape[0] if Wf is not None else 0, _INFER)
+        ldn = rt.ldn
         LB = None
-        ldn = _dec_ld(Nt, F_, n_hidden, Wf is not None)
         if ldn != Nt:
             _note('dec.ld_pad')
-        # Fourier-feature first layer on the split pipe: the per-image latent term joins the reduction (rows z[img(n)] under
-        # the features, weights [Wc | Wl]) instead of being a per-image bias
-        four_x6 = Wf is not None and _dense_x6_ok(F_, Nt)
+        # Fourier-feature first layer on the split pipe (four_x6): the per-image latent term joins the reduction (rows
+        # z[img(n)] under the features, weights [Wc | Wl]) instead of being a per-image bias
         if Wl is not None:
             z = z.contiguous()
-        if Wl is not None and not four_x6:
+        if Wl is not None and not rt.four_x6:
             zd = Wl.shape[1]
             LB = torch.empty(B, F_, dtype=torch.float32, device=dev)
             call('tvae_latent_bias', Wl.contiguous(), z, LB, B, F_, zd)
@@ -953,28 +975,26 @@ class DecoderFn(torch.autograd.Function):
         feat_amax = h_bound = h_rows = None       # h3 bounds of operands that are streamed from memory (include/tvae_hip.h: x_amax)
         # without Fourier features the coordinate layer's output is two FMAs and an activation per element: the layers
         # that consume it (first hidden layer: forward, mask of the data gradient, weight gradient) recompute it and the
-        # [hid][B*n^2] tensor is never written or read
-        virt_act = (FUSE_VIRT_ACT and FUSE_IN_TAIL and Wf is None and n_hidden >= 1 and not resid and 256 <= F_ <= 512
-                    and Np % 128 == 0 and Nt >= 32 and _dense_x6_ok(F_, Nt))
-        va = (xr.view(Nt, 2), Wc.contiguous(), bc, LB, Np) if virt_act else None
-        h = None if virt_act else torch.empty(F_, ldn, dtype=torch.float32, device=dev)
-        if virt_act:
+        # [hid][B*n^2] tensor is never written or read (virt_act)
+        va = (xr.view(Nt, 2), Wc.contiguous(), bc, LB, Np) if rt.virt_act else None
+        h = None if rt.virt_act else torch.empty(F_, ldn, dtype=torch.float32, device=dev)
+        if rt.virt_act:
             _note('dec.virt_act')
         elif Wf is not None:
             Ff = Wf.shape[0]
-            zx = Wl.shape[1] if (four_x6 and Wl is not None) else 0
+            zx = Wl.shape[1] if (rt.four_x6 and Wl is not None) else 0
             feat_all = torch.empty(Ff + zx, ldn, dtype=torch.float32, device=dev)
             feat = feat_all[:Ff]
             call('tvae_fourier_fwd', xr, Wf.contiguous(), bf.contiguous(), sigma, feat, ldn, Ff, Nt)
-            if four_x6:
+            if rt.four_x6:
                 _note('dec.four_x6')
                 if zx:
                     feat_all[Ff:, :Nt].view(zx, B, Np).copy_(z.contiguous().t().unsqueeze(2).expand(zx, B, Np))
                 Wfull = torch.cat([Wc, Wl], 1) if zx else Wc
                 # h3 (round 4): the streamed operand is cos(.) <= 1 over the latent rows: its bound max(1, max |z|) is known
                 # without looking at it; the layer's OUTPUT is then bounded by the largest absolute row sum of the weights
-                p_c = parts() if parts() != 2 else 2
-                if p_c == 2:
+                p_c = parts()
+                if rt.h3:
                     feat_amax = torch.clamp(_inf_norm(z), min=1.0) if zx else torch.ones(1, dtype=torch.float32, device=dev)
                     # per-unit bound of this layer's output (the weight gradient of the layer BEHIND it takes one
                     # scale per row of its X operand = per unit here), and its maximum for the forward of that layer
@@ -984,94 +1004,80 @@ class DecoderFn(torch.autograd.Function):
                 w3c = _split_weight(Wfull, F_, Ff + zx, False, 'x6_dense_wc', nparts=p_c)
                 with _timed('tvae_linear_fwd_x6', p_c):
                     call('tvae_linear_fwd_x6', w3c, feat_all, bc, None, h, F_, Nt, Ff + zx, ldn, ldn, act, LRELU_SLOPE,
-                         None, None, None, None, None, None, None, 0, None, p_c, feat_amax if p_c == 2 else None)
+                         None, None, None, None, None, None, None, 0, None, p_c, feat_amax)
             else:
                 call('tvae_linear_fwd', Wc.contiguous(), feat, bc, LB, Np, None, h, F_, Nt, Ff, ldn, ldn, act, LRELU_SLOPE)
         else:
             call('tvae_dec_l0_fwd', xr, Wc.contiguous(), bc, LB, h, ldn, F_, Nt, Np, act, LRELU_SLOPE)
-            if parts() == 2 and _dense_x6_ok(F_, Nt):      # the stored coordinate layer: |act(pre)| <= |pre| <= this bound
+            if rt.h3:                                  # the stored coordinate layer: |act(pre)| <= |pre| <= this bound
                 h_rows = _inf_norm(xr) * Wc.detach().abs().sum(1) + \
                     ((bc.detach()[None, :] + LB).abs().amax(0) if LB is not None else bc.detach().abs())      # per unit
                 h_bound = h_rows.amax().reshape(1)
         hs = [h]
         yh = torch.empty(B, Np, n_out, dtype=torch.float32, device=dev)
-        fused_out = False
         sbits = None
         # Round 6: every hidden layer whose input is a STORED activation runs h3 -- the launch that stores hs[l] also leaves
         # max |hs[l]| in a word (tvae_linear_fwd_x6 y_amax, atomic max from its epilogue), the measured bound of the launch that
         # streams it next (forward here, weight gradient in the backward).  An analytic row-sum chain would lose ~5 bits of
         # fp16's exponent headroom per layer; a measured maximum loses none, whatever the depth.
-        meas_words = torch.zeros(max(n_hidden, 1), dtype=torch.float32, device=dev) if (
-            H3_DEEP and parts() == 2 and n_hidden >= 2 and _dense_x6_ok(F_, Nt)) else None
+        meas_words = torch.zeros(max(n_hidden, 1), dtype=torch.float32, device=dev) if (rt.h3 and n_hidden >= 2) else None
         h_meas = [None] * (n_hidden + 1)          # h_meas[l]: measured max |hs[l]| (one device word) or None
         rows_l = h_rows                           # per-unit bound of hs[l] by the row-sum chain (None: not available)
         rows_all = [rows_l]
         for li, (W, b) in enumerate(hidden):
             hn = None
-            if _dense_x6_ok(F_, Nt):
+            last = li == n_hidden - 1
+            if rt.split:
                 # h3 instances: the layer whose streamed operand is the recomputed first-layer activation, or (round 4) the
                 # stored output of the first layer under its bound, or (round 6) a deeper layer's stored input under its
                 # measured maximum
-                h3_mem = parts() == 2 and not (va and li == 0) and (
+                h3_mem = rt.h3 and not (va and li == 0) and (
                     (li == 0 and h_bound is not None and not resid) or (li > 0 and h_meas[li] is not None))
                 x_bound = (h_bound if li == 0 else h_meas[li]) if h3_mem else None
-                p_l = 2 if (parts() == 2 and ((va and li == 0) or h3_mem)) else _p3()
+                p_l = 2 if (rt.h3 and ((va and li == 0) or h3_mem)) else _p3()
                 if h3_mem:
                     _note('dec.hidden_h3_mem' if li == 0 else 'dec.hidden_h3_meas')
                 w3 = _split_weight(W, F_, F_, False, 'x6_dense_w', nparts=p_l)
                 # the last hidden layer also applies the single-output Linear that follows it (one pass less over h)
-                fuse = FUSE_COLDOT and li == n_hidden - 1 and n_out == 1 and F_ <= 512
+                fuse = last and rt.fused_out
                 # the backward of the single-output Linear behind the last hidden layer needs only the SIGN of this
                 # layer's LeakyReLU output (two-valued implicit gradient): one bit per element, stored by this launch
-                bits_ok = (li == n_hidden - 1 and FUSE_SIGN_BITS and FUSE_VIRT_GRAD and n_out == 1 and not resid
-                           and act == ACT_LRELU and F_ >= 256 and Nt % 32 == 0)
-                if bits_ok and not infer:
+                if last and rt.sign_bits and not rt.infer:
                     sbits = torch.empty(F_, Nt // 32, dtype=torch.int32, device=dev)
                     _note('dec.sign_bits')
                 # Round 4: with the fused output dot AND the sign bits, nothing downstream needs this layer's activation
                 # itself -- the backward takes [H > 0] from the bits and dWo from the identity sum_k W[m][k] G[m][k] +
                 # b[m] g0[m] (include/tvae_hip.h: tvae_linear_dgrad_x6 vg_bits) -- so the 2.1 GB tensor is neither written
-                # here nor read there.  Same conditions as the backward's row-sum fusion (it forms g0).
-                # (inference: same launch without the bits -- only the fused output dot leaves it)
-                no_h = (FUSE_NO_H and fuse and (sbits is not None or (infer and bits_ok)) and li == n_hidden - 1 and
-                        FUSE_ROW_SUMS and F_ <= 512 and Nt % 128 == 0 and not resid)
-                if no_h:
-                    _note('dec.no_h_inference' if infer else 'dec.no_h')
+                # here nor read there.  (inference: same launch without the bits -- only the fused output dot leaves it)
+                if last and rt.no_h:
+                    _note('dec.no_h_inference' if rt.infer else 'dec.no_h')
                 else:
                     hn = torch.empty(F_, ldn, dtype=torch.float32, device=dev)
                 # this layer's output feeds another hidden layer: leave its maximum for that launch
-                emit = (meas_words[li:li + 1] if (meas_words is not None and li + 1 < n_hidden and hn is not None and not fuse)
-                        else None)
+                emit = meas_words[li:li + 1] if (meas_words is not None and not last) else None
                 with _timed('tvae_linear_fwd_x6', p_l):
                     call('tvae_linear_fwd_x6', w3, hs[-1], b, hs[-1] if resid else None, hn, F_, Nt, F_, ldn, ldn, act,
                          LRELU_SLOPE, Wo.contiguous() if fuse else None, bo if fuse else None, yh if fuse else None,
-                         *(va if va and li == 0 else (None, None, None, None, 0)), sbits if li == n_hidden - 1 else None,
-                         p_l, x_bound, emit)
+                         *(va if va and li == 0 else (None, None, None, None, 0)), sbits, p_l, x_bound, emit)
                 h_meas[li + 1] = emit
-                if rows_l is not None and parts() == 2:      # |act(W h + b [+ h])| <= |W| rows + |b| [+ rows], unit by unit
-                    rows_l = torch.addmv(b.detach().abs(), W.detach().abs(), rows_l) + (rows_l if resid else 0.0)
-                else:
-                    rows_l = None
-                rows_all.append(rows_l)
-                fused_out = fuse
                 _note('dec.fused_out' if fuse else 'dec.hidden_x6')
             else:
                 hn = torch.empty(F_, ldn, dtype=torch.float32, device=dev)
                 call('tvae_linear_fwd', W.contiguous(), hs[-1], b, None, 1, hs[-1] if resid else None, hn, F_, Nt, F_,
                      ldn, ldn, act, LRELU_SLOPE)
-                rows_l = None
-                rows_all.append(None)
+            if rows_l is not None:                     # |act(W h + b [+ h])| <= |W| rows + |b| [+ rows], unit by unit
+                rows_l = torch.addmv(b.detach().abs(), W.detach().abs(), rows_l) + (rows_l if resid else 0.0)
+            rows_all.append(rows_l)
             hs.append(hn)
-        if not fused_out:
+        if not rt.fused_out:
             call('tvae_coldot', hs[-1], ldn, F_, Nt, Wo.contiguous(), 1, F_, bo, n_out, yh)
-        if infer:
+        if rt.infer:
             return yh
-        ctx.save_for_backward(xr, z if Wl is not None else None, feat, LB if virt_act else None, *hs,
+        ctx.save_for_backward(xr, z if Wl is not None else None, feat, LB if rt.virt_act else None, *hs,
                               *[p for p in params if p is not None])
         ctx.meta = (act, resid, sigma, n_hidden, Wl is not None, Wf is not None, B, Np)
         ctx.arith = get_gemm_mode()
-        ctx.sbits = sbits
-        ctx.h_bound, ctx.feat_amax, ctx.h_rows = h_bound, feat_amax, h_rows
+        ctx.route, ctx.sbits = rt, sbits
         ctx.h_meas, ctx.rows_all = h_meas, rows_all
         return yh
 
@@ -1079,6 +1085,7 @@ class DecoderFn(torch.autograd.Function):
     @_in_forward_arithmetic
     def backward(ctx, gy):
         act, resid, sigma, n_hidden, has_l, has_f, B, Np = ctx.meta
+        rt = ctx.route
         sv = list(ctx.saved_tensors)
         xr, z, feat, LB = sv[0], sv[1], sv[2], sv[3]
         hs = sv[4:4 + n_hidden + 1]
@@ -1092,7 +1099,7 @@ class DecoderFn(torch.autograd.Function):
         Nt = B * Np
         F_, n_out = Wc.shape[0], Wo.shape[0]
         dev = xr.device
-        ldn = _dec_ld(Nt, F_, n_hidden, has_f)           # (row stride of every stored [features][Nt] tensor, as in forward)
+        ldn = rt.ldn                                     # (row stride of every stored [features][Nt] tensor)
         gy = gy.contiguous().view(Nt, n_out)
         gy_max = []                                      # max |gy|, formed once (one reduction over the output gradient) on first use
 
@@ -1100,41 +1107,44 @@ class DecoderFn(torch.autograd.Function):
             if not gy_max:
                 gy_max.append(_inf_norm(gy))
             return gy_max[0]
+
+        def in_bound(li):
+            """Bound of hidden layer li's stored input (None: none): the first layer's analytic per-unit bound, or a deeper
+            layer's measured maximum, capped unit by unit by the row-sum chain where the forward formed it (a unit far below
+            the others keeps its own scale)."""
+            if li == 0:
+                return ctx.rows_all[0]
+            m, r = ctx.h_meas[li], ctx.rows_all[li]
+            return m if (m is None or r is None) else torch.minimum(r, m)
         # last layer: one pass over h gives d (pre-activation gradient), its row sums and dWo
         gyT = gy.t().contiguous()
         dbo = _rowsum(gyT, n_out, Nt)
         # with a single output the gradient of the last hidden activation, Wo[f] gy[n] act'(h[f][n]), is cheap to
         # re-form inside the two GEMMs that consume it: it is then never written (dec_out_bwd only produces row sums)
-        virt = (FUSE_VIRT_GRAD and n_out == 1 and n_hidden >= 1 and not resid and _dense_x6_ok(F_, Nt) and F_ >= 256
-                and Nt % 16 == 0)
-        d = None if virt else torch.empty(F_, ldn, dtype=torch.float32, device=dev)
+        d = None if rt.virt_grad else torch.empty(F_, ldn, dtype=torch.float32, device=dev)
         tot = torch.empty(1 + n_out, F_, dtype=torch.float32, device=dev)
-        # two-valued implicit gradient: the data-gradient launch of the last hidden layer streams H anyway and returns the
-        # two row sums this layer's backward needs of it (tot[0] = bias gradient below, tot[1] = dWo): no pass of its own
-        fuse_rs = (FUSE_ROW_SUMS and virt and act == ACT_LRELU and F_ <= 512 and Nt % 128 == 0)
-        no_h = hs[-1] is None                            # the forward did not store the last hidden activation (dec.no_h)
-        _expect(not no_h or (fuse_rs and ctx.sbits is not None), 'decoder backward without the saved activation needs the bits path')
-        if not fuse_rs:
+        # two-valued implicit gradient without the saved activation: the data-gradient launch of the last hidden layer
+        # streams the sign bits anyway and returns the two row sums this layer's backward needs (tot[0] = bias gradient
+        # below, tot[1] = dWo): no pass of its own
+        if not rt.no_h:
             part = workspace(dev, ((Nt + 1023) // 1024) * F_ * (1 + n_out))
             call('tvae_dec_out_bwd', gy, n_out, Wo.contiguous(), hs[-1], ldn, d, ldn, F_, Nt, act, LRELU_SLOPE, part,
                  part.numel(), tot)
         else:
             _note('dec.row_sums_in_dgrad')
-        vg = (Wo.contiguous().view(-1), gy.view(-1), act) if virt else None
-        if virt:
+        vg = (Wo.contiguous().view(-1), gy.view(-1), act) if rt.virt_grad else None
+        if rt.virt_grad:
             _note('dec.virt_grad')
         dWo, drow = tot[1:], tot[0]
         grads_hidden = []
-        fused_in = False
         # Round 6 (h3 for every hidden layer): one bound word per stored gradient tensor -- the top one analytically
         # (|d[m][n]| <= max_m sum_o |Wo[o][m]| max |gy|: act' <= 1), every later one measured by the data-gradient launch that
         # stores it (tvae_linear_dgrad_x6 y_amax)
-        h3_deep = H3_DEEP and parts() == 2 and _dense_x6_ok(F_, Nt)
         # (words for the measured maxima: only where a stored gradient is streamed again -- a second hidden layer, or the Fourier
         #  first layer behind the first one; the single-hidden-layer configurations need none and launch no fill)
-        dmeas = torch.zeros(n_hidden + 1, dtype=torch.float32, device=dev) if (h3_deep and (n_hidden >= 2 or has_f)) else None
+        dmeas = torch.zeros(n_hidden + 1, dtype=torch.float32, device=dev) if (rt.h3 and (n_hidden >= 2 or has_f)) else None
         d_bnd = None                                     # bound word of the stored gradient `d` (None: none / not stored)
-        if h3_deep and not virt:
+        if rt.h3 and not rt.virt_grad:
             d_bnd = (gy_amax() * Wo.detach().abs().sum(0).amax()).reshape(1)
         for li in range(n_hidden - 1, -1, -1):
             W, b = hidden[li]
@@ -1143,46 +1153,31 @@ class DecoderFn(torch.autograd.Function):
             dsrc = hs[-1] if use_vg else d             # implicit operand: pass the saved activation instead
             va = (xr.view(Nt, 2), Wc.contiguous(), bc, LB, Np) if hprev is None else None   # recomputed first layer
             sbits = ctx.sbits if (use_vg and act == ACT_LRELU) else None      # [h > 0] as stored bits (two-valued form)
-            from_bits = use_vg and no_h
-            # h3 with the layer's input read from memory (round 4): the stored first-layer output under its forward bound,
-            # times max |gy| (the operand of the two-valued form is gy[n] X[k][n])
-            xg_amax = None
-            if parts() == 2 and use_vg and sbits is not None and va is None and li == 0 and ctx.h_bound is not None:
-                # one bound per unit (row of the X operand) where the forward formed them, else the tensor's
-                xg_amax = (ctx.h_rows if ctx.h_rows is not None else ctx.h_bound) * gy_amax()      # (vg[1] is gy: n_out == 1)
-            elif parts() == 2 and use_vg and sbits is not None and va is None and li > 0 and ctx.h_meas[li] is not None:
-                # (round 6) a deeper layer's stored input under its measured maximum, capped per unit by the row-sum chain
-                xb_ = ctx.h_meas[li] if ctx.rows_all[li] is None else torch.minimum(ctx.rows_all[li], ctx.h_meas[li])
-                xg_amax = xb_ * gy_amax()
-            # plain form (both operands stored tensors) in h3: bound of d (one word) and of the layer's input -- the first
-            # layer's analytic per-unit bound, or a deeper layer's measured maximum (capped unit by unit by the row-sum chain
-            # where the forward formed it: a unit far below the others keeps its own scale)
-            plain_h3 = h3_deep and not use_vg and d_bnd is not None and va is None
-            xw_amax = None
+            # ... without the stored activation: the weight gradient also returns rowdot[m] = sum_k W[m][k] G[m][k] for dWo,
+            # and the data gradient below the two row sums of the layer behind
+            from_bits = use_vg and rt.no_h
+            # h3 with the layer's input read from memory, under its bound: the two-valued form (round 4; its operand is
+            # gy[n] X[k][n], so times max |gy| -- vg[1] is gy: n_out == 1), or the plain form of two stored tensors (round 6)
+            xb = in_bound(li) if (rt.h3 and va is None and (sbits is not None if use_vg else d_bnd is not None)) else None
+            plain_h3 = not use_vg and xb is not None
             if plain_h3:
-                if li == 0:
-                    xw_amax = ctx.h_rows if ctx.h_rows is not None else ctx.h_bound
-                elif ctx.h_meas[li] is not None:
-                    xw_amax = ctx.h_meas[li] if ctx.rows_all[li] is None else torch.minimum(ctx.rows_all[li], ctx.h_meas[li])
-            if from_bits:                              # + rowdot[m] = sum_k W[m][k] G[m][k] for dWo (the dgrad launch below)
-                dW, rowdot = _wgrad(None, hprev, F_, Nt, F_, vg, va, act, sbits, rowdot_w=W, x_amax=xg_amax, ld=ldn)
-            elif plain_h3 and xw_amax is not None:
                 _note('dec.wgrad_h3_meas')
-                dW, rowdot = _wgrad(dsrc, hprev, F_, Nt, F_, None, None, act, None, a_amax=d_bnd, x_amax=xw_amax, ld=ldn), None
-            else:
-                dW, rowdot = _wgrad(dsrc, hprev, F_, Nt, F_, vg if use_vg else None, va, act, sbits, x_amax=xg_amax, ld=ldn), None
+            elif xb is not None:
+                xb = xb * gy_amax()
+            wg = _wgrad(dsrc, hprev, F_, Nt, F_, vg if use_vg else None, va, act, sbits, rowdot_w=W if from_bits else None,
+                        a_amax=d_bnd if plain_h3 else None, x_amax=xb, ld=ldn)
+            dW, rowdot = wg if from_bits else (wg, None)
             db = drow if drow is not None else _rowsum(d, F_, Nt, ld=ldn)
             drow = None
-            # the data gradient of the FIRST hidden layer can feed the coordinate layer's backward from its epilogue
-            # (coordinate gradient + per-panel row sums); its result is then never written
-            fuse_in = (FUSE_IN_TAIL and li == 0 and not has_f and not resid and F_ <= 512 and Np % 128 == 0 and
-                       _dense_x6_ok(F_, Nt))
+            # the data gradient of the FIRST hidden layer behind a recomputed coordinate layer feeds that layer's backward
+            # from its epilogue (coordinate gradient + per-panel row sums); its result is then never written
+            fuse_in = li == 0 and rt.virt_act
             dprev = None if fuse_in else torch.empty(F_, ldn, dtype=torch.float32, device=dev)
-            if _dense_x6_ok(F_, Nt):
+            if rt.split:
                 # LeakyReLU: the implicit gradient in its two-valued form (3 MFMAs per block instead of 6)
                 two_val = use_vg and act == ACT_LRELU
                 # h3 instances: the exact 0 / 1 operand (two products), or (round 6) a stored gradient under its bound word
-                p_d = 2 if (parts() == 2 and (two_val or (not use_vg and d_bnd is not None))) else _p3()
+                p_d = 2 if (rt.h3 and (two_val or (not use_vg and d_bnd is not None))) else _p3()
                 if p_d == 2 and not two_val:
                     _note('dec.dgrad_h3_meas')
                 emit = dmeas[li:li + 1] if (dmeas is not None and not fuse_in) else None      # max |dprev| for its consumers
@@ -1194,38 +1189,35 @@ class DecoderFn(torch.autograd.Function):
                 if fuse_in:
                     gxr_f = torch.empty(B, Np, 2, dtype=torch.float32, device=dev)
                     part_f = workspace(dev, (Nt // 128) * F_ * 3)
-                rs = two_val and fuse_rs
-                rs_part = _scratch(dev, 'dec_rs_part', (Nt // 128) * F_ * 2) if rs else None
+                rs_part = _scratch(dev, 'dec_rs_part', (Nt // 128) * F_ * 2) if from_bits else None
                 with _timed('tvae_linear_dgrad_x6', p_d, two_val):
                     call('tvae_linear_dgrad_x6', w3t, dsrc, d if resid else None, hprev, dprev, F_, Nt, F_, ldn, ldn, act,
                          LRELU_SLOPE, xr.view(Nt, 2) if fuse_in else None, Wc.contiguous() if fuse_in else None,
                          gxr_f if fuse_in else None, part_f if fuse_in else None, part_f.numel() if fuse_in else 0,
                          vg[0] if (use_vg and not two_val) else None, vg[1] if use_vg else None, csum,
                          bc if va else None, LB if va else None, Np if va else 0,
-                         rs_part, rs_part.numel() if rs else 0, vg[0] if rs else None, dbo if rs else None,
-                         tot[0] if rs else None, tot[1] if rs else None, p_d,
+                         rs_part, rs_part.numel() if from_bits else 0, vg[0] if from_bits else None,
+                         dbo if from_bits else None, tot[0] if from_bits else None, tot[1] if from_bits else None, p_d,
                          sbits if from_bits else None, rowdot, b if from_bits else None,
                          d_bnd if (p_d == 2 and not two_val) else None, emit)
-                if two_val and li == 0 and n_hidden == 1 and has_f and parts() == 2:
-                    # bound of the gradient this launch leaves in `dprev` (read again by the Fourier first layer's backward):
-                    # |dX[k][n]| <= max |gy| * sum_m |wo[m] W[m][k]|
-                    ctx.d_bound = gy_amax() * (W.detach().abs() * vg[0].detach().abs()[:, None]).sum(0).amax().reshape(1)
-                fused_in = fuse_in
                 if fuse_in:
                     _note('dec.fuse_in')
                 d_bnd = emit
+                if two_val and li == 0 and has_f and rt.h3:
+                    # the gradient this launch leaves in `dprev` is read again by the Fourier first layer's backward, under
+                    # this analytic bound: |dX[k][n]| <= max |gy| * sum_m |wo[m] W[m][k]|
+                    d_bnd = gy_amax() * (W.detach().abs() * vg[0].detach().abs()[:, None]).sum(0).amax().reshape(1)
             else:
                 call('tvae_linear_dgrad', W.contiguous(), d, d if resid else None, hprev, dprev, F_, Nt, F_, ldn, ldn,
                      act, LRELU_SLOPE)
-                d_bnd = None
             d = dprev
             grads_hidden.append((dW, db))
         grads_hidden.reverse()
         # first layer: d is the pre-activation gradient [F][Nt]
         Simg = torch.empty(B, F_, dtype=torch.float32, device=dev)
         dbc = torch.empty(F_, dtype=torch.float32, device=dev)
-        gxr = torch.empty(B, Np, 2, dtype=torch.float32, device=dev) if not fused_in else gxr_f
-        if fused_in:
+        gxr = gxr_f if rt.virt_act else torch.empty(B, Np, 2, dtype=torch.float32, device=dev)
+        if rt.virt_act:
             dWc = torch.empty(F_, 2, dtype=torch.float32, device=dev)
             call('tvae_dec_in_total', part_f, B, Np // 128, F_, Simg, dbc, dWc)
         elif has_f:
@@ -1246,20 +1238,17 @@ class DecoderFn(torch.autograd.Function):
         if has_f:
             Ff = Wf.shape[0]
             # h3 for the Fourier first layer's backward (round 4): both operands come from memory with known bounds -- the
-            # features are cosines (<= 1), d is bounded by the two-valued data gradient that produced it (ctx.d_bound)
-            d_bound = getattr(ctx, 'd_bound', None) if parts() == 2 else None
-            if d_bound is None and parts() == 2:
-                d_bound = d_bnd                          # (round 6) measured by the launch that stored d
-            one = torch.ones(1, dtype=torch.float32, device=dev) if d_bound is not None else None
-            dWc = _wgrad(d, feat, F_, Nt, Ff, a_amax=d_bound, x_amax=one, ld=ldn)
+            # features are cosines (<= 1), d is under its bound word (analytic behind a two-valued data gradient, else measured)
+            one = torch.ones(1, dtype=torch.float32, device=dev) if d_bnd is not None else None
+            dWc = _wgrad(d, feat, F_, Nt, Ff, a_amax=d_bnd, x_amax=one, ld=ldn)
             dfeat = torch.empty(Ff, ldn, dtype=torch.float32, device=dev)
-            if _dense_x6_ok(Ff, Nt):
-                p_f = 2 if d_bound is not None else _p3()
+            if rt.four_dgrad_x6:
+                p_f = 2 if d_bnd is not None else _p3()
                 w3t = _split_weight(Wc, Ff, F_, True, 'x6_dense_wct', nparts=p_f)
                 with _timed('tvae_linear_dgrad_x6', p_f):
                     call('tvae_linear_dgrad_x6', w3t, d, None, None, dfeat, F_, Nt, Ff, ldn, ldn, ACT_NONE, LRELU_SLOPE,
                          None, None, None, None, 0, None, None, None, None, None, 0, None, 0, None, None, None, None, p_f,
-                         None, None, None, d_bound)
+                         None, None, None, d_bnd)
             else:
                 call('tvae_linear_dgrad', Wc.contiguous(), d, None, None, dfeat, F_, Nt, Ff, ldn, ldn, ACT_NONE, LRELU_SLOPE)
             call('tvae_fourier_bwd', xr, Wf.contiguous(), bf.contiguous(), sigma, dfeat, ldn, Ff, Nt, gxr)

@@ -1004,8 +1004,10 @@ def test_deep_decoder_runs_h3_on_measured_bounds(fourier, n_out, resid, gemm_mod
 def test_decoder_padded_row_stride_is_layout_only(fourier, L, n_out, resid, gemm_mode):
     """Round 6: decoders that store activations / gradients (Fourier first layer, two or more hidden layers; galaxy: reference
     train_galaxy.py:412-420, src/models.py:84-123) give their [features][B*Np] tensors a padded row stride when the column count
-    is a multiple of 2^14 (ops._dec_ld: the rows of a weight-gradient panel otherwise share their L2 sets).  Layout only: output
-    and every gradient bit for bit what the dense layout gives (TVAE_DEC_LD_PAD=0), and the padded path must be the one taken."""
+    is a multiple of 2^14 (ops.decoder_route: the rows of a weight-gradient panel otherwise share their L2 sets).  Layout only:
+    output and every gradient bit for bit what the dense layout gives (TVAE_DEC_LD_PAD=0), and the padded path must be the one
+    taken.  The backward reads the stride its forward chose (ctx.route): switching the padding off between the two changes
+    nothing."""
     import src.models as M
     from tvae import ops
     torch.manual_seed(3)
@@ -1015,7 +1017,7 @@ def test_decoder_padded_row_stride_is_layout_only(fourier, L, n_out, resid, gemm
     z = torch.randn(B, zd, device=dev())
     gy = torch.randn(B, Np, n_out, device=dev())
 
-    def run(pad):
+    def run(pad, pad_bwd=None):
         old = ops.DEC_LD_PAD
         ops.DEC_LD_PAD = pad
         ops.PATH_LOG = set()
@@ -1024,6 +1026,8 @@ def test_decoder_padded_row_stride_is_layout_only(fourier, L, n_out, resid, gemm
                 p_.grad = None
             xg, zg = x.clone().requires_grad_(True), z.clone().requires_grad_(True)
             yh = gen(xg, zg)
+            if pad_bwd is not None:
+                ops.DEC_LD_PAD = pad_bwd
             (yh * gy).sum().backward()
             torch.cuda.synchronize()
             return [yh.detach(), xg.grad, zg.grad] + [p_.grad.clone() for p_ in gen.parameters()], set(ops.PATH_LOG)
@@ -1032,10 +1036,13 @@ def test_decoder_padded_row_stride_is_layout_only(fourier, L, n_out, resid, gemm
 
     r1, took1 = run(64)
     r0, took0 = run(0)
+    # padding on in the forward, off before the backward (this direction only: a backward that took its stride from the
+    # switch would read past the end of dense tensors the other way)
+    r10, took10 = run(64, pad_bwd=0)
     split = gemm_mode in ('x6', 'h3', 'bf16')
-    assert ('dec.ld_pad' in took1) == split and 'dec.ld_pad' not in took0, (took1, took0)
-    for a_, b_ in zip(r1, r0):
-        assert torch.equal(a_, b_)
+    assert ('dec.ld_pad' in took1) == split and 'dec.ld_pad' not in took0 and took10 == took1, (took1, took0, took10)
+    for a_, b_, c_ in zip(r1, r0, r10):
+        assert torch.equal(a_, b_) and torch.equal(a_, c_)
     with torch.no_grad():                                # inference path (no stored tensors besides the first layer's)
         ops.DEC_LD_PAD = 64
         try:

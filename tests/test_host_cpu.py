@@ -380,6 +380,45 @@ def test_shape_validation_happens_before_any_launch():
         ops.HeadFn.apply(torch.zeros(7, 10), torch.zeros(2, 36), torch.zeros(2, 2), torch.zeros(2), tb, 2, 2)
 
 
+# (B, Np, hidden units, hidden layers, outputs, LeakyReLU, resid, Fourier features) -> the route fields that hold in the split
+# arithmetics (x6 / h3 / bf16; 'h3' in h3 only) and the row padding there; in f32 none holds.  bench.py's decoders at their
+# bench batch, then one each of resid / tanh / 128 / 1024 hidden units.  The GPU tests' path sets follow from these:
+# virt_act -> dec.virt_act + dec.fuse_in, sign_bits -> dec.sign_bits + dec.virt_grad_2val, no_h -> dec.no_h +
+# dec.row_sums_in_dgrad (test_step_hot_widths_golden, test_decoder_kink_free_probe_at_bench_size).
+_S64 = {'split', 'virt_act', 'fused_out', 'virt_grad', 'sign_bits', 'no_h'}
+DECODER_ROUTES = {
+    'S64': ((256, 4096, 512, 1, 1, True, False, 0), _S64, 0),
+    'S28': ((256, 784, 512, 1, 1, True, False, 0), _S64, 0),                  # 784 pixels padded to 896 (split arithmetics)
+    'S28F': ((256, 784, 512, 1, 1, True, False, 1024), {'split', 'four_x6', 'four_dgrad_x6', 'fused_out', 'virt_grad',
+                                                        'sign_bits', 'no_h'}, 0),
+    'S128G': ((8, 16384, 512, 3, 3, True, False, 1024), {'split', 'four_x6', 'four_dgrad_x6'}, 64),
+    'resid': ((4, 4096, 512, 3, 1, True, True, 0), {'split', 'fused_out'}, 64),
+    'tanh': ((64, 4096, 512, 1, 1, False, False, 0), {'split', 'virt_act', 'fused_out', 'virt_grad'}, 0),
+    'F128': ((8, 16384, 128, 1, 1, True, False, 1024), {'four_dgrad_x6'}, 0),        # too narrow for the split-pipe layers
+    'F1024': ((64, 4096, 1024, 2, 1, True, False, 0), {'split', 'virt_grad', 'sign_bits'}, 64),
+}
+
+
+@pytest.mark.parametrize('mode', ['f32', 'x6', 'h3', 'bf16'])
+@pytest.mark.parametrize('name', sorted(DECODER_ROUTES))
+def test_decoder_route_of_named_configurations(name, mode):
+    """ops.decoder_route -- every structural decision of the decoder, taken once in the forward and kept for the backward --
+    for named configurations in each arithmetic, in training and in inference (host only: no library, no GPU)."""
+    from tvae import ops
+    from tvae._lib import arithmetic
+    (B, Np, F_, nh, n_out, lrelu, resid, Ff), fields, pad = DECODER_ROUTES[name]
+    act = ops.ACT_LRELU if lrelu else ops.ACT_TANH
+    split = mode != 'f32'
+    with arithmetic(mode):
+        Np_p = ops.decoder_padded_pixels(Np, B, F_, nh, n_out, resid, Ff > 0, act)
+        assert Np_p == (896 if (name == 'S28' and split) else 0), Np_p
+        Np = Np_p or Np
+        for infer in (False, True):
+            want = {f: split and f in fields for f in ops.DecoderRoute._fields}
+            want.update(ldn=B * Np + (pad if split else 0), h3=split and mode == 'h3' and 'split' in fields, infer=infer)
+            assert ops.decoder_route(B, Np, F_, nh, n_out, act, resid, Ff, infer)._asdict() == want
+
+
 def test_scratch_buffers_outlive_a_captured_graph():
     """once a hipGraph has been captured (tvae/graph.py -> ops.pin_scratch), growing a scratch buffer
     or the shared workspace must not free the block the graph still points to.  ADVICE r04: the pin belongs to the graph
