@@ -124,6 +124,20 @@ long tvae_conv1_dft_at_floats(int B, int Cin, int n, int ksz, int pad, int C, in
 long tvae_conv1_dft_ws_floats(int B, int Cin, int n, int ksz, int pad, int C, int R);
 int tvae_conv1_dft_frame(int B, int Cin, int n, int ksz, int pad, int C, int R);
 int tvae_conv1_dft_ring(int B, int Cin, int n, int ksz, int pad, int C, int R);
+/* tvae_conv1_dft_route: the kernel instance one step of the pair above launches for this geometry and `parts` (1 .. 3), -1 if
+ * the geometry or `parts` is not handled.  Host arithmetic only (no device call); the launchers dispatch on the same ids.
+ *   which = 0, output transform along w (tvae_conv1_fwd_dft):
+ *     1 .. 6   ring instance of that frame (= tvae_conv1_dft_ring)      10       dft_out_h3_kernel<11, 5, 5> (parts = 2)
+ *     11 / 12  dft_out_wide_kernel<82, 6> / <96, 8>                     21 .. 25 dft_out_gen_kernel<NT = 1 .. 5>
+ *     31 .. 39 dft_out_mf_kernel<LHP, NT, REM1>: 30 + 3 i + v, LHP = 23 / 49 / 64 for i = 0 / 1 / 2,
+ *              v = 1: <LHP, 1, false>, 2: <LHP, 1, true>, 3: <LHP, 2, false>
+ *   which = 1, dY transform along w (tvae_conv1_wgrad_dft):
+ *     1 .. 6   ring instance of that frame                              10       dft_dy_h3_kernel<9, 6, 11> (parts = 2)
+ *     11 / 12 / 13  dft_dy_wide_kernel<50 | 66 | 80, 16, 2>             20       dft_dy_gen_kernel
+ *     31 .. 35 dft_dy_mf_kernel <9, 2, 46, true>, <9, 2, 0, true>, <17, 4, 98, true>, <17, 4, 0, true>, <32, 4, 0, false>
+ *   which = 2, forward spectral GEMM: 1 streamed panel resident in LDS (dense_x6_xres_kernel), 2 256-row tile, 3 512-row tile
+ *   which = 3, weight-gradient GEMM: 1 standard 512 x 128 tile, 2 exact-fit 256 x 192 tile (dense_wgrad_x6_wide_kernel) */
+int tvae_conv1_dft_route(int B, int Cin, int n, int ksz, int pad, int C, int R, int parts, int which);
 int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, float* out, float* at, float* ws,
                        long ws_floats, int B, int Cin, int n, int ksz, int pad, int C, int R, int act, float slope,
                        int parts, tvae_stream_t stream);

@@ -72,6 +72,11 @@ static size_t dft_lds_spectra(int S, int L, int FXB, bool mixed = false) {
     return (size_t)S * FXB * 8 + (mixed ? 0 : (size_t)L * FXB * 8) + (size_t)L * 8;
 }
 constexpr size_t DFT_LDS_TARGET = 50 * 1024;       // three workgroups per CU for the latency-bound direct-sum transforms
+// the h3 instances of the transforms along w (conv_dft_h3_kernels.hpp): dft_out_h3_kernel<KS, NWT, NLD> covers 2 Lh <= 16 KS,
+// Ho <= 32 NWT, 16 Lh <= NLD 64 NWT; dft_dy_h3_kernel<WS, NKT, NLD> covers Ho <= 16 WS, 2 Lh <= 32 NKT, 32 Ho <= NLD 64 NKT.
+// The plan admits a frame for the one instance and the route for the other from these numbers (dft_route).
+constexpr int OH3_KS = 11, OH3_NWT = 5, OH3_NLD = 5;
+constexpr int DH3_WS = 9, DH3_NKT = 6, DH3_NLD = 11;
 static DftPlan dft_plan(int B, int Cin, int n, int ksz, int pad, int C, int R) {
     DftPlan q;
     q.Cin = Cin;
@@ -138,9 +143,10 @@ static DftPlan dft_plan(int B, int Cin, int n, int ksz, int pad, int C, int R) {
     // the h3 instances of the wide transforms: the galaxy frame (L = 160: Lh = 81, Ho = 129) and every other generic frame whose
     // step / tile counts they cover
     q.KS = (2 * q.Lh + 15) / 16; q.NWT = (q.Ho + 31) / 32; q.WS = (q.Ho + 15) / 16; q.NKT = (2 * q.Lh + 31) / 32;
-    q.h3w = (q.gen && q.KS <= 11 && q.NWT <= 5 && q.WS <= 9 && q.NKT <= 6 && q.Ho >= 32) ? 1 : 0;
-    q.eoc_floats = q.h3w ? (long)5 * 11 * 2 * 64 * 4 : 0;
-    q.edc_floats = q.h3w ? (long)6 * 9 * 2 * 64 * 4 : 0;
+    // (h3w: the cell tables of both instances are made; which transform then runs on them is dft_route's decision)
+    q.h3w = (q.gen && q.KS <= OH3_KS && q.NWT <= OH3_NWT && q.WS <= DH3_WS && q.NKT <= DH3_NKT && q.Ho >= 32) ? 1 : 0;
+    q.eoc_floats = q.h3w ? (long)OH3_NWT * OH3_KS * 2 * 64 * 4 : 0;
+    q.edc_floats = q.h3w ? (long)DH3_NKT * DH3_WS * 2 * 64 * 4 : 0;
     // EO + ED + per-row bias-gradient sums (+ the h3 cell tables, 16-byte aligned)
     q.tab_floats = ((q.eo_floats + 3) & ~3L) + ((q.ed_floats + 3) & ~3L) + ((q.M + 3) & ~3L) + q.eoc_floats + q.edc_floats;
     q.g_floats = (long)q.Lh * 2 * q.M * q.K2;
@@ -211,6 +217,77 @@ static DftPlan dft_plan(int B, int Cin, int n, int ksz, int pad, int C, int R) {
     return q;
 }
 
+// ---- which instance each step launches (tvae_conv1_dft_route; the ids are listed in include/tvae_hip.h) -----------------
+// The two launchers dispatch on these ids and nothing else, so the query and the launch cannot disagree.
+enum DftStep { DFT_STEP_OUT = 0, DFT_STEP_DY = 1, DFT_STEP_FWD_GEMM = 2, DFT_STEP_WGRAD_GEMM = 3 };
+enum DftRouteId {
+    // transforms along w, both directions: ring r (1 .. 6) = the LDS-DMA ring instance of that frame
+    DFT_R_H3 = 10,                                     // dft_out_h3_kernel<11, 5, 5> / dft_dy_h3_kernel<9, 6, 11>
+    DFT_R_OUT_WIDE82 = 11, DFT_R_OUT_WIDE96 = 12,      // dft_out_wide_kernel<82, 6> / <96, 8>
+    DFT_R_OUT_GEN = 20,                                // + NT: dft_out_gen_kernel<NT>, NT = 1 .. 5
+    DFT_R_OUT_MF = 30,                                 // + 3 i + v: dft_out_mf_kernel, LHP = 23 / 49 / 64 (i = 0 / 1 / 2),
+                                                       //   v = 1: <LHP, 1, false>, 2: <LHP, 1, true>, 3: <LHP, 2, false>
+    DFT_R_DY_WIDE50 = 11, DFT_R_DY_WIDE66 = 12, DFT_R_DY_WIDE80 = 13,   // dft_dy_wide_kernel<50 | 66 | 80, 16, 2>
+    DFT_R_DY_GEN = 20,                                 // dft_dy_gen_kernel
+    DFT_R_DY_MF = 30,                                  // + 1 .. 5: dft_dy_mf_kernel<9, 2, 46, true>, <9, 2, 0, true>,
+                                                       //   <17, 4, 98, true>, <17, 4, 0, true>, <32, 4, 0, false>
+    // spectral GEMMs
+    DFT_R_FWD_XRES = 1, DFT_R_FWD_X4 = 2, DFT_R_FWD_X6 = 3,    // panel resident in LDS / 256-row tile / 512-row tile
+    DFT_R_WG_STD = 1, DFT_R_WG_WIDE = 2,                       // dense_wgrad_x6 512 x 128 tile / exact-fit 256 x 192 tile
+};
+// bf16 STORAGE of T (round 4): the one-part throughput mode on a ring geometry with whole 256-row tiles writes and reads T as
+// 2-byte elements (TVAE_BF16_STORE=0 keeps fp32 storage; the fp32-class arithmetics never take this path)
+// (ring 3, the 50 x 50 geometry on its 60-wide frame: a bf16 slot of 4 KB cannot hold the 32 x 39 transposition patch)
+static bool dft_t16(const DftPlan& q, int parts) {
+    constexpr bool bf16_store = true;
+    return bf16_store && parts == 1 && q.ring && q.ring != 3 && q.K2 <= 256 && (2 * q.M) % DX4_ROWS == 0;
+}
+// dft_out_wide_kernel: output tiles on the matrix pipe (the single last column of Ho = 32 k + 1 goes to the vector ALU), the
+// instance's padded slot, its LDS
+static int dft_out_wide_ntw(const DftPlan& q) { return (q.Ho % 32 == 1 && q.NT > 1) ? q.NT - 1 : q.NT; }
+static int dft_out_wide_lhr(const DftPlan& q) {
+    return (q.Lh <= 82 && cdiv(16 * q.Lh, 64 * dft_out_wide_ntw(q)) <= 6) ? 82 : DFT_WIDE_LH;
+}
+static size_t dft_out_wide_lds(const DftPlan& q) {
+    return ((size_t)2 * dft_out_wide_lhr(q) * 64 + (size_t)dft_out_wide_ntw(q) * 32 * 33 + 2 * q.Lh) * 4;
+}
+static int dft_route(const DftPlan& q, int parts, int step) {
+    if (!q.ok || parts < 1 || parts > 3) return -1;
+    const bool h3 = parts == 2;
+    if (step == DFT_STEP_OUT) {
+        if (q.ring) return q.ring;
+        if (q.h3w && h3 && 16 * q.Lh <= OH3_NLD * 64 * OH3_NWT) return DFT_R_H3;
+        const int NTW = dft_out_wide_ntw(q);
+        if (q.gen && q.Lh <= DFT_WIDE_LH && NTW <= 8 && q.REM1 == 0 && q.Lh * 16 <= 8 * 64 * NTW &&
+            dft_out_wide_lds(q) <= 150 * 1024)
+            return dft_out_wide_lhr(q) == 82 ? DFT_R_OUT_WIDE82 : DFT_R_OUT_WIDE96;
+        if (q.gen) return DFT_R_OUT_GEN + q.NT;
+        return DFT_R_OUT_MF + 3 * (q.LHP == 23 ? 0 : (q.LHP == 49 ? 1 : 2)) + (q.REM1 ? 2 : (q.NT == 1 ? 1 : 3));
+    }
+    if (step == DFT_STEP_DY) {
+        if (q.ring) return q.ring;
+        // (the instance stages 32 Ho values of a tile in NLD dwords per thread: frames with Ho up to 16 WS = 144 make the tables,
+        //  only those up to NLD 64 NKT / 32 = 132 fit the staging)
+        if (q.h3w && h3 && 32 * q.Ho <= DH3_NLD * 64 * DH3_NKT) return DFT_R_H3;
+        if (q.gen && q.NS <= DFT_WIDE_NS && q.NRT <= 8 && 32 * q.Ho <= 16 * 64 * q.NRT &&
+            (size_t)2 * (32 * (q.Ho | 1) + 1) * 4 <= 150 * 1024)
+            return q.NS <= 50 ? DFT_R_DY_WIDE50 : (q.NS <= 66 ? DFT_R_DY_WIDE66 : DFT_R_DY_WIDE80);
+        if (q.gen) return DFT_R_DY_GEN;
+        if (q.NS == 9) return DFT_R_DY_MF + (q.Lh == 23 ? 1 : 2);
+        if (q.NS == 17) return DFT_R_DY_MF + (q.Lh == 49 ? 3 : 4);
+        return DFT_R_DY_MF + 5;
+    }
+    if (step == DFT_STEP_FWD_GEMM) {
+        // short reductions (K2 <= 256: twelve k-steps at the 64 x 64 shape): 256-row tiles, two 4-wave workgroups per CU
+        if (q.K2 > 256) return DFT_R_FWD_X6;
+        const bool xres = !dft_t16(q, parts) && dense_x6_xres_fits(2 * q.M, q.Mb, (int)q.NBpad, q.K2, parts);
+        return xres ? DFT_R_FWD_XRES : DFT_R_FWD_X4;
+    }
+    if (step == DFT_STEP_WGRAD_GEMM)     // (the one-part mode keeps its bf16-stored S' path)
+        return (parts != 1 && q.wsplits > 0) ? DFT_R_WG_WIDE : DFT_R_WG_STD;
+    return -1;
+}
+
 extern "C" {
 
 // ---- lifting convolution through the frequency domain (conv_dft_kernels.hpp) -------------------------------------
@@ -228,6 +305,10 @@ long tvae_conv1_dft_at_floats(int B, int Cin, int n, int ksz, int pad, int C, in
 // / generic; 1 .. 6: the LDS-DMA ring kernels, dft_plan)
 int tvae_conv1_dft_frame(int B, int Cin, int n, int ksz, int pad, int C, int R) { return dft_plan(B, Cin, n, ksz, pad, C, R).L; }
 int tvae_conv1_dft_ring(int B, int Cin, int n, int ksz, int pad, int C, int R) { return dft_plan(B, Cin, n, ksz, pad, C, R).ring; }
+// the instance one step launches (dft_route), -1: geometry or parts not handled.  Host arithmetic only, no device call.
+int tvae_conv1_dft_route(int B, int Cin, int n, int ksz, int pad, int C, int R, int parts, int which) {
+    return dft_route(dft_plan(B, Cin, n, ksz, pad, C, R), parts, which);
+}
 long tvae_conv1_dft_ws_floats(int B, int Cin, int n, int ksz, int pad, int C, int R) {
     const DftPlan q = dft_plan(B, Cin, n, ksz, pad, C, R);
     // forward: W + W3 + T + tables; backward: S' (= T) + split-K slabs of G + tables
@@ -240,7 +321,9 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
                        long ws_floats, int B, int Cin, int n, int ksz, int pad, int C, int R, int act, float slope,
                        int parts, tvae_stream_t stream) {
     const DftPlan q = dft_plan(B, Cin, n, ksz, pad, C, R);
-    if (!q.ok || ws_floats < tvae_conv1_dft_ws_floats(B, Cin, n, ksz, pad, C, R) || !aligned16(ws) || !aligned16(at))
+    const int r_gemm = dft_route(q, parts, DFT_STEP_FWD_GEMM), r_out = dft_route(q, parts, DFT_STEP_OUT);
+    if (r_gemm < 0 || r_out < 0 || ws_floats < tvae_conv1_dft_ws_floats(B, Cin, n, ksz, pad, C, R) || !aligned16(ws) ||
+        !aligned16(at))
         return (int)hipErrorInvalidValue;
     hipStream_t st = S(stream);
     float* W = ws;
@@ -254,11 +337,7 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
     // h3 arithmetic (two fp16 parts, three products): both forms of the spectral GEMM (four-wave tile for reductions <= 256,
     // eight-wave tile beyond: several channels, wide frames) take the operand maxima dft_spectra leaves behind A^T
     const bool h3 = parts == 2;
-    // bf16 STORAGE of T (round 4): the one-part throughput mode on a ring geometry with whole 256-row tiles writes and reads T
-    // as 2-byte elements (TVAE_BF16_STORE=0 keeps fp32 storage; the fp32-class arithmetics never take this path)
-    constexpr bool bf16_store = true;
-    // (ring 3, the 50 x 50 geometry on its 60-wide frame: a bf16 slot of 4 KB cannot hold the 32 x 39 transposition patch)
-    const bool t16 = bf16_store && parts == 1 && q.ring && q.ring != 3 && q.K2 <= 256 && (2 * q.M) % DX4_ROWS == 0;
+    const bool t16 = dft_t16(q, parts);               // bf16 storage of T
     // the maxima are produced in every arithmetic (one small fill and a few atomics): the weight gradient may run in
     // h3 after a forward that did not
     float* amax = at + ((q.at_floats + 3) & ~3L);
@@ -321,7 +400,7 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
         ep.ctile = (long)2 * q.M * q.Lh * 128;
         const int Rpad = x6_round_up(rows, DX6_ROWS);
         // short reductions (K2 <= 256: twelve k-steps at the 64 x 64 shape): 256-row tiles, two 4-wave workgroups per CU
-        const int TR = q.K2 <= 256 ? DX4_ROWS : DX6_ROWS;
+        const int TR = r_gemm == DFT_R_FWD_X6 ? DX6_ROWS : DX4_ROWS;
         TileMap tm{Rpad / TR, (int)(q.NBpad / 128), 1};
         tm.bt = q.Mb / TR;                             // group = (fx, quarter of the column tiles): 4*Lh groups over 8 XCDs
         tm.nch = 4;
@@ -329,9 +408,11 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
         // h3: one scale per stacked row (fx, m') of the spectral weight, one per (fx, image) of A^T's columns
         const H3Scale hs{mxp.wmax, mxp.cmax, 1, 0, 0, q.Ho, B};
         // the panel of A^T resident in LDS, weight cells streamed by free-running waves (dense_x6_xres_kernel)
-        if (TR == DX4_ROWS && !t16 &&
-            dense_x6_batched_xres(W3, at, q.NBpad, ep, 2 * q.M, q.Mb, q.Lh, (int)q.NBpad, q.K2, bt.x_stride, 128, parts, st, hs, &rc)) {
-            if (rc) return rc;
+        if (r_gemm == DFT_R_FWD_XRES) {
+            // (dft_route admitted the shape: a refusal here would be the two disagreeing, an error rather than another path)
+            if (!dense_x6_batched_xres(W3, at, q.NBpad, ep, 2 * q.M, q.Mb, q.Lh, (int)q.NBpad, q.K2, bt.x_stride, 128, parts, st, hs,
+                                       &rc))
+                return (int)hipErrorInvalidValue;
         } else
         rc = TR == DX4_ROWS ? dense_x6_batched4(W3, at, q.NBpad, ep, 2 * q.M, rows, (int)q.NBpad, q.K2, tm, bt, parts, st, hs, t16)
                             : dense_x6_batched(W3, at, q.NBpad, ep, 2 * q.M, rows, (int)q.NBpad, q.K2, tm, bt, parts, st, hs);
@@ -344,7 +425,7 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
                            q.NRT, q.mixed ? 1.f / (float)q.L : 1.f / ((float)q.L * (float)q.L));
         TVAE_CHECK_LAUNCH();
         const long ntiles = (long)q.M * (q.NBpad / 32);
-        if (q.ring) {
+        if (r_out == q.ring) {                                        // ring ids 1 .. 6
             const long vt = (long)q.M * ((q.NB + 31) / 32);           // tiles with at least one real column
             const int cus = dev_cu_count();
             const int grid = (int)((vt + 3) / 4 < cus ? (vt + 3) / 4 : cus);
@@ -372,38 +453,36 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
             TVAE_CHECK_LAUNCH();
             return 0;
         }
-        constexpr bool wide_gen = true, wide_h3 = true;
-        if (q.h3w && h3 && wide_h3 && !t16) {
+        if (r_out == DFT_R_H3) {
             // round 6: large frames in the h3 arithmetic leave the fp32 matrix pipe (which bounds them: conv_dft_h3_kernels.hpp)
             uint4* EOc = reinterpret_cast<uint4*>(ED + ((q.ed_floats + 3) & ~3L) + ((q.M + 3) & ~3L));
             uint4* EDc = EOc + q.eoc_floats / 4;
             const float norm = q.mixed ? 1.f / (float)q.L : 1.f / ((float)q.L * (float)q.L);
-            hipLaunchKernelGGL(dft_wtab_h3_kernel, dim3(64), dim3(256), 0, st, EOc, EDc, q.L, q.Lh, q.Ho, 11, 5, 9, 6, norm);
+            hipLaunchKernelGGL(dft_wtab_h3_kernel, dim3(64), dim3(256), 0, st, EOc, EDc, q.L, q.Lh, q.Ho, OH3_KS, OH3_NWT, DH3_WS,
+                               DH3_NKT, norm);
             TVAE_CHECK_LAUNCH();
             int ex = 0;
             frexpf(2.f * norm, &ex);                     // 2 norm in [2^(ex-1), 2^ex): h3_scale = 2^(15 - ex)
             const float eo_inv = ldexpf(1.f, ex - 15);
-            constexpr size_t lds_h = ((size_t)16 * 11 * 32 + 2 * 2 * 11 * 32 * 4 + 32 + 5 * 32 * 33) * 4;
-            e = allow_big_lds(dft_out_h3_kernel<11, 5, 5>, lds_h);
+            constexpr size_t lds_h = ((size_t)16 * OH3_KS * 32 + 2 * 2 * OH3_KS * 32 * 4 + 32 + OH3_NWT * 32 * 33) * 4;
+            e = allow_big_lds(dft_out_h3_kernel<OH3_KS, OH3_NWT, OH3_NLD>, lds_h);
             if (e != hipSuccess) return (int)e;
             const int cus = dev_cu_count();
             const int grid = (int)(ntiles < 2L * cus ? ntiles : 2L * cus);
-            hipLaunchKernelGGL((dft_out_h3_kernel<11, 5, 5>), dim3(grid), dim3(320), lds_h, st, (const float*)T,
-                               (const uint4*)EOc, bias, out, q.M, R, B, q.Ho, q.Lh, q.NBpad, act, slope, eo_inv, a1max);
+            hipLaunchKernelGGL((dft_out_h3_kernel<OH3_KS, OH3_NWT, OH3_NLD>), dim3(grid), dim3(64 * OH3_NWT), lds_h, st,
+                               (const float*)T, (const uint4*)EOc, bias, out, q.M, R, B, q.Ho, q.Lh, q.NBpad, act, slope, eo_inv, a1max);
             TVAE_CHECK_LAUNCH();
             return 0;
         }
         // large frames (galaxy shape): a workgroup per tile, its waves split the output rows (dft_out_wide_kernel); the single
         // last column of Ho = 32 k + 1 outputs goes to the vector ALU instead of a whole wave
-        const int NTW = (q.Ho % 32 == 1 && q.NT > 1) ? q.NT - 1 : q.NT;
-        if (q.gen && wide_gen && q.Lh <= DFT_WIDE_LH && NTW <= 8 && q.REM1 == 0 && q.Lh * 16 <= 8 * 64 * NTW) {
-            const int LHR = (q.Lh <= 82 && cdiv(16 * q.Lh, 64 * NTW) <= 6) ? 82 : DFT_WIDE_LH;      // the instance's padded slot
-            const size_t lds_w = ((size_t)2 * LHR * 64 + (size_t)NTW * 32 * 33 + 2 * q.Lh) * 4;
-            if (lds_w <= 150 * 1024) {
-                const int cus = dev_cu_count();
-                const long fit = (long)(150 * 1024 / lds_w);
-                const long wg_per_cu = fit < 2 ? fit : 2;
-                const int grid = (int)(ntiles < wg_per_cu * cus ? ntiles : wg_per_cu * cus);
+        if (r_out == DFT_R_OUT_WIDE82 || r_out == DFT_R_OUT_WIDE96) {
+            const int NTW = dft_out_wide_ntw(q);
+            const size_t lds_w = dft_out_wide_lds(q);                 // (<= 150 KB: dft_route)
+            const int cus = dev_cu_count();
+            const long fit = (long)(150 * 1024 / lds_w);
+            const long wg_per_cu = fit < 2 ? fit : 2;
+            const int grid = (int)(ntiles < wg_per_cu * cus ? ntiles : wg_per_cu * cus);
 #define TVAE_OUT_WIDE(LHR_, NLD_)                                                                                    \
     do {                                                                                                            \
         e = allow_big_lds(dft_out_wide_kernel<LHR_, NLD_>, lds_w);                                                  \
@@ -411,19 +490,18 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
         hipLaunchKernelGGL((dft_out_wide_kernel<LHR_, NLD_>), dim3(grid), dim3(64 * NTW), lds_w, st, (const float*)T, \
                            (const float*)EO, bias, out, q.M, R, B, q.Ho, q.Lh, q.NBpad, q.NT, NTW, act, slope, a1max); \
     } while (0)
-                const int nld = cdiv(16 * q.Lh, 64 * NTW);            // float4 pieces per thread and tile
-                if (q.Lh <= 82 && nld <= 6) TVAE_OUT_WIDE(82, 6); else TVAE_OUT_WIDE(DFT_WIDE_LH, 8);
+            // float4 pieces per thread and tile: cdiv(16 Lh, 64 NTW) <= 6 in the 82-wide slot, <= 8 in the 96-wide one
+            if (r_out == DFT_R_OUT_WIDE82) TVAE_OUT_WIDE(82, 6); else TVAE_OUT_WIDE(DFT_WIDE_LH, 8);
 #undef TVAE_OUT_WIDE
-                TVAE_CHECK_LAUNCH();
-                return 0;
-            }
+            TVAE_CHECK_LAUNCH();
+            return 0;
         }
-        if (q.gen) {
+        if (r_out > DFT_R_OUT_GEN && r_out <= DFT_R_OUT_GEN + 5) {
             const int grid = (int)((ntiles + 3) / 4 < 4096 ? (ntiles + 3) / 4 : 4096);
 #define TVAE_OUT_GEN(N_)                                                                                            \
     hipLaunchKernelGGL(dft_out_gen_kernel<N_>, dim3(grid), dim3(256), 0, st, (const float*)T, (const float*)EO, bias, out, \
                        q.M, R, B, q.Ho, q.Lh, q.NBpad, act, slope, a1max)
-            switch (q.NT) {
+            switch (r_out - DFT_R_OUT_GEN) {
                 case 1: TVAE_OUT_GEN(1); break;
                 case 2: TVAE_OUT_GEN(2); break;
                 case 3: TVAE_OUT_GEN(3); break;
@@ -434,6 +512,8 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
             TVAE_CHECK_LAUNCH();
             return 0;
         }
+        if (r_out <= DFT_R_OUT_MF || r_out > DFT_R_OUT_MF + 9) return (int)hipErrorInvalidValue;
+        const int mf_l = (r_out - DFT_R_OUT_MF - 1) / 3, mf_v = (r_out - DFT_R_OUT_MF - 1) % 3;      // LHP 23 / 49 / 64; instance
         const size_t lds_o = ((size_t)q.LHP * NTT * 64 + (size_t)4 * 32 * (q.Ho | 1)) * 4;
         const int grid = (int)((ntiles + 3) / 4 < 768 ? (ntiles + 3) / 4 : 768);
         const int iters = (int)((ntiles + 4L * grid - 1) / (4L * grid));
@@ -446,9 +526,9 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
     } while (0)
 #define TVAE_OUT_MF_L(L_)                                                                                           \
     do {                                                                                                            \
-        if (q.REM1) TVAE_OUT_MF(L_, 1, true); else if (q.NT == 1) TVAE_OUT_MF(L_, 1, false); else TVAE_OUT_MF(L_, 2, false); \
+        if (mf_v == 1) TVAE_OUT_MF(L_, 1, true); else if (mf_v == 0) TVAE_OUT_MF(L_, 1, false); else TVAE_OUT_MF(L_, 2, false); \
     } while (0)
-        if (q.LHP == 23) TVAE_OUT_MF_L(23); else if (q.LHP == 49) TVAE_OUT_MF_L(49); else TVAE_OUT_MF_L(64);
+        if (mf_l == 0) TVAE_OUT_MF_L(23); else if (mf_l == 1) TVAE_OUT_MF_L(49); else TVAE_OUT_MF_L(64);
 #undef TVAE_OUT_MF_L
 #undef TVAE_OUT_MF
         TVAE_CHECK_LAUNCH();
@@ -459,7 +539,9 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
 int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float* dbias, float* ws, long ws_floats, int B,
                          int Cin, int n, int ksz, int pad, int C, int R, int parts, tvae_stream_t stream) {
     const DftPlan q = dft_plan(B, Cin, n, ksz, pad, C, R);
-    if (!q.ok || ws_floats < tvae_conv1_dft_ws_floats(B, Cin, n, ksz, pad, C, R) || !aligned16(ws) || !aligned16(at))
+    const int r_dy = dft_route(q, parts, DFT_STEP_DY), r_wg = dft_route(q, parts, DFT_STEP_WGRAD_GEMM);
+    if (r_dy < 0 || r_wg < 0 || ws_floats < tvae_conv1_dft_ws_floats(B, Cin, n, ksz, pad, C, R) || !aligned16(ws) ||
+        !aligned16(at))
         return (int)hipErrorInvalidValue;
     hipStream_t st = S(stream);
     // h3 arithmetic: the bounds of A^T were left behind it by the forward; the per-row maxima of S' come from the transform
@@ -481,7 +563,7 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
                            q.NT + q.REM1, q.NS, q.NRT, q.mixed ? 1.f / (float)q.L : 1.f / ((float)q.L * (float)q.L));
         TVAE_CHECK_LAUNCH();
         const long ntiles = (long)q.M * (q.NBpad / 32);
-        if (q.ring) {
+        if (r_dy == q.ring) {                                         // ring ids 1 .. 6
             const int cus = dev_cu_count();
             const int grid = (int)((ntiles + 3) / 4 < 2 * cus ? (ntiles + 3) / 4 : 2 * cus);
             hipError_t er = hipSuccess;
@@ -504,25 +586,24 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
 #undef TVAE_DY_RING
 #undef TVAE_DY_RING_ONE
             TVAE_CHECK_LAUNCH();
-        } else if (q.h3w && parts == 2) {
+        } else if (r_dy == DFT_R_H3) {
             // round 6: the same transform on the 16-bit matrix pipe (conv_dft_h3_kernels.hpp)
             uint4* EOc = reinterpret_cast<uint4*>(ED + ((q.ed_floats + 3) & ~3L) + ((q.M + 3) & ~3L));
             uint4* EDc = EOc + q.eoc_floats / 4;
-            hipLaunchKernelGGL(dft_wtab_h3_kernel, dim3(64), dim3(256), 0, st, EOc, EDc, q.L, q.Lh, q.Ho, 11, 5, 9, 6,
-                               q.mixed ? 1.f / (float)q.L : 1.f / ((float)q.L * (float)q.L));
+            hipLaunchKernelGGL(dft_wtab_h3_kernel, dim3(64), dim3(256), 0, st, EOc, EDc, q.L, q.Lh, q.Ho, OH3_KS, OH3_NWT, DH3_WS,
+                               DH3_NKT, q.mixed ? 1.f / (float)q.L : 1.f / ((float)q.L * (float)q.L));
             TVAE_CHECK_LAUNCH();
-            const size_t lds_h = ((size_t)((32 * (q.Ho | 1) + 3) & ~3) + 2 * 2 * 9 * 32 * 4 + 32) * 4;
-            hipError_t eh = allow_big_lds(dft_dy_h3_kernel<9, 6, 11>, lds_h);
+            const size_t lds_h = ((size_t)((32 * (q.Ho | 1) + 3) & ~3) + 2 * 2 * DH3_WS * 32 * 4 + 32) * 4;
+            hipError_t eh = allow_big_lds(dft_dy_h3_kernel<DH3_WS, DH3_NKT, DH3_NLD>, lds_h);
             if (eh != hipSuccess) return (int)eh;
             const int cus = dev_cu_count();
             const int gridh = (int)(ntiles < 2L * cus ? ntiles : 2L * cus);
-            hipLaunchKernelGGL((dft_dy_h3_kernel<9, 6, 11>), dim3(gridh), dim3(384), lds_h, st, dpre, (const uint4*)EDc, Sp, q.M,
-                               R, B, q.Ho, q.Lh, q.NBpad, ldexpf(1.f, -14), smax);
+            hipLaunchKernelGGL((dft_dy_h3_kernel<DH3_WS, DH3_NKT, DH3_NLD>), dim3(gridh), dim3(64 * DH3_NKT), lds_h, st, dpre,
+                               (const uint4*)EDc, Sp, q.M, R, B, q.Ho, q.Lh, q.NBpad, ldexpf(1.f, -14), smax);
             TVAE_CHECK_LAUNCH();
-        } else if (q.gen && q.NS <= DFT_WIDE_NS &&
-                   q.NRT <= 8 && 32 * q.Ho <= 16 * 64 * q.NRT && (size_t)2 * (32 * (q.Ho | 1) + 1) * 4 <= 150 * 1024) {
+        } else if (r_dy >= DFT_R_DY_WIDE50 && r_dy <= DFT_R_DY_WIDE80) {
             // large frames (galaxy shape): a workgroup per tile, its waves split the rows of S' (dft_dy_wide_kernel)
-            const int NSR = q.NS <= 50 ? 50 : (q.NS <= 66 ? 66 : DFT_WIDE_NS);      // the instance's padded slot
+            const int NSR = r_dy == DFT_R_DY_WIDE50 ? 50 : (r_dy == DFT_R_DY_WIDE66 ? 66 : DFT_WIDE_NS);   // the instance's slot
             const size_t lds_w = (size_t)2 * (32 * (q.Ho | 1) + 2 * NSR + 2) * 4;
             const int cus = dev_cu_count();
             const long fit = (long)(150 * 1024 / lds_w);
@@ -538,10 +619,12 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
     } while (0)
             // (an instance at three waves per SIMD -- two of the galaxy shape's six-wave workgroups per CU, 168 registers with 17
             //  spilled -- measured 2.17 ms against 2.05 for this one)
-            if (q.NS <= 50) TVAE_DY_WIDE(50, 16, 2); else if (q.NS <= 66) TVAE_DY_WIDE(66, 16, 2); else TVAE_DY_WIDE(DFT_WIDE_NS, 16, 2);
+            if (NSR == 50) TVAE_DY_WIDE(50, 16, 2);
+            else if (NSR == 66) TVAE_DY_WIDE(66, 16, 2);
+            else TVAE_DY_WIDE(DFT_WIDE_NS, 16, 2);
 #undef TVAE_DY_WIDE
             TVAE_CHECK_LAUNCH();
-        } else if (q.gen) {
+        } else if (r_dy == DFT_R_DY_GEN) {
             const size_t lds_g = (size_t)4 * 32 * ((2 * q.NS) | 1) * 4;
             hipError_t eg = allow_big_lds(dft_dy_gen_kernel, lds_g);
             if (eg != hipSuccess) return (int)eg;
@@ -550,6 +633,7 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
                                q.Ho, q.Lh, q.NBpad, q.NS, q.NRT, smax);
             TVAE_CHECK_LAUNCH();
         } else {
+        if (r_dy <= DFT_R_DY_MF || r_dy > DFT_R_DY_MF + 5) return (int)hipErrorInvalidValue;
         const size_t lds_d = ((size_t)q.NS * q.NRT * 64 + (size_t)4 * (32 * ((2 * q.NS) | 1) + 64)) * 4;
         const int grid = (int)((ntiles + 3) / 4 < 768 ? (ntiles + 3) / 4 : 768);
         const int iters = (int)((ntiles + 4L * grid - 1) / (4L * grid));
@@ -562,9 +646,13 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
                            (const float*)ED, Sp, q.M, R, B, q.Ho, q.Lh, q.NBpad, iters,                             \
                            smax);                                                        \
     } while (0)
-        if (q.NS == 9) { if (q.Lh == 23) TVAE_DY_MF(9, 2, 46, true); else TVAE_DY_MF(9, 2, 0, true); }
-        else if (q.NS == 17) { if (q.Lh == 49) TVAE_DY_MF(17, 4, 98, true); else TVAE_DY_MF(17, 4, 0, true); }
-        else TVAE_DY_MF(32, 4, 0, false);
+        switch (r_dy - DFT_R_DY_MF) {
+            case 1: TVAE_DY_MF(9, 2, 46, true); break;
+            case 2: TVAE_DY_MF(9, 2, 0, true); break;
+            case 3: TVAE_DY_MF(17, 4, 98, true); break;
+            case 4: TVAE_DY_MF(17, 4, 0, true); break;
+            default: TVAE_DY_MF(32, 4, 0, false); break;
+        }
 #undef TVAE_DY_MF
         TVAE_CHECK_LAUNCH();
         }
@@ -579,8 +667,7 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
     }
     // G[fx][m'][k] = sum_n S'[fx][m'][n] A^T[fx][k][n]: batched split-pipe weight-gradient GEMM into reduction-slice slabs
     // exact-fit tile where the 2 L Cin columns are one and a half of the 128-wide tiles (dense_wgrad_x6_wide_kernel)
-    constexpr bool wide_on = true;
-    const bool wide = wide_on && parts != 1 && q.wsplits > 0;       // (the one-part mode keeps its bf16-stored S' path)
+    const bool wide = r_wg == DFT_R_WG_WIDE;                         // (the one-part mode keeps its bf16-stored S' path)
     const int nslabs = wide ? q.wsplits : q.splits;
     {
         const int M2 = 2 * q.M;

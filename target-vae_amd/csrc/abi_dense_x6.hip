@@ -64,9 +64,8 @@ bool dense_x6_batched_xres(const void* w3, const float* X, long ldx, const Epilo
     // Two parts (h3): 1.21 against 1.38 ms; three (x6): 1.76 against 1.80.
     // Round 5 (short frame: reduction 2 L = 160 at the 64 x 64 shape): ten steps take it as well.
     // ... and eight (mixed form: reduction 2 ksz = 128).
-    const bool shape_ok = (parts == 2 || parts == 3) && (nk == 12 || nk == 10 || nk == 8);
-    if (!on || !lean || !shape_ok || N % 128 != 0 || Mb < rows_per_problem ||
-        lds > X6_LDS_MAX || !aligned16(w3) || (parts == 2 && (!hs.amax_a || !hs.amax_x)))
+    if (!on || !lean || !dense_x6_xres_fits(rows_per_problem, Mb, N, K, parts) || !aligned16(w3) ||
+        (parts == 2 && (!hs.amax_a || !hs.amax_x)))
         return false;
     const int Rpad = x6_round_up(nprob * Mb, DX6_ROWS), tilesN = N / 128, nch = 4, cs = cdiv(tilesN, nch);
     const unsigned grid = 8u * cdiv(nprob * nch, 8) * cs;

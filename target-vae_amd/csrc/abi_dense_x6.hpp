@@ -13,6 +13,16 @@ static inline long dense_x6_bytes(int rows, int K) {
     return 3 * K8pad * Rpad * 16;
 }
 
+// shapes of the spectral contraction with the streamed panel resident in LDS (dense_x6_batched_xres): 8, 10 or 12 k-steps, two
+// or three parts, whole 128-column panels, whole 512-row problems, its LDS within a CU.  Host arithmetic only: the route query of
+// the frequency-domain convolution (tvae_conv1_dft_route) asks it on machines without a device.
+static inline bool dense_x6_xres_fits(int rows_per_problem, int Mb, int N, int K, int parts) {
+    const int nk = dense_k8pad(K) / 2;
+    const size_t lds = (size_t)nk * parts * 256 * 16 + (size_t)(Mb + 128) * 4;
+    return (parts == 2 || parts == 3) && (nk == 12 || nk == 10 || nk == 8) && N % 128 == 0 && rows_per_problem % DX6_ROWS == 0 &&
+           Mb >= rows_per_problem && lds <= X6_LDS_MAX;
+}
+
 // h3 cells (tvae_dense_split2h): one maximum per padded row (and, behind them, scratch words of the GEMM entry points) behind
 // the two part arrays
 static inline float* h3_trailer(const void* a3, int rows, int K) {

@@ -1116,3 +1116,45 @@ def test_encoder_with_many_head_rows_takes_the_wide_tail(zd, geom, gemm_mode):
         ops.PATH_LOG = None
     assert {'enc.tail_fwd_wide', 'enc.inference'} <= took_i, took_i
     assert torch.equal(oi[5], o1[3]) and torch.equal(oi[6], o1[4])
+
+
+_ENC_H3_FRAME_REF = {}
+
+
+def test_encoder_at_a_frame_beyond_the_h3_dy_staging_vs_oracle(gemm_mode):
+    """Encoder forward (the stacked heads) and backward at n 128, k 64, pad 34 -- the galaxy frame with two more pixels of
+    padding: Ho = 133, one output row more than the h3 dY transform stages (32 Ho <= 11 * 64 * 6) -- against the fp64 oracle,
+    in every arithmetic.  The lifting convolution must take the frequency-domain path."""
+    import src.models as M
+    from tvae import ops
+    n, k, pad, C, R, zd, B = 128, 64, 34, 4, 4, 2, 2
+    Ho = n + 2 * pad - k + 1
+    torch.manual_seed(6)
+    enc = M.InferenceNetwork_AttentionTranslation_AttentionRotation(n, 1, zd, kernels_num=C, kernels_size=k, padding=pad,
+                                                                    groupconv=R, rot_refinement=True, theta_prior=np.pi,
+                                                                    normal_prior_over_r=False)
+    y = torch.rand(B, 1, n, n, generator=torch.Generator().manual_seed(7))
+    w = torch.randn(B, 3 + 2 * zd, R, Ho, Ho, generator=torch.Generator().manual_seed(8), dtype=torch.float64)
+    if not _ENC_H3_FRAME_REF:                            # the oracle once for the three arithmetics
+        p64 = {k_: v.detach().double().requires_grad_(True) for k_, v in enc.state_dict().items()}
+        heads, _, _ = O.encoder_heads(p64, y.double(), R, pad)
+        (heads * w).sum().backward()
+        _ENC_H3_FRAME_REF.update(heads=heads.detach(), grads={k_: v.grad for k_, v in p64.items()})
+    ref = _ENC_H3_FRAME_REF
+    enc = enc.to(dev())
+    ops.PATH_LOG = set()
+    try:
+        heads = enc.encode_heads(y.to(dev()))              # [3 + 2 z][B R Ho Ho]
+        (heads * w.permute(1, 0, 2, 3, 4).reshape(3 + 2 * zd, -1).float().to(dev())).sum().backward()
+        torch.cuda.synchronize()
+        took = set(ops.PATH_LOG)
+    finally:
+        ops.PATH_LOG = None
+    if gemm_mode == 'h3':
+        assert 'conv1.dft' in took, took
+    assert rel_err(heads, ref['heads'].permute(1, 0, 2, 3, 4).reshape(3 + 2 * zd, -1)) < OUT_TOL
+    params = dict(enc.named_parameters())
+    compared = [k_ for k_, g_ in ref['grads'].items() if g_ is not None]
+    assert {'conv1.weight', 'conv1.bias', 'conv2.weight', 'conv_z.weight'} <= set(compared)
+    for k_ in compared:
+        assert_grad_close(params[k_].grad, ref['grads'][k_], tol=GRAD_TOL, name=k_)

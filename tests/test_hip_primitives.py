@@ -301,6 +301,184 @@ def test_conv1_dft_matches_fp64(B, n, k, pad, C, R, act, Cin, nparts):
     assert rel_err(dbank.view(C * R, Cin, k, k), ref_g) < GEMM_TOL['f32']
 
 
+# ---- frequency-domain lifting convolution at the edges of its kernel instances (tvae_conv1_dft_route) --------------------
+# tests/test_host_cpu.py::test_conv1_dft_routes_fit_their_instances_and_are_covered_on_the_gpu sweeps every frame on the host and
+# fails when a (step, instance, parts) it meets is reached by no geometry of this list.
+DFT_ROUTE_GEOMETRIES = [      # (B, Cin, n, k, pad, C, R, act)
+    # every transform instance (ring 1 .. 6, h3, wide, generic, fixed-size) at the smallest and the largest Ho and Lh it admits
+    (2, 1, 30, 20, 3, 2, 4, 1), (2, 1, 74, 48, 3, 2, 4, 1), (2, 1, 54, 22, 3, 2, 4, 1), (2, 1, 38, 28, 3, 2, 4, 1),
+    (2, 1, 90, 64, 3, 2, 4, 1), (2, 1, 64, 28, 1, 2, 4, 1), (2, 1, 122, 97, 3, 2, 4, 1), (2, 1, 8, 1, 68, 2, 4, 1),
+    (2, 1, 9, 1, 28, 2, 4, 1), (2, 1, 171, 32, 2, 2, 4, 1), (2, 1, 8, 1, 76, 2, 4, 1), (2, 1, 159, 4, 2, 2, 4, 1),
+    (2, 1, 9, 1, 68, 2, 4, 1), (2, 1, 90, 32, 3, 2, 4, 1), (2, 1, 158, 5, 3, 2, 4, 1), (2, 1, 187, 32, 2, 2, 4, 1),
+    (2, 1, 170, 111, 3, 2, 4, 1), (2, 1, 8, 128, 60, 2, 4, 1), (2, 1, 207, 180, 2, 2, 4, 1), (2, 1, 170, 145, 3, 2, 4, 1),
+    (2, 1, 122, 98, 3, 2, 4, 1), (2, 1, 122, 96, 3, 2, 4, 1), (2, 1, 122, 65, 3, 2, 4, 1), (2, 1, 229, 166, 0, 2, 4, 1),
+    (2, 1, 170, 144, 3, 2, 4, 1), (2, 1, 170, 113, 3, 2, 4, 1), (2, 1, 122, 64, 3, 2, 4, 1), (2, 1, 186, 97, 3, 2, 4, 1),
+    (2, 1, 242, 153, 3, 2, 4, 1), (2, 1, 170, 112, 3, 2, 4, 1), (2, 1, 186, 96, 3, 2, 4, 1), (2, 1, 186, 65, 3, 2, 4, 1),
+    (2, 1, 256, 139, 5, 2, 4, 1), (2, 1, 186, 64, 3, 2, 4, 1), (2, 1, 186, 33, 3, 2, 4, 1), (2, 1, 256, 131, 17, 2, 4, 1),
+    (2, 1, 8, 44, 18, 2, 4, 1), (2, 1, 38, 13, 3, 2, 4, 1), (2, 1, 45, 14, 0, 2, 4, 1), (2, 1, 38, 12, 3, 2, 4, 1),
+    (2, 1, 45, 13, 0, 2, 4, 1), (2, 1, 38, 11, 3, 2, 4, 1), (2, 1, 18, 1, 23, 2, 4, 1), (2, 1, 38, 1, 3, 2, 4, 1),
+    (2, 1, 45, 1, 0, 2, 4, 1), (2, 1, 8, 96, 44, 2, 4, 1), (2, 1, 90, 65, 3, 2, 4, 1), (2, 1, 97, 66, 0, 2, 4, 1),
+    (2, 1, 97, 65, 0, 2, 4, 1), (2, 1, 90, 63, 3, 2, 4, 1), (2, 1, 90, 33, 3, 2, 4, 1), (2, 1, 97, 34, 0, 2, 4, 1),
+    (2, 1, 8, 8, 0, 2, 4, 1), (2, 1, 8, 1, 12, 2, 4, 1), (2, 1, 8, 1, 0, 2, 4, 1), (2, 1, 123, 96, 2, 2, 4, 1),
+    (2, 1, 9, 1, 12, 2, 4, 1), (2, 1, 123, 95, 2, 2, 4, 1), (2, 1, 8, 1, 13, 2, 4, 1), (2, 1, 8, 1, 28, 2, 4, 1),
+    (2, 1, 123, 64, 2, 2, 4, 1), (2, 1, 8, 1, 62, 2, 4, 1), (2, 1, 171, 44, 2, 2, 4, 1), (2, 1, 86, 1, 7, 2, 4, 1),
+    (2, 1, 57, 1, 4, 2, 4, 1), (2, 1, 247, 152, 2, 2, 4, 1), (2, 1, 170, 77, 3, 2, 4, 1), (2, 1, 85, 1, 8, 2, 4, 1),
+    (2, 1, 118, 1, 7, 2, 4, 1), (2, 1, 251, 124, 2, 2, 4, 1), (2, 1, 170, 76, 3, 2, 4, 1), (2, 1, 170, 45, 3, 2, 4, 1),
+    (2, 1, 117, 1, 8, 2, 4, 1), (2, 1, 90, 1, 35, 2, 4, 1), (2, 1, 251, 96, 2, 2, 4, 1), (2, 1, 250, 148, 3, 2, 4, 1),
+    (2, 1, 9, 1, 62, 2, 4, 1), (2, 1, 38, 27, 3, 2, 4, 1), (2, 1, 45, 28, 0, 2, 4, 1), (2, 1, 8, 1, 5, 2, 4, 1),
+    (2, 1, 59, 46, 2, 2, 4, 1), (2, 1, 97, 64, 0, 2, 4, 1), (2, 1, 8, 64, 28, 2, 4, 1), (2, 1, 9, 1, 5, 2, 4, 1),
+    (2, 1, 123, 94, 2, 2, 4, 1), (2, 1, 9, 1, 13, 2, 4, 1),
+    # Ho = 32 j, 32 j + 1, 32 j + 31 (whole, one-column and one-short output tiles), tanh at the last
+    (2, 1, 8, 1, 44, 2, 4, 1), (2, 1, 8, 1, 60, 2, 4, 1), (2, 1, 9, 1, 44, 2, 4, 1), (2, 1, 9, 1, 60, 2, 4, 1),
+    (2, 1, 9, 1, 11, 2, 4, 2), (2, 1, 9, 1, 27, 2, 4, 2), (2, 1, 9, 1, 43, 2, 4, 2), (2, 1, 9, 1, 59, 2, 4, 2),
+    (2, 1, 9, 1, 75, 2, 4, 2),
+    # the h3 frames around the dY instance's staging bound (32 Ho <= 11 * 64 * 6: Ho <= 132) and the end of its tables (Ho 144),
+    # among them the galaxy frame with two more pixels of padding (n 128, k 64, pad 34: Ho 133) and n 128, k 20, pad 16 (Ho 141)
+    (2, 1, 9, 1, 66, 2, 4, 1), (2, 1, 128, 64, 34, 2, 4, 1), (2, 1, 128, 20, 16, 2, 4, 1),
+    # Lh = 64 / 65, 82 / 83, 88 / 89, 96 / 97: the register slots of the wide and the h3 instances, no activation
+    (2, 1, 124, 1, 1, 2, 4, 0), (2, 1, 122, 1, 3, 2, 4, 0), (2, 1, 160, 3, 1, 2, 4, 0), (2, 1, 158, 5, 3, 2, 4, 0),
+    (2, 1, 172, 15, 1, 2, 4, 0), (2, 1, 170, 17, 3, 2, 4, 0), (2, 1, 188, 31, 1, 2, 4, 0), (2, 1, 186, 161, 3, 2, 4, 0),
+    # B Ho = 126 and 129: just below and just above the 128-column panel (NBpad)
+    (3, 1, 8, 1, 17, 2, 4, 1), (3, 1, 9, 1, 17, 2, 4, 1),
+    # three input channels on the wide frames
+    (2, 3, 9, 1, 28, 2, 4, 1), (2, 3, 158, 5, 3, 2, 4, 1), (2, 3, 57, 1, 4, 2, 4, 1), (2, 3, 85, 1, 8, 2, 4, 1),
+    (2, 3, 117, 1, 8, 2, 4, 1),
+    # the spectral GEMM forms: panel resident in LDS (2 M = 512 at 8 / 10 / 12 k-steps), 512-row tile (2 k Cin > 256),
+    # the exact-fit weight-gradient tile (2 M = 256, 2 k Cin > 128)
+    (2, 1, 60, 60, 6, 32, 8, 1), (2, 1, 64, 76, 16, 32, 8, 1), (2, 3, 28, 30, 8, 32, 8, 1), (2, 3, 50, 44, 6, 2, 4, 1),
+    (2, 3, 28, 28, 8, 16, 8, 1),
+]
+DFT_EDGE_GEOMETRIES = [       # one geometry per transform instance that h3 (parts = 2) reaches; no activation
+    (2, 1, 30, 20, 3, 2, 4, 0), (2, 1, 74, 48, 3, 2, 4, 0), (2, 1, 54, 22, 3, 2, 4, 0), (2, 1, 38, 28, 3, 2, 4, 0),
+    (2, 1, 90, 64, 3, 2, 4, 0), (2, 1, 64, 28, 1, 2, 4, 0), (2, 1, 122, 97, 3, 2, 4, 0), (2, 1, 8, 1, 76, 2, 4, 0),
+    (2, 1, 158, 5, 3, 2, 4, 0), (2, 1, 8, 128, 60, 2, 4, 0), (2, 1, 229, 166, 0, 2, 4, 0), (2, 1, 186, 97, 3, 2, 4, 0),
+    (2, 1, 186, 96, 3, 2, 4, 0), (2, 1, 186, 64, 3, 2, 4, 0), (2, 1, 8, 44, 18, 2, 4, 0), (2, 1, 38, 12, 3, 2, 4, 0),
+    (2, 1, 38, 11, 3, 2, 4, 0), (2, 1, 8, 96, 44, 2, 4, 0), (2, 1, 97, 65, 0, 2, 4, 0), (2, 1, 90, 63, 3, 2, 4, 0),
+    (2, 1, 8, 8, 0, 2, 4, 0), (2, 1, 9, 1, 12, 2, 4, 0), (2, 1, 8, 1, 13, 2, 4, 0), (2, 1, 170, 111, 3, 2, 4, 0),
+    (2, 1, 186, 65, 3, 2, 4, 0), (2, 1, 171, 32, 2, 2, 4, 0), (2, 1, 8, 1, 68, 2, 4, 0), (2, 1, 38, 13, 3, 2, 4, 0),
+    (2, 1, 18, 1, 23, 2, 4, 0),
+]
+
+
+def dft_fp64(y, bank, bias, g, k, pad, act):
+    """fp64 references of the lifting convolution (out, act applied), its weight gradient and its bias gradient for the output
+    gradient g [B][C][R][Ho][Ho]: plain F.conv2d / conv2d_weight in float64 (on the GPU: the largest frames here have 180-tap
+    filters whose unfolded operand does not fit a host test)."""
+    B, Cin = y.shape[:2]
+    CR, C = bank.shape[0], bias.shape[0]
+    yd, wd = y.double().to(dev()), bank.double().to(dev()).view(CR, Cin, k, k)
+    pre = F.conv2d(yd, wd, None, 1, pad)
+    Ho = pre.shape[-1]
+    out = act_ref(pre.view(B, C, CR // C, Ho, Ho) + bias.double().to(dev()).view(1, C, 1, 1, 1), act)
+    gd = g.double().to(dev())
+    dbank = torch.nn.grad.conv2d_weight(yd, (CR, Cin, k, k), gd.view(B, CR, Ho, Ho), padding=pad)
+    return out.cpu(), dbank.cpu(), gd.sum(dim=(0, 2, 3, 4)).cpu()
+
+
+def dft_run(y, bank, bias, dpre, B, Cin, n, k, pad, C, R, act, parts):
+    """Forward and weight gradient through the C ABI; returns out [B][C][R][Ho][Ho], dbank, dbias and A^T with its trailer.
+    Outputs start as NaN: an element no kernel writes fails the comparison."""
+    Ho = n + 2 * pad - k + 1
+    at = torch.zeros(query('tvae_conv1_dft_at_floats', B, Cin, n, k, pad, C, R), device=dev())
+    ws = torch.empty(query('tvae_conv1_dft_ws_floats', B, Cin, n, k, pad, C, R), device=dev())
+    out = torch.full((C, B * R * Ho * Ho), float('nan'), device=dev())
+    call('tvae_conv1_fwd_dft', y.to(dev()), bank.to(dev()), bias.to(dev()), out, at, ws, ws.numel(), B, Cin, n, k, pad, C, R,
+         act, SLOPE, parts)
+    dbank = torch.full((C * R, Cin * k * k), float('nan'), device=dev())
+    dbias = torch.full((C,), float('nan'), device=dev())
+    call('tvae_conv1_wgrad_dft', dpre.to(dev()), at, dbank, dbias, ws, ws.numel(), B, Cin, n, k, pad, C, R, parts)
+    torch.cuda.synchronize()
+    return out.view(C, B, R, Ho, Ho).permute(1, 0, 2, 3, 4).cpu(), dbank.cpu(), dbias.cpu(), at.cpu()
+
+
+@pytest.mark.parametrize('B,Cin,n,k,pad,C,R,act', DFT_ROUTE_GEOMETRIES)
+def test_conv1_dft_route_edges(B, Cin, n, k, pad, C, R, act):
+    """Every instance of the transforms along w and of the spectral GEMMs at the edges of the frames it is routed, against fp64:
+    the exact three-part split and h3 to 2e-5 (as test_conv1_dft_matches_fp64), the one-part bf16 mode to 1.5e-2 (as
+    test_conv1_dft_bf16_mode).  Each fp64 reference is computed once for the three arithmetics."""
+    assert query('tvae_conv1_dft_supported', B, Cin, n, k, pad, C, R)
+    Ho = n + 2 * pad - k + 1
+    y = torch.rand(B, Cin, n, n, generator=torch.Generator().manual_seed(1))
+    bank = rnd(C * R, Cin * k * k, seed=2, scale=(Cin * k * k) ** -0.5)
+    bias = rnd(C, seed=3, scale=0.1)
+    g = rnd(B, C, R, Ho, Ho, seed=4)
+    ref, ref_g, ref_db = dft_fp64(y, bank, bias, g, k, pad, act)
+    dpre = g.permute(1, 0, 2, 3, 4).contiguous().view(C, -1)
+    for parts in (3, 2, 1):
+        tol = GEMM_TOL['f32'] if parts > 1 else 1.5e-2
+        routes = [query('tvae_conv1_dft_route', B, Cin, n, k, pad, C, R, parts, w) for w in range(4)]
+        got, dbank, dbias, _ = dft_run(y, bank, bias, dpre, B, Cin, n, k, pad, C, R, act, parts)
+        assert rel_err(got, ref) < tol, (parts, routes, rel_err(got, ref))
+        assert rel_err(dbank.view(C * R, Cin, k, k), ref_g) < tol, (parts, routes, rel_err(dbank.view(C * R, Cin, k, k), ref_g))
+        assert rel_err(dbias, ref_db) < (TOL if parts > 1 else tol), (parts, routes, rel_err(dbias, ref_db))
+
+
+def test_conv1_dft_first_unsupported_geometry_launches_nothing():
+    """Ho = 161 (six 32-row output tiles, one more than any instance takes): both entry points refuse it, in every arithmetic,
+    and leave the output, A^T and the workspace as they were."""
+    from tvae._lib import TvaeHipError
+    B, Cin, n, k, pad, C, R = 2, 1, 9, 1, 76, 2, 4
+    Ho = n + 2 * pad - k + 1
+    assert Ho == 161 and query('tvae_conv1_dft_supported', B, Cin, n, k, pad - 1, C, R)
+    assert not query('tvae_conv1_dft_supported', B, Cin, n, k, pad, C, R)
+    y, bank, bias = torch.rand(B, Cin, n, n, device=dev()), torch.rand(C * R, k * k, device=dev()), torch.zeros(C, device=dev())
+    at = torch.full((max(query('tvae_conv1_dft_at_floats', B, Cin, n, k, pad, C, R), 4096),), 7.0, device=dev())
+    ws = torch.full((max(query('tvae_conv1_dft_ws_floats', B, Cin, n, k, pad, C, R), 4096),), 7.0, device=dev())
+    out = torch.full((C, B * R * Ho * Ho), 7.0, device=dev())
+    dbank, dbias = torch.full((C * R, k * k), 7.0, device=dev()), torch.full((C,), 7.0, device=dev())
+    for parts in (1, 2, 3):
+        assert all(query('tvae_conv1_dft_route', B, Cin, n, k, pad, C, R, parts, w) == -1 for w in range(4))
+        with pytest.raises(TvaeHipError):
+            call('tvae_conv1_fwd_dft', y, bank, bias, out, at, ws, ws.numel(), B, Cin, n, k, pad, C, R, 1, SLOPE, parts)
+        with pytest.raises(TvaeHipError):
+            call('tvae_conv1_wgrad_dft', out, at, dbank, dbias, ws, ws.numel(), B, Cin, n, k, pad, C, R, parts)
+    torch.cuda.synchronize()
+    for t in (at, ws, out, dbank, dbias):
+        assert bool((t == 7.0).all())
+
+
+@pytest.mark.parametrize('B,Cin,n,k,pad,C,R,act', DFT_EDGE_GEOMETRIES)
+def test_conv1_dft_h3_edge_placed_maxima(B, Cin, n, k, pad, C, R, act):
+    """h3 (parts = 2) on one geometry per transform instance, with the largest input values where tiles end: a 2^8 spike at
+    the last pixel of the last image and channel, and in the output gradient at the last w of the last row of the last image
+    and at the first column of the second 32-column tile.  Per-row accuracy against fp64 (rows of out: (image, filter);
+    of dbank: filter rows); the per-channel maxima behind A^T equal max |out| exactly; every operand maximum the kernels
+    leave behind A^T (cmax [Lh][B], fmax [Lh], wmax [Lh][2 M of Mb], smax [M]) is finite and positive.
+    No activation: the transforms along w spread an error of ~1e-7 of the spike's pre-activation value over its output row,
+    in every arithmetic (parts = 3 as well); a LeakyReLU that shrinks a negative spike 100-fold leaves that error in place
+    against a row norm 100 times smaller (1.2e-5 per row at Ho = 160) -- a property of the frequency-domain form, not of the
+    maxima this test is about."""
+    Ho = n + 2 * pad - k + 1
+    y = torch.rand(B, Cin, n, n, generator=torch.Generator().manual_seed(1))
+    y[-1, -1, -1, -1] = 2.0 ** 8
+    bank = rnd(C * R, Cin * k * k, seed=2, scale=(Cin * k * k) ** -0.5)
+    bias = rnd(C, seed=3, scale=0.1)
+    g = rnd(B, C, R, Ho, Ho, seed=4)
+    g[-1, -1, -1, -1, -1] = 2.0 ** 8
+    if B * Ho > 32:                                       # column (image, row) 32: the seam of the first two tiles
+        g[32 // Ho, 0, 0, 32 % Ho, Ho - 1] = -2.0 ** 8
+    ref, ref_g, ref_db = dft_fp64(y, bank, bias, g, k, pad, act)
+    dpre = g.permute(1, 0, 2, 3, 4).contiguous().view(C, -1)
+    got, dbank, dbias, at = dft_run(y, bank, bias, dpre, B, Cin, n, k, pad, C, R, act, 2)
+    routes = [query('tvae_conv1_dft_route', B, Cin, n, k, pad, C, R, 2, w) for w in range(2)]
+    assert row_rel_err(got.reshape(B * C * R, -1), ref.reshape(B * C * R, -1)) < ROW_TOL, routes
+    assert row_rel_err(dbank, ref_g.reshape(C * R, -1)) < ROW_TOL, routes
+    assert rel_err(dbias, ref_db) < TOL, routes
+    # trailer of A^T (csrc/abi_conv_dft.hip: DftPlan): cmax, fmax, wmax, smax, then the per-channel maxima as its last C words
+    Lh = query('tvae_conv1_dft_frame', B, Cin, n, k, pad, C, R) // 2 + 1
+    M, K2, NBpad, Mb = C * R, 2 * k * Cin, -(-B * Ho // 128) * 128, -(-2 * C * R // 512) * 512
+    base = (Lh * K2 * NBpad + 3) // 4 * 4
+    o_fmax, o_wmax = Lh * B, Lh * B + Lh
+    o_smax = o_wmax + Lh * Mb
+    assert at.numel() == base + (o_smax + M + 3) // 4 * 4 + C
+    assert torch.equal(at[-C:], got.abs().amax(dim=(0, 2, 3, 4))), routes
+    tr = at[base:]
+    for name, words in (('cmax', tr[:o_fmax]), ('fmax', tr[o_fmax:o_wmax]),
+                        ('wmax', tr[o_wmax:o_smax].view(Lh, Mb)[:, :2 * M]), ('smax', tr[o_smax:o_smax + M])):
+        assert bool(torch.isfinite(words).all()) and bool((words > 0).all()), (name, routes, words.min())
+
+
+
 @pytest.mark.parametrize('B,n,k,pad,C,R,act', [
     (24, 64, 64, 16, 16, 8, 1), (40, 28, 28, 8, 32, 8, 1), (12, 50, 28, 8, 32, 8, 2),      # ring frames: bf16 STORAGE of T and S'
     (5, 40, 32, 6, 64, 4, 0), (3, 28, 28, 8, 16, 8, 1)])                                  # register-staged frame; ragged ring batch

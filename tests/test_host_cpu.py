@@ -522,3 +522,138 @@ def test_hand_counted_kernels_use_no_scratch_and_no_packed_fp32():
                 assert int(p.group(1)) == 0, (n.group(1), int(p.group(1)))
     assert seen >= 23, seen
     assert npk == 0, npk
+
+
+# ---- frequency-domain lifting convolution: which kernel instance every step takes (tvae_conv1_dft_route) -----------------
+# Capacities of the instances, written from their header comments (csrc/conv_dft_kernels.hpp, conv_dft_h3_kernels.hpp,
+# abi_dense_x6.hpp, dense_x6_kernels.hpp) and NOT from the plan that routes to them.  Frame: L (tvae_conv1_dft_frame),
+# Lh = L // 2 + 1 frequencies, Ho outputs per side; K2 = 2 k Cin (reduction of the spectral GEMMs), M = C R filter rows.
+DFT_RING_FRAMES = {1: (36, 17), 2: (80, 33), 3: (60, 39), 4: (44, 17), 5: (96, 33), 6: (66, 39)}   # (L, Ho) of ring 1 .. 6
+DFT_STEPS = ('out', 'dy', 'fwd_gemm', 'wgrad_gemm')                                             # `which` 0 .. 3
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def dft_instance_fits(which, rid, L, Ho, K2, M, parts):
+    Lh = L // 2 + 1
+    if which in (0, 1) and 1 <= rid <= 6:      # ring instances: compiled for one frame each
+        return (L, Ho) == DFT_RING_FRAMES[rid]
+    if which == 0:
+        if rid == 10:       # dft_out_h3_kernel<KS 11, NWT 5, NLD 5>: 2 Lh <= 16 KS, Ho <= 32 NWT, 16 Lh <= NLD 64 NWT; h3 only
+            return parts == 2 and 2 * Lh <= 16 * 11 and Ho <= 32 * 5 and 16 * Lh <= 5 * 64 * 5
+        if rid in (11, 12):  # dft_out_wide_kernel<LHR, NLD>: Lh <= LHR; NTW waves of 32 columns (the last column of
+            LHR, NLD = (82, 6) if rid == 11 else (96, 8)      # Ho = 32 NTW + 1 on the vector ALU), 64 NTW <= 512 threads,
+            NTW = Ho // 32 if (Ho % 32 == 1 and Ho > 32) else _cdiv(Ho, 32)                 # 16 Lh <= NLD 64 NTW
+            return Lh <= LHR and NTW <= 8 and 16 * Lh <= NLD * 64 * NTW and Ho <= 32 * NTW + 1
+        if 21 <= rid <= 25:  # dft_out_gen_kernel<NT>: NT whole 32-row output tiles
+            return Ho <= 32 * (rid - 20)
+        if 31 <= rid <= 39:  # dft_out_mf_kernel<LHP, NT, REM1>: Lh <= LHP; NT tiles of 32 rows; REM1: the one extra row w = 32 NT
+            LHP = (23, 49, 64)[(rid - 31) // 3]
+            NT, REM1 = ((1, False), (1, True), (2, False))[(rid - 31) % 3]
+            return Lh <= LHP and (Ho == 32 * NT + 1 if REM1 else Ho <= 32 * NT)
+    if which == 1:
+        if rid == 10:       # dft_dy_h3_kernel<WS 9, NKT 6, NLD 11>: Ho <= 16 WS, 2 Lh <= 32 NKT, 32 Ho <= NLD 64 NKT; h3 only
+            return parts == 2 and Ho <= 16 * 9 and 2 * Lh <= 32 * 6 and 32 * Ho <= 11 * 64 * 6
+        if rid in (11, 12, 13):   # dft_dy_wide_kernel<NSR, NLD 16, 2>: ceil(Ho / 2) k-steps <= NSR, NRT = ceil(2 Lh / 32) waves
+            NSR, NRT = {11: 50, 12: 66, 13: 80}[rid], _cdiv(2 * Lh, 32)            # of 64 <= 512 threads, 32 Ho <= NLD 64 NRT
+            return _cdiv(Ho, 2) <= NSR and NRT <= 8 and 32 * Ho <= 16 * 64 * NRT
+        if rid == 20:       # dft_dy_gen_kernel: sized at run time
+            return True
+        if 31 <= rid <= 35:  # dft_dy_mf_kernel<NS, NRT, LH2, AREG>: ceil(32 Ho / 64) <= NS, 2 Lh <= 32 NRT, LH2 = 0 or 2 Lh
+            NS, NRT, LH2 = ((9, 2, 46), (9, 2, 0), (17, 4, 98), (17, 4, 0), (32, 4, 0))[rid - 31]
+            return _cdiv(32 * Ho, 64) <= NS and 2 * Lh <= 32 * NRT and LH2 in (0, 2 * Lh)
+    if which == 2:
+        if rid == 1:        # dense_x6_xres_kernel<NP, NK>: 2 or 3 parts, NK = 8 / 10 / 12 k-steps of 16, whole 512-row problems,
+            nk, Mb = _cdiv(K2, 16), _cdiv(2 * M, 512) * 512    # the cells of a k-step and the row scales in 160 KB of LDS
+            return parts in (2, 3) and nk in (8, 10, 12) and (2 * M) % 512 == 0 and \
+                nk * parts * 256 * 16 + (Mb + 128) * 4 <= 160 * 1024
+        if rid == 2:        # dense_x6_plain4_kernel: the 256-row tile of short reductions
+            return K2 <= 256
+        return rid == 3     # dense_x6_kernel: the 512-row tile, any reduction
+    if which == 3:
+        if rid == 2:        # dense_wgrad_x6_wide_kernel: 256-row tiles, 2 L Cin > 128 columns, split arithmetics only
+            return parts != 1 and (2 * M) % 256 == 0 and K2 > 128
+        return rid == 1     # dense_wgrad_x6 512 x 128 tile, any shape
+    return False
+
+
+def dft_sweep_geometries():
+    """One (n, k, pad) per distinct frame (L, Ho) with 8 <= n <= 256 (k <= 256, pad < 200, Ho <= 192: the plan takes at most
+    five 32-row output tiles, so a margin of unsupported frames is included): the smallest filter that makes the frame and
+    the largest.  L as documented in include/tvae_hip.h: max(n + pad, k) rounded up to a multiple of 4, at most n + 2 pad."""
+    n = np.arange(8, 257)[:, None, None]
+    k = np.arange(1, 257)[None, :, None]
+    p = np.arange(0, 200)[None, None, :]
+    Ho = n + 2 * p - k + 1
+    Lmin = (np.maximum(n + p, k) + 3) & ~3
+    L = np.where(Lmin > n + 2 * p, n + 2 * p, Lmin)
+    sel = (Ho >= 1) & (Ho <= 192)
+    N, K, P = np.broadcast_arrays(n, k, p)
+    Lv, Hv, Nv, Kv, Pv = L[sel], Ho[sel], N[sel], K[sel], P[sel]
+    key = Lv.astype(np.int64) * 1000 + Hv
+    o = np.lexsort((Nv, Kv, key))
+    ks = key[o]
+    edge = ks[1:] != ks[:-1]
+    pick = np.unique(np.concatenate([o[np.r_[True, edge]], o[np.r_[edge, True]]]))
+    return [(int(a), int(b), int(c), int(d), int(e)) for a, b, c, d, e in zip(Nv[pick], Kv[pick], Pv[pick], Lv[pick], Hv[pick])]
+
+
+DFT_SWEEP_CR = ((5, 4), (32, 8))     # 2 M = 40: no whole tile; 512: whole 256-row (weight gradient) and 512-row (forward) tiles
+DFT_SWEEP_B = 2
+
+
+def test_conv1_dft_routes_fit_their_instances_and_are_covered_on_the_gpu():
+    """Every frame reachable with 8 <= n <= 256, one and three input channels, three filter counts, parts 1 / 2 / 3: the
+    instance each step takes (tvae_conv1_dft_route) is one whose capacity, as its header states it, holds for the geometry;
+    unsupported geometries route nowhere; the transforms take the ring instance exactly when tvae_conv1_dft_ring says so.
+    Every (step, instance, parts) seen here must be reached by a geometry of the GPU boundary test
+    (tests/test_hip_primitives.py::DFT_ROUTE_GEOMETRIES), so a new route fails here until a GPU test covers it."""
+    from test_hip_primitives import DFT_EDGE_GEOMETRIES, DFT_ROUTE_GEOMETRIES
+    from tvae import _lib
+    L_ = _lib.lib()
+    route, supported, frame, ring = (L_.tvae_conv1_dft_route, L_.tvae_conv1_dft_supported, L_.tvae_conv1_dft_frame,
+                                     L_.tvae_conv1_dft_ring)
+    seen, bad, checked, n_ok = {}, [], {}, 0
+    for n, k, pad, L, Ho in dft_sweep_geometries():
+        assert frame(DFT_SWEEP_B, 1, n, k, pad, 4, 4) == L, (n, k, pad, L)
+        rg = ring(DFT_SWEEP_B, 1, n, k, pad, 4, 4)
+        for Cin in (1, 3):
+            K2 = 2 * k * Cin
+            for C, R in DFT_SWEEP_CR:
+                ok = supported(DFT_SWEEP_B, Cin, n, k, pad, C, R)
+                n_ok += ok
+                if not ok:
+                    for which in range(4):
+                        if route(DFT_SWEEP_B, Cin, n, k, pad, C, R, 2, which) != -1:
+                            bad.append(('unsupported but routed', DFT_STEPS[which], (n, k, pad, Cin, C, R)))
+                    continue
+                for parts in (1, 2, 3):
+                    for which in range(4):
+                        rid = route(DFT_SWEEP_B, Cin, n, k, pad, C, R, parts, which)
+                        if which < 2 and (rid if 1 <= rid <= 6 else 0) != rg:
+                            bad.append(('ring', DFT_STEPS[which], rid, rg, (n, k, pad)))
+                        ck = (which, rid, L, Ho, parts) if which < 2 else (which, rid, K2, C * R, parts)
+                        fits = checked.get(ck)
+                        if fits is None:
+                            fits = checked[ck] = dft_instance_fits(which, rid, L, Ho, K2, C * R, parts)
+                        if not fits:
+                            bad.append(('over capacity', DFT_STEPS[which], rid, parts,
+                                        dict(n=n, k=k, pad=pad, Cin=Cin, C=C, R=R, L=L, Ho=Ho)))
+                        seen.setdefault((which, rid, parts), (n, k, pad, Cin, C, R))
+    assert n_ok > 10000
+    assert not bad, '%d geometries routed beyond an instance (Ho %s), e.g.:\n%s' % (
+        len(bad), sorted({b[-1]['Ho'] for b in bad if b[0] == 'over capacity'}), '\n'.join(map(str, bad[:40])))
+    gpu = set()
+    for B, Cin, n, k, pad, C, R, act in DFT_ROUTE_GEOMETRIES:
+        assert supported(B, Cin, n, k, pad, C, R), (B, Cin, n, k, pad, C, R)
+        for parts in (1, 2, 3):
+            for which in range(4):
+                gpu.add((which, route(B, Cin, n, k, pad, C, R, parts, which), parts))
+    missing = sorted(set(seen) - gpu)
+    assert not missing, 'routes without a GPU test (step, id, parts) -> an example (n, k, pad, Cin, C, R):\n%s' % '\n'.join(
+        '%s %s parts %d: %s' % (DFT_STEPS[w], r, p, seen[(w, r, p)]) for w, r, p in missing)
+    # ... and every transform instance that h3 reaches has its edge-placed maxima test (test_conv1_dft_h3_edge_placed_maxima)
+    edge = {(w, route(B, Cin, n, k, pad, C, R, 2, w)) for B, Cin, n, k, pad, C, R, act in DFT_EDGE_GEOMETRIES for w in (0, 1)}
+    assert {(w, r) for w, r, p in seen if w < 2 and p == 2} <= edge
