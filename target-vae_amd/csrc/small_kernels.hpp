@@ -449,6 +449,14 @@ static __global__ void fourier_bwd_kernel(const float* __restrict__ xr, const fl
 // train_particles.py:284-296,336-338).  kind: 0 BCE-with-logits, 1 Gaussian, 2 Gaussian with learned log-variance
 // (mu = yh[i], logvar = yh[L+i], i < L).
 // ------------------------------------------------------------------------------------------
+// One pixel's Gaussian term subtracted from a running sum, as two roundings of its own (0.5 d * d, then the subtraction) under
+// every compiler choice: the plain and the masked kernel contracted it differently (fma in one of them), and a mask that keeps
+// every pixel has to give bit for bit the plain likelihood (tests/test_hip_primitives.py::test_loglik_masked).
+__device__ __forceinline__ float gauss_sub(float acc, float d) {
+#pragma clang fp contract(off)
+    const float t = (0.5f * d) * d;
+    return acc - t;
+}
 static __global__ void loglik_fwd_kernel(const float* __restrict__ yh, const float* __restrict__ y, float* __restrict__ lp,
                                   int L, int kind) {
     __shared__ float sm[16];
@@ -460,7 +468,7 @@ static __global__ void loglik_fwd_kernel(const float* __restrict__ yh, const flo
     for (int i = threadIdx.x; i < L; i += blockDim.x) {
         const float x = a[i], yy = t[i];
         if (kind == 0) acc[0] -= fmaxf(x, 0.f) - x * yy + log1pf(expf(-fabsf(x)));
-        else if (kind == 1) acc[0] -= 0.5f * (x - yy) * (x - yy);
+        else if (kind == 1) acc[0] = gauss_sub(acc[0], x - yy);
         else { const float lv = a[L + i]; acc[0] -= 0.5f * ((x - yy) * (x - yy) * expf(-lv) + lv); }
     }
     block_sum<1>(acc, sm);
@@ -536,8 +544,7 @@ static __global__ void loglik_masked_fwd_kernel(const float* __restrict__ yh, co
     for (int t = threadIdx.x; t < L; t += blockDim.x) {
         const int i = t / n, j = t - i * n;
         if (mask_keep(i, j, n, cx, cy, r2)) {
-            const float d = yh[(long)b * L + t] - y[(long)b * L + t];
-            acc[0] -= 0.5f * d * d;
+            acc[0] = gauss_sub(acc[0], yh[(long)b * L + t] - y[(long)b * L + t]);
         }
     }
     block_sum<1>(acc, sm);

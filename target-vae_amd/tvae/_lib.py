@@ -304,15 +304,37 @@ def _ptr(t, name, pos):
     return t.data_ptr()
 
 
+# debugging aid (None by default, one `if` per call): a callable hook(name, sig, args, do_call) that decides how a call runs --
+# `args` is the complete argument tuple (optional tails filled in), `do_call(args)` launches the entry point on those
+# arguments and raises TvaeHipError on an error code.  tests/guardband.py uses it to run every launch on relocated,
+# guard-banded copies of its tensors.  Looked up here at call time (tvae.ops binds `call` by name); bypassed while the
+# current stream is capturing: a captured graph must hold the real pointers.
+CALL_HOOK = None
+
+
+def set_call_hook(hook):
+    """Install (or, with None, remove) the call hook; returns the previous one."""
+    global CALL_HOOK
+    old, CALL_HOOK = CALL_HOOK, hook
+    return old
+
+
 def call(name, *args):
     """Invoke a C-ABI entry point on the current torch stream."""
-    L = lib()
     sig = SIGNATURES[name]
     if len(args) < len(sig) and (set(sig[len(args):]) == {'p'} or len(sig) - len(args) <= OPTIONAL_TAIL.get(name, 0)):
         # optional trailing arguments (added by later ABI versions): NULL pointers / zero strides
         args = args + tuple(None if c == 'p' else 0 for c in sig[len(args):])
     if len(args) != len(sig):
         raise TvaeHipError(f'{name}: expected {len(sig)} arguments, got {len(args)}')
+    hook = CALL_HOOK
+    if hook is not None and not torch.cuda.is_current_stream_capturing():
+        return hook(name, sig, tuple(args), lambda a: _launch(name, sig, a))
+    _launch(name, sig, args)
+
+
+def _launch(name, sig, args):
+    L = lib()
     conv = []
     for pos, (c, a) in enumerate(zip(sig, args)):
         if c == 'p':

@@ -270,6 +270,25 @@ def test_step_hot_widths_golden(name, gemm_mode):
         assert_grad_close(t.grad, fx['gd.' + k_], tol=max(GRAD_TOL, 2 * float(fx['kd.' + k_])), name='gen.' + k_)
 
 
+# (n, z_dim, R, B, C, hidden, k, padding, Fourier decoder) of the two memory-safety tests below
+OOB_CONFIGS = {'small': (20, 2, 8, 8, 8, 32, 20, 4, False),
+               'small_fourier': (20, 2, 8, 8, 8, 32, 20, 4, True),
+               'S28': (28, 2, 8, 16, 128, 512, 28, 14, False),
+               'S28F': (28, 2, 16, 8, 128, 512, 28, 14, True),
+               'S64': (64, 2, 8, 4, 128, 512, 64, 16, False),
+               # B * Ho a multiple of 32 (as at the bench's B = 256): no ragged last tile
+               'S64x': (64, 2, 8, 32, 128, 512, 64, 16, False),
+               'M50x': (50, 2, 8, 32, 128, 512, 28, 8, False),
+               # the reference's MNIST geometries (k = 28, padding 8): the 44- and 66-wide ring
+               # transforms; M28r: a batch whose last 32-column tile is ragged
+               'M28': (28, 2, 8, 32, 128, 512, 28, 8, False),
+               'M28r': (28, 2, 8, 5, 128, 512, 28, 8, False),
+               'M50': (50, 2, 8, 4, 128, 512, 28, 8, False),
+               # round 5: a large frame (L = 112, Ho = 97 = 3 x 32 + 1): the WIDE generic transforms
+               # along w (workgroup per tile, extra output column on the vector ALU), ragged batch
+               'G96': (96, 2, 8, 3, 16, 64, 32, 16, False)}
+
+
 @pytest.mark.parametrize('cfg', ['small', 'small_fourier', 'S28', 'S28F', 'S64', 'S64x', 'M28', 'M28r', 'M50', 'M50x', 'G96'])
 def test_step_does_not_read_out_of_bounds(cfg):
     """Out-of-bounds READ detector.  Every float tensor the step allocates (torch.empty / torch.zeros, workspaces
@@ -281,22 +300,7 @@ def test_step_does_not_read_out_of_bounds(cfg):
     Full kernel widths (C = 128, hidden 512) at small batches."""
     import src.models as M
     from tvae import ops, step, tables
-    n, zd, R, B, C, hid, k, pad, four = {'small': (20, 2, 8, 8, 8, 32, 20, 4, False),
-                                         'small_fourier': (20, 2, 8, 8, 8, 32, 20, 4, True),
-                                         'S28': (28, 2, 8, 16, 128, 512, 28, 14, False),
-                                         'S28F': (28, 2, 16, 8, 128, 512, 28, 14, True),
-                                         'S64': (64, 2, 8, 4, 128, 512, 64, 16, False),
-                                         # B * Ho a multiple of 32 (as at the bench's B = 256): no ragged last tile
-                                         'S64x': (64, 2, 8, 32, 128, 512, 64, 16, False),
-                                         'M50x': (50, 2, 8, 32, 128, 512, 28, 8, False),
-                                         # the reference's MNIST geometries (k = 28, padding 8): the 44- and 66-wide ring
-                                         # transforms; M28r: a batch whose last 32-column tile is ragged
-                                         'M28': (28, 2, 8, 32, 128, 512, 28, 8, False),
-                                         'M28r': (28, 2, 8, 5, 128, 512, 28, 8, False),
-                                         'M50': (50, 2, 8, 4, 128, 512, 28, 8, False),
-                                         # round 5: a large frame (L = 112, Ho = 97 = 3 x 32 + 1): the WIDE generic transforms
-                                         # along w (workgroup per tile, extra output column on the vector ALU), ragged batch
-                                         'G96': (96, 2, 8, 3, 16, 64, 32, 16, False)}[cfg]
+    n, zd, R, B, C, hid, k, pad, four = OOB_CONFIGS[cfg]
     torch.manual_seed(0)
     gen = M.SpatialGenerator(zd, hid, num_layers=2, fourier_expansion=four, sigma=2.0 / (n - 1)).to(dev())
     enc = M.InferenceNetwork_AttentionTranslation_AttentionRotation(
@@ -346,6 +350,150 @@ def test_step_does_not_read_out_of_bounds(cfg):
         assert e1 == e0, (g, e0, e1)
         for k_ in g0:
             assert torch.equal(g0[k_], g1[k_]), (g, k_)
+
+
+def _bits_equal(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and \
+        torch.equal(a.contiguous().reshape(-1).view(torch.uint8), b.contiguous().reshape(-1).view(torch.uint8))
+
+
+def _oob_case(case):
+    """run() of one configuration of test_step_does_not_write_out_of_bounds: a closure that performs the whole computation from
+    the same inputs on every call and returns {name: tensor} of everything it produced."""
+    import src.models as M
+    from tvae import latent, ops, optim, step, tables
+
+    def fresh(n, zd, R, B, C, hid, k, pad, four, cin=1):
+        torch.manual_seed(0)
+        gen = M.SpatialGenerator(zd, hid, num_layers=2, fourier_expansion=four, sigma=2.0 / (n - 1)).to(dev())
+        enc = M.InferenceNetwork_AttentionTranslation_AttentionRotation(
+            n, cin, zd, kernels_num=C, kernels_size=k, padding=pad, groupconv=R, rot_refinement=True, theta_prior=np.pi,
+            normal_prior_over_r=False).to(dev())
+        x = torch.from_numpy(tables.image_coords(n)).to(dev())
+        y = torch.randn(B, cin, n, n, device=dev())
+        nz = step.draw_noise(B, R * enc.output_size() ** 2, zd, dev())
+        return gen, enc, x, y, nz
+
+    def step_run(gen, enc, terms):
+        params = list(gen.named_parameters()) + list(enc.named_parameters())
+
+        def run():
+            for _, p in params:
+                p.grad = None
+            e, lp, kl = terms()
+            (-e).backward()
+            out = {'elbo': e.detach().clone(), 'log_p': lp.detach().clone(), 'kl': kl.detach().clone()}
+            out.update({'grad.' + k_: p.grad.clone() for k_, p in params})
+            return out
+        return run
+
+    def encoder_run(enc, y, zd, R):
+        Ho = enc.output_size()
+        B = y.shape[0]
+        g = torch.Generator(device=dev()).manual_seed(1)
+        wts = [torch.randn(B, R, Ho, Ho, device=dev(), generator=g), torch.randn(B, 2, R, Ho, Ho, device=dev(), generator=g),
+               torch.randn(B, 2 * zd, R, Ho, Ho, device=dev(), generator=g)]
+
+        def run():
+            for p in enc.parameters():
+                p.grad = None
+            torch.manual_seed(77)                        # the encoder draws its Gumbel noise itself
+            attn, q, p_r, a, off, theta, z = enc(y, dev())
+            ((q * wts[0]).sum() + (theta * wts[1]).sum() + (z * wts[2]).sum()).backward()
+            out = {k_: t.detach().clone() for k_, t in (('attn', attn), ('q', q), ('a', a), ('theta', theta), ('z', z))}
+            out.update({'grad.' + k_: p.grad.clone() for k_, p in enc.named_parameters()})
+            return out
+        return run
+
+    if case in OOB_CONFIGS:
+        gen, enc, x, y, nz = fresh(*OOB_CONFIGS[case])
+        return step_run(gen, enc, lambda: step.elbo_terms(x, y, gen, enc, 'gauss', nz))
+    if case in ('heads103', 'heads103_x32'):
+        # z_dim = 50: 103 head rows (the wide encoder tail in h3); second geometry: a column count that is a multiple of 32
+        (n, k, pad, B), R, zd = {'heads103': (20, 20, 4, 3), 'heads103_x32': (21, 20, 3, 2)}[case], 4, 50
+        torch.manual_seed(5)
+        enc = M.InferenceNetwork_AttentionTranslation_AttentionRotation(n, 1, zd, kernels_num=128, kernels_size=k, padding=pad,
+                                                                        groupconv=R, rot_refinement=True, theta_prior=np.pi,
+                                                                        normal_prior_over_r=False).to(dev())
+        with torch.no_grad():
+            for m in (enc.conv_a, enc.conv_r, enc.conv_z):
+                m.weight.mul_(8.0)
+        return encoder_run(enc, torch.rand(B, 1, n, n, device=dev()), zd, R)
+    if case == 'cin3_direct':
+        # three input channels through the DIRECT convolution kernels (fp32 MFMA in f32, the LDS-resident split kernels
+        # otherwise): the frequency-domain route is switched off for this case
+        n, k, pad, B, R, zd = 20, 9, 3, 5, 4, 2
+        torch.manual_seed(6)
+        enc = M.InferenceNetwork_AttentionTranslation_AttentionRotation(n, 3, zd, kernels_num=128, kernels_size=k, padding=pad,
+                                                                        groupconv=R, rot_refinement=True, theta_prior=np.pi,
+                                                                        normal_prior_over_r=False).to(dev())
+        inner = encoder_run(enc, torch.rand(B, 3, n, n, device=dev()), zd, R)
+
+        def run():
+            old, ops.CONV_DFT = ops.CONV_DFT, False
+            try:
+                return inner()
+            finally:
+                ops.CONV_DFT = old
+        return run
+    if case == 'inference_latent':
+        gen, enc, x, y, nz = fresh(*OOB_CONFIGS['M28r'])
+
+        def run():
+            with torch.no_grad():
+                e, lp, kl = step.elbo_terms(x, y, gen, enc, 'gauss', nz)
+            zc, th, dx = latent.get_latent(x, y, enc, 'attention', 'attention+offsets', dev(), y.shape[-1])
+            return {k_: t.detach().clone() for k_, t in (('elbo', e), ('log_p', lp), ('kl', kl), ('zc', zc), ('th', th), ('dx', dx))}
+        return run
+    if case in ('particles_ctf_mask', 'galaxy_fourier_nout3'):
+        fx = load_golden('step_particles32_ctf_mask' if case == 'particles_ctf_mask' else 'step_galaxy_small')
+        enc, gen, n = build_step_models(fx)
+        x = O.image_coords(n).to(dev())
+        noise = tuple(torch.from_numpy(fx[k_]).to(dev()) for k_ in ('E', 'eps_z', 'eps_theta'))
+        yy = torch.from_numpy(fx['y']).to(dev())
+        if case == 'particles_ctf_mask':
+            ctf = torch.from_numpy(fx['ctf']).to(dev())
+            return step_run(gen, enc, lambda: step.eval_minibatch_particles(x, yy, ctf, gen, enc, 'attention', 'attention+offsets', 0,
+                                                                            dev(), np.pi, 8, 8, int(fx['mask_radius']), noise=noise))
+        assert [int(v) for v in fx['cfg']][11:13] == [3, 1]          # n_out = 3, Fourier decoder
+        return step_run(gen, enc, lambda: step.elbo_terms(x, yy, gen, enc, 'bce', noise))
+    assert case == 'adam'
+
+    def run():                                           # two training steps over the flat buffers, from the same initial state
+        gen, enc, x, y, nz = fresh(*OOB_CONFIGS['small'])
+        opt = optim.FlatAdam(list(gen.parameters()) + list(enc.parameters()), lr=2e-3)
+        for _ in range(2):
+            e, _, _ = step.elbo_terms(x, y, gen, enc, 'gauss', nz)
+            step.backward_neg_elbo(e)
+            opt.step()
+            opt.zero_grad(set_to_none=True)
+        return {'elbo': e.detach().clone(), 'p': opt.flat_p.clone(), 'm': opt.flat_m.clone(), 'v': opt.flat_v.clone()}
+    return run
+
+
+@pytest.mark.parametrize('case', sorted(OOB_CONFIGS) + ['heads103', 'heads103_x32', 'cin3_direct', 'inference_latent',
+                                                        'particles_ctf_mask', 'galaxy_fourier_nout3', 'adam'])
+def test_step_does_not_write_out_of_bounds(case, gemm_mode):
+    """Out-of-bounds WRITE detector (tests/guardband.py).  Every C-ABI launch of the step runs on relocated copies of its
+    tensors -- integer sign words, torch.empty_like outputs and workspace VIEWS included -- between guard bands that must
+    come back untouched.  The configurations of the read test above, forward + backward, and: 103 head rows, the inference
+    forward followed by get_latent, the particle tail with CTF and mask, a Fourier decoder with three outputs (the galaxy
+    fixture: three input channels, z_dim 50), three input channels through the direct convolution, two Adam steps over the
+    flat buffers.  In f32 / x6 / h3 (the file's fixture) and, beside h3, in the bf16 throughput mode.
+    Everything the guarded run produces must be BITWISE what the same run gives without the guard in the same process: the
+    relocation keeps every pointer modulo 256 bytes, so the guarded launches are the kernel instances production runs."""
+    import guardband
+    from tvae import _lib
+    run = _oob_case(case)
+    for mode in [gemm_mode] + (['bf16'] if gemm_mode == 'h3' else []):
+        with _lib.arithmetic(mode):
+            want = run()
+            with guardband.GuardedCalls() as g:
+                got = run()
+        assert g.calls > 0
+        assert sorted(want) == sorted(got)
+        for k_ in want:
+            assert _bits_equal(want[k_], got[k_]), (mode, k_)
 
 
 @pytest.mark.parametrize('name', ['hot_S28F_B8', 'hot_S64_B2'])

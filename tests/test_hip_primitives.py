@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import guardband
 from conftest import rel_err
 from oracle import tvae_oracle as O
 
@@ -22,6 +23,15 @@ GEMM_TOL = {'f32': 2e-5}
 @pytest.fixture(params=['f32'])
 def gemm_mode(request):
     return request.param
+
+
+@pytest.fixture(autouse=True)
+def guarded_calls():
+    """Every test of this file runs each of its C-ABI calls on relocated tensors between guard bands, twice from the same
+    inputs (tests/guardband.py): a store outside a tensor, a read outside one that reaches a result, and a result that
+    differs between two runs all fail the test (reported at teardown, with the call).  No test runs with replay off."""
+    with guardband.GuardedCalls(replay=True):
+        yield
 
 
 def dev():
@@ -1339,12 +1349,21 @@ def test_coord():
     assert rel_err(dxg.grad, dx.grad) < TOL and rel_err(thg.grad, th.grad) < TOL
 
 
-@pytest.mark.parametrize('kind,name', [(0, 'bce'), (1, 'gauss'), (2, 'gauss_var')])
-def test_loglik(kind, name):
-    B, L = 3, 500
-    y = torch.rand(B, L, generator=torch.Generator().manual_seed(1))
-    yh = rnd(B, 2 * L if kind == 2 else L, seed=2, scale=2.0).requires_grad_(True)
-    w = rnd(B, seed=3)
+@pytest.mark.parametrize('kind,name,B,L,spikes', [
+    pytest.param(k_, n_, B_, L_, s_, id=f'{k_}-{n_}' + i_)
+    for B_, L_, s_, i_ in ((3, 500, False, ''), (3, 500, True, '-spikes'), (2, 16384 + 37, True, '-B2-L16421-spikes'),
+                           (300, 20000, False, '-B300-L20000'))
+    for k_, n_ in ((0, 'bce'), (1, 'gauss'), (2, 'gauss_var'))])
+def test_loglik(kind, name, B, L, spikes):
+    """Against float64.  (2, 16 384 + 37): the 1024-thread instance of the forward (B < 256 and L >= 16 384) with a ragged
+    last round; (300, 20 000): the 256-thread instance just beyond that boundary in B; spikes: logits / means of +-60 in a
+    few positions (exp(-|x|) underflows towards 0, the stable form of the BCE has to hold)."""
+    y = torch.rand(B, L, generator=torch.Generator().manual_seed(1)).double()
+    yh = rnd(B, 2 * L if kind == 2 else L, seed=2, scale=2.0)
+    if spikes:
+        yh[0, 0], yh[0, L - 1], yh[B - 1, L // 2], yh[B - 1, 1] = 60.0, -60.0, 60.0, -60.0
+    yh = yh.double().requires_grad_(True)
+    w = rnd(B, seed=3).double()
     if kind == 0:
         per = -(F.binary_cross_entropy_with_logits(yh, y, reduction='none')).sum(1)
     elif kind == 1:
@@ -1354,15 +1373,21 @@ def test_loglik(kind, name):
     (per * w).sum().backward()
     assert abs(float(per.mean()) - float(O.likelihood_logp(yh.detach(), y, name))) < 1e-3 * abs(float(per.mean()))
     from tvae import ops
-    yg = yh.detach().to(dev()).requires_grad_(True)
-    lp = ops.LogLikFn.apply(yg, y.to(dev()), kind)
+    yg = yh.detach().float().to(dev()).requires_grad_(True)
+    lp = ops.LogLikFn.apply(yg, y.float().to(dev()), kind)
     assert rel_err(lp, per) < TOL
-    (lp * w.to(dev())).sum().backward()
+    (lp * w.float().to(dev())).sum().backward()
     assert rel_err(yg.grad, yh.grad) < TOL
 
 
 def test_adam_flat():
-    n = 10001
+    """n > 2048 x 256: the grid-stride loop of the kernel takes more than one round; grad_scale (the data-parallel average)
+    against torch's Adam on the scaled gradient, moments included."""
+    for n, grad_scale in ((10001, 1.0), (2048 * 256 + 12345, 0.25)):
+        _adam_flat_case(n, grad_scale)
+
+
+def _adam_flat_case(n, grad_scale):
     p0, steps = rnd(n, seed=1), 3
     p_ref = p0.clone().requires_grad_(True)
     opt = torch.optim.Adam([p_ref], lr=2e-4)
@@ -1372,10 +1397,16 @@ def test_adam_flat():
     from tvae import ops
     for s in range(steps):
         g = rnd(n, seed=10 + s)
-        p_ref.grad = g.clone()
+        p_ref.grad = g * grad_scale                  # 0.25: exact in fp32
         opt.step()
-        ops.adam_flat(p, g.to(dev()), m, v, s + 1, 2e-4)
+        ops.adam_flat(p, g.to(dev()), m, v, s + 1, 2e-4, grad_scale=grad_scale)
     assert rel_err(p, p_ref.detach()) < 1e-6
+    # The moments.  The C ABI takes b1 / b2 as float32 and the kernel forms 1 - b from them, torch forms 1 - b in double: the
+    # rounding of float32(b), at most 2^-24 b, is magnified by 1 / (1 - b) in the weight of the new gradient -- a relative 5.4e-7
+    # for m (b1 = 0.9) and 6.0e-5 for v (b2 = 0.999; float32(0.999) gives 1.3e-5) -- plus 16 fp32 roundings over the three steps.
+    u = 2.0 ** -24
+    assert rel_err(m, opt.state[p_ref]['exp_avg']) < u * 0.9 / 0.1 + 16 * u
+    assert rel_err(v, opt.state[p_ref]['exp_avg_sq']) < u * 0.999 / 0.001 + 16 * u
 
 
 def _head_reference(hd, E, eps_z, eps_t, R, Ho, zd, refine, theta_prior, normal, spacing):
@@ -1427,10 +1458,12 @@ def test_attn_head(R, Ho, zd, refine, normal, scale):
     assert rel_err(hg.grad, hr.grad) < 2e-4
 
 
-@pytest.mark.parametrize('fourier,zd,F_', [(False, 2, 64), (True, 3, 32)])
-def test_decoder_ends(fourier, zd, F_):
-    """dec_l0 / latent / fourier kernels against torch."""
-    B, Np = 2, 50
+@pytest.mark.parametrize('fourier,zd,F_,B', [pytest.param(False, 2, 64, 2, id='False-2-64'), pytest.param(True, 3, 32, 2, id='True-3-32'),
+                                             pytest.param(False, 3, 16, 40, id='False-3-16-B40')])
+def test_decoder_ends(fourier, zd, F_, B):
+    """dec_l0 / latent / fourier kernels against torch.  B = 40, F = 16: B zd > F zd, the other half of latent_bwd's index space,
+    and more images than one round of its slices."""
+    Np = 50
     Nt = B * Np
     xr = (torch.rand(B, Np, 2, generator=torch.Generator().manual_seed(1)) * 2 - 1)
     z = rnd(B, zd, seed=2)
@@ -1673,3 +1706,243 @@ def test_linear_x6_lean_store_epilogue_and_measured_maximum(M, K, parts):
     with pytest.raises(Exception):                       # y_amax needs a stored output with nothing fused behind it
         call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, None, M, N, K, N, N, 1, SLOPE, None, None, None, None, None, None,
              None, 0, None, parts, xmax, amax)
+
+
+# ---- the guard itself on the real library, and the entry points no other test of this file reaches --------------------------
+def test_guard_reports_a_planted_one_word_overrun():
+    """Positive control of tests/guardband.py on the real library: tvae_seg_sum is told L outputs but given a VIEW of L - 1 of a
+    tensor that has L.  Unguarded the call is legal (every address lies in the caller's own tensor); guarded, the last store
+    falls into the band behind `out`, and the report has to say exactly that: one word, offset 0, argument 3."""
+    from tvae import _lib
+    S, L = 5, 300
+    X = rnd(S, L, seed=1).to(dev())
+    full = torch.zeros(L, device=dev())
+    short = full[:L - 1]
+    with pytest.raises(guardband.GuardViolation) as ei:
+        with guardband.GuardedCalls():
+            call('tvae_seg_sum', X, S, L, short, 1.0, 0)
+    (v,) = ei.value.violations
+    assert (v['entry'], v['kind'], v['args'], v['side'], v['count'], v['first'], v['last']) == \
+        ('tvae_seg_sum', 'band', (3,), 'behind', 1, 0, 0), v
+    assert v['scalars'] == {1: S, 2: L, 4: 1.0, 5: 0} and 'tvae_seg_sum' in str(ei.value)
+    ref = X.double().sum(0)
+    assert rel_err(short, ref[:L - 1]) < TOL and float(full[L - 1]) == 0.0     # the interior came back, nothing else did
+    old = _lib.set_call_hook(None)
+    try:
+        call('tvae_seg_sum', X, S, L, short, 1.0, 0)
+    finally:
+        _lib.set_call_hook(old)
+    assert rel_err(full, ref) < TOL
+
+
+@pytest.mark.parametrize('B', [1, 3, 256, 257, 1000])
+def test_elbo_reduce(B):
+    """tvae_elbo_reduce / _bwd.  The kernel sums in double: kld within 1e-12 of the exact mean (B 2^-53 << 1e-12), logp within one
+    float32 ulp of float32(exact mean), elbo == double(logp) - kld exactly from the returned values.  Backward: the eight
+    NULL / non-NULL combinations of the upstream gradients, every element exactly float32((g_elbo + g_logp) / B) resp.
+    float32((g_kld - g_elbo) / B)."""
+    g = torch.Generator().manual_seed(100 + B)
+    lp = -700.0 + 50.0 * torch.randn(B, generator=g)
+    kl = 10.0 + 3.0 * torch.randn(B, generator=g)
+    elbo = torch.empty((), dtype=torch.float64, device=dev())
+    logp = torch.empty((), dtype=torch.float32, device=dev())
+    kld = torch.empty((), dtype=torch.float64, device=dev())
+    call('tvae_elbo_reduce', lp.to(dev()), kl.to(dev()), B, elbo, logp, kld)
+    kl_ref = math.fsum(kl.double().tolist()) / B
+    lp_ref = np.float32(math.fsum(lp.double().tolist()) / B)
+    assert abs(kld.item() - kl_ref) <= 1e-12 * abs(kl_ref), (kld.item(), kl_ref)
+    assert abs(float(logp.item()) - float(lp_ref)) <= float(np.spacing(np.abs(lp_ref))), (logp.item(), lp_ref)
+    assert elbo.item() == float(logp.item()) - kld.item()
+    ge, gl, gk = -1.25, 0.3, 2.5
+    for combo in range(8):
+        t_ge = torch.tensor(ge, dtype=torch.float64, device=dev()) if combo & 1 else None
+        t_gl = torch.tensor(gl, dtype=torch.float32, device=dev()) if combo & 2 else None
+        t_gk = torch.tensor(gk, dtype=torch.float64, device=dev()) if combo & 4 else None
+        g_lp = torch.full((B,), float('nan'), device=dev())
+        g_kl = torch.full((B,), float('nan'), device=dev())
+        call('tvae_elbo_reduce_bwd', t_ge, t_gl, t_gk, B, g_lp, g_kl)
+        e_, l_, k_ = ge if combo & 1 else 0.0, float(np.float32(gl)) if combo & 2 else 0.0, gk if combo & 4 else 0.0
+        want_lp, want_kl = np.float32((e_ + l_) / B), np.float32((k_ - e_) / B)
+        assert (g_lp.cpu().numpy() == want_lp).all() and (g_kl.cpu().numpy() == want_kl).all(), combo
+    with pytest.raises(Exception):
+        call('tvae_elbo_reduce', lp.to(dev()), kl.to(dev()), 0, elbo, logp, kld)
+    with pytest.raises(Exception):
+        call('tvae_elbo_reduce', lp.to(dev()), kl.to(dev()), B, elbo, None, kld)
+    with pytest.raises(Exception):
+        call('tvae_elbo_reduce_bwd', None, None, None, 0, g_lp, g_kl)
+    with pytest.raises(Exception):
+        call('tvae_elbo_reduce_bwd', None, None, None, B, g_lp, None)
+
+
+@pytest.mark.parametrize('B,n,kc', [(3, 32, 31), (2, 32, 33), (5, 17, 5), (1, 40, 1), (2, 64, 63)])
+def test_ctf_corr(B, n, kc):
+    """Per-image cross-correlation with an odd filter (kc = 33 > n: the filter is larger than the image) against conv2d in
+    float64; flip = 1 against autograd's gradient with respect to the input; and the two as adjoints of each other."""
+    x, ctf, g = rnd(B, n * n, seed=1), rnd(B, kc * kc, seed=2, scale=1.0 / kc), rnd(B, n * n, seed=3)
+    x64 = x.double().view(1, B, n, n).requires_grad_(True)
+    ref = F.conv2d(x64, ctf.double().view(B, 1, kc, kc), padding=kc // 2, groups=B)
+    (ref.view(B, -1) * g.double()).sum().backward()
+    out = torch.full((B, n * n), float('nan'), device=dev())
+    call('tvae_ctf_corr', x.to(dev()), ctf.to(dev()), out, B, n, kc, 0)
+    assert rel_err(out, ref.detach().view(B, -1)) < TOL
+    gi = torch.full((B, n * n), float('nan'), device=dev())
+    call('tvae_ctf_corr', g.to(dev()), ctf.to(dev()), gi, B, n, kc, 1)
+    assert rel_err(gi, x64.grad.view(B, -1)) < TOL
+    lhs, rhs = float((out.double().cpu() * g.double()).sum()), float((x.double() * gi.double().cpu()).sum())
+    assert abs(lhs - rhs) <= 1e-5 * float(out.double().norm()) * float(g.double().norm()), (lhs, rhs)
+    with pytest.raises(Exception):                 # an even filter has no centre (kc - 1: within the tensors given either way)
+        call('tvae_ctf_corr', x.to(dev()), ctf.to(dev()), out, B, n, kc - 1, 0)
+
+
+def _mask_margin(c, n, radius):
+    """min over pixels of |d^2 - r^2| in float64 for the image centre c (2,), and the mask, on the reference's grid
+    (train_particles.py:309-333: gx_j = -ceil(n/2) + j, gy_i = floor(n/2) - i)."""
+    gx = torch.arange(n, dtype=torch.float64) - (n + 1) // 2
+    gy = n // 2 - torch.arange(n, dtype=torch.float64)
+    d2 = (c[0].double() - gx)[None, :] ** 2 + (c[1].double() - gy)[:, None] ** 2
+    return float((d2 - radius * radius).abs().min()), (d2 < radius * radius).reshape(-1)
+
+
+@pytest.mark.parametrize('n', [32, 33, 50])
+@pytest.mark.parametrize('radius', [3.5, 7.25, 12.0, None])
+def test_loglik_masked(n, radius):
+    """tvae_loglik_masked_fwd / _bwd against oracle.particles_logp in float64 and its autograd gradient.  B = 4; for a finite
+    radius the last image's centre lies outside the frame by more than the radius (lp == 0, no gradient); radius None = 4 n
+    keeps every pixel and has to give exactly what tvae_loglik_fwd / _bwd (kind 1) give on the same data (same thread count,
+    same order, same tree).  A pixel ON the circle is ill-conditioned (the kernel forms d^2 in fp32: rounding of a few 1e-5
+    at d^2 ~ 150), so centres come from a seeded generator and are redrawn until no pixel has |d^2 - r^2| < 1e-3 in float64;
+    of 20 candidate draws at most 2 may be rejected (2 pi 1e-3 ~ 0.6 % is expected), so the filter cannot select the
+    cases away."""
+    B, spacing = 4, 0.5                                  # a power of two: dx / spacing is exact in fp32 and in fp64
+    r = 4.0 * n if radius is None else radius
+    gen = torch.Generator().manual_seed(7 * n + int(10 * r))
+    cand = torch.rand(20, 2, generator=gen) * 12 - 6
+    ok = [_mask_margin(c, n, r)[0] >= 1e-3 for c in cand]
+    assert ok.count(False) <= 2, ok
+    centres = cand[[i for i, o in enumerate(ok) if o][:B]].clone()
+    if radius is not None:
+        centres[B - 1] = torch.tensor([n / 2 + r + 3.25, 1.5])
+    masks = []
+    for c in centres:                                    # the margin holds for the inputs that are used
+        mg, mk = _mask_margin(c, n, r)
+        assert mg >= 1e-3
+        masks.append(mk)
+    mask = torch.stack(masks)
+    assert bool(mask.all()) == (radius is None) and (radius is None or not mask[B - 1].any())
+    dx = (centres * spacing).float()
+    yh, y, w = rnd(B, n * n, seed=1), rnd(B, n * n, seed=2), rnd(B, seed=3)
+    yh64 = yh.double().requires_grad_(True)
+    per = torch.stack([O.particles_logp(yh64[b:b + 1], y[b].double().view(1, 1, n, n), None, r, dx[b].double().view(1, 1, 2), spacing)
+                       for b in range(B)])
+    (per * w.double()).sum().backward()
+    d = [t.to(dev()) for t in (yh, y, dx, w)]
+    lp = torch.full((B,), float('nan'), device=dev())
+    call('tvae_loglik_masked_fwd', d[0], d[1], d[2], 1.0 / spacing, r, B, n, lp)
+    assert rel_err(lp, per.detach()) < TOL
+    gyh = torch.full((B, n * n), float('nan'), device=dev())
+    call('tvae_loglik_masked_bwd', d[0], d[1], d[2], 1.0 / spacing, r, B, n, d[3], gyh)
+    assert rel_err(gyh, yh64.grad) < TOL
+    assert torch.equal(gyh.cpu() != 0, mask)             # the zero pattern IS the reference's mask
+    if radius is not None:
+        assert float(lp[B - 1]) == 0.0 and not gyh[B - 1].any()
+    else:
+        lp1 = torch.full((B,), float('nan'), device=dev())
+        g1 = torch.full((B, n * n), float('nan'), device=dev())
+        call('tvae_loglik_fwd', d[0], d[1], lp1, B, n * n, 1)
+        call('tvae_loglik_bwd', d[0], d[1], d[3], g1, B, n * n, 1)
+        assert torch.equal(lp, lp1) and torch.equal(gyh, g1)
+
+
+@pytest.mark.parametrize('R,Ho,zd,scale,tie', [(4, 5, 1, 1.0, False), (8, 17, 2, 1.0, False), (8, 17, 2, 1.0, True),
+                                               (8, 66, 2, 30.0, False), (4, 9, 50, 1.0, False)])
+def test_get_latent(R, Ho, zd, scale, tie):
+    """tvae_get_latent against float64: argmax over (r, h, w) of logit + log p(r) (the sum itself in fp32, as the kernel and the
+    reference form it; everything behind it in float64), gather of (z_mu, exp(z_logstd)) and theta there, softmax-expected grid
+    position.  Fewer positions than the 1024 threads, 34 848 positions, z_dim 50, a padded row stride, logits x 30 (peaked
+    softmax); tie: the maximum planted twice, at j1 < j2 with (j2 mod 1024) < (j1 mod 1024) -- thread order and index order
+    disagree, the FIRST index has to win (include/tvae_hip.h)."""
+    B, P = 3, Ho * Ho
+    RP, nh = R * P, 3 + 2 * zd
+    ldh = B * RP + 37
+    heads = rnd(nh, ldh, seed=1)
+    heads[0] *= scale
+    heads[3 + zd:] *= 0.5
+    p_r = torch.log_softmax(rnd(R, seed=2), 0)
+    off, grid, tos = rnd(R, seed=3), rnd(P, 2, seed=4), 0.7
+    j1, j2 = 1000, 1029
+    if tie:
+        assert j2 < RP and j1 // P == j2 // P and j2 % 1024 < j1 % 1024
+        for b in range(B):
+            heads[0, b * RP + j1] = heads[0, b * RP + j2] = 50.0
+    zc = torch.full((B, 2 * zd), float('nan'), device=dev())
+    th = torch.full((B, 1), float('nan'), device=dev())
+    dxo = torch.full((B, 2), float('nan'), device=dev())
+    call('tvae_get_latent', heads.to(dev()), ldh, p_r.to(dev()), off.to(dev()), grid.to(dev()), B, R, P, zd, tos, zc, th, dxo)
+    zc_ref, th_ref, dx_ref = torch.empty(B, 2 * zd, dtype=torch.float64), torch.empty(B, 1, dtype=torch.float64), \
+        torch.empty(B, 2, dtype=torch.float64)
+    for b in range(B):
+        l32 = heads[0, b * RP:(b + 1) * RP] + p_r.repeat_interleave(P)
+        j = int((l32 == l32.max()).nonzero()[0])
+        if tie:
+            assert j == j1 and l32[j2] == l32[j1]
+        col = heads[:, b * RP + j].double()
+        zc_ref[b] = torch.cat([col[3:3 + zd], torch.exp(col[3 + zd:])])
+        th_ref[b] = col[1] + tos * off[j // P].double()
+        a = torch.softmax(l32.double(), 0).view(R, P).sum(0)
+        dx_ref[b] = a @ grid.double()
+    assert torch.equal(zc[:, :zd].cpu(), zc_ref[:, :zd].float())          # a gather: exact (and shows WHICH index won)
+    assert rel_err(zc, zc_ref) < TOL and rel_err(th, th_ref) < TOL and rel_err(dxo, dx_ref) < TOL
+
+
+@pytest.mark.parametrize('Mr,nparts', [(512, 3), (384, 3), (512, 2)])
+def test_dgrad_rowsum_total(Mr, nparts):
+    """tvae_dgrad_rowsum_total: tvae_linear_dgrad_x6 with rs_db = rs_dwo = NULL leaves only the per-tile partial sums; the total
+    as a call of its own has to give bit for bit the rs_db / rs_dwo of the fused launch (same kernel, same partials), and both
+    match float64 (the two-valued setups of test_linear_x6_implicit_gradient_operand / test_h3_decoder_entry_points)."""
+    from tvae._lib import query
+    N, K = 1024, 512
+    W, H = rnd(Mr, K, seed=1, scale=Mr ** -0.5), rnd(Mr, N, seed=2).clamp(-0.9, 0.9)
+    wo, gy = rnd(Mr, seed=3), rnd(N, seed=4)
+    aux = rnd(K, N, seed=5).clamp(-0.9, 0.9)
+    split = 'tvae_dense_split2h' if nparts == 2 else 'tvae_dense_split3'
+    w3 = torch.empty(query('tvae_dense_x6_bytes', K, Mr) // 4, device=dev())
+    cs = torch.empty(K, device=dev())
+    call(split, W.to(dev()), K, w3, w3.numel() * 4, K, Mr, 1, wo.to(dev()), cs)
+    gys = gy.sum().reshape(1).to(dev())
+    Hd, auxd, gyd, wod = H.to(dev()), aux.to(dev()), gy.to(dev()), wo.to(dev())
+    res = []
+    for fused in (True, False):
+        dX = torch.full((K, N), float('nan'), device=dev())
+        part = torch.full(((N // 128) * Mr * 2,), float('nan'), device=dev())
+        db, dwo = torch.full((Mr,), float('nan'), device=dev()), torch.full((Mr,), float('nan'), device=dev())
+        call('tvae_linear_dgrad_x6', w3, Hd, None, auxd, dX, Mr, N, K, N, N, 1, SLOPE, None, None, None, None, 0, None, gyd, cs,
+             None, None, 0, part, part.numel(), wod, gys, db if fused else None, dwo if fused else None, nparts)
+        if not fused:
+            assert torch.isnan(db).all() and torch.isnan(dwo).all()
+            call('tvae_dgrad_rowsum_total', part, N // 128, Mr, wod, gys, SLOPE, db, dwo, None, None)
+        res.append((dX, part, db, dwo))
+    for a, b in zip(*res):
+        assert torch.equal(a, b)
+    _, _, db, dwo = res[1]
+    assert rel_err(db, (wo.double()[:, None] * gy.double()[None, :] * dact_ref(H.double(), 1)).sum(1)) < TOL
+    assert rel_err(dwo, H.double() @ gy.double()) < TOL
+    with pytest.raises(Exception):
+        call('tvae_dgrad_rowsum_total', part, N // 128, Mr, wod, gys, SLOPE, db, None, None, None)
+    with pytest.raises(Exception):
+        call('tvae_dgrad_rowsum_total', part, 0, Mr, wod, gys, SLOPE, db, dwo, None, None)
+
+
+def test_every_entry_point_ran_under_guard(request):
+    """Keeps the coverage closed: when this whole file has run in the session, every entry point of the C ABI
+    (tvae._lib.SIGNATURES) has been called under guard bands by some test of it.  No exemptions."""
+    from tvae import _lib
+    mine = [it for it in request.session.items if it.fspath == request.node.fspath]
+    ran = {getattr(it, 'originalname', None) or it.name for it in mine}
+    defined = {k_ for k_, v_ in globals().items() if k_.startswith('test_') and callable(v_)}
+    tr = request.config.pluginmanager.get_plugin('terminalreporter')
+    cut = [it for it in (tr.stats.get('deselected', []) if tr else []) if getattr(it, 'fspath', None) == request.node.fspath]
+    if ran != defined or cut:
+        pytest.skip('only meaningful when the whole file runs (a -k / -m / node-id selection left part of it out)')
+    # ('stand_in' is the Python stand-in of the guard's CPU self-tests, when they ran in the same session)
+    assert guardband.GUARDED_NAMES - {'stand_in'} == set(_lib.SIGNATURES), \
+        (sorted(set(_lib.SIGNATURES) - guardband.GUARDED_NAMES), sorted(guardband.GUARDED_NAMES - set(_lib.SIGNATURES)))
