@@ -1,0 +1,189 @@
+"""Driver shared by clustering_{mnist,particles,galaxy,dsprites}.py: the second half of the reference workflow.
+
+Keeps the reference command lines (flags and defaults of the four clustering_*.py parsers, tests/golden/
+cli_flags_clustering.json), their default data paths, the whole-module torch.load of the saved encoder and the wording
+of results.txt.  The latents of the whole stack are extracted on the device (tvae.latent.extract_latents) and k-means
+runs on the HIP kernels (tvae.cluster.kmeans); agglomerative clustering stays on the host as in the reference.
+New optional flags: --seed, --n-init, --out-dir.  Besides results.txt the run writes latents.npy, rotations.npy,
+translations.npy and clusters.npy.  The plots of the reference (t-SNE, confusion matrix, histograms) are not built.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import cluster, latent, tables
+
+TITLES = {'mnist': 'Cluster the content latents of MNIST / MNIST-N / MNIST-U', 'particles': 'Cluster the content latents of a particle stack',
+          'galaxy': 'Cluster the content latents of the galaxy images', 'dsprites': 'Cluster the content latents of dSprites'}
+
+
+def build_parser(kind: str) -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(TITLES[kind])
+    if kind == 'mnist':
+        p.add_argument('--dataset', choices=['mnist', 'mnist-U', 'mnist-N'], default='mnist-U')
+    elif kind == 'galaxy':
+        p.add_argument('--train-path', default='data/galaxy_zoo/galaxy_zoo_train.npy')
+        p.add_argument('--test-path', default='data/galaxy_zoo/galaxy_zoo_test.npy')
+    elif kind == 'dsprites':
+        p.add_argument('--train-path', default='data/dsprites-dataset-master/imgs_train.npy')
+        p.add_argument('--test-path', default='data/dsprites-dataset-master/imgs_test.npy')
+        p.add_argument('--train-labels', default='./data/dsprites-dataset-master/latent_train.npy')
+        p.add_argument('--test-labels', default='./data/dsprites-dataset-master/latent_test.npy')
+    p.add_argument('-z', '--z-dim', type=int, default=2)
+    if kind == 'dsprites':
+        p.add_argument('--inp-channel', type=int, default=1)
+    if kind == 'particles':
+        p.add_argument('--test-path', help='stack to cluster (.npy, .mrc or .mrcs)')
+    p.add_argument('--path-to-encoder', help='whole-module checkpoint of the trained encoder (inference.sav)')
+    if kind == 'mnist':
+        p.add_argument('--path-to-mnist-test', default='./data/MNIST/processed/test.pt')
+    if kind == 'particles':
+        p.add_argument('--path-to-transformations',
+                       help='.npy with the ground-truth rotation in the first column and the x, y translations in the next two')
+    p.add_argument('--t-inf', default='attention', choices=['unimodal', 'attention'])
+    p.add_argument('--r-inf', default='attention+offsets', choices=['unimodal', 'attention', 'attention+offsets'])
+    p.add_argument('--clustering', default='k-means' if kind in ('mnist', 'dsprites') else 'agglomerative',
+                   choices=['agglomerative', 'k-means'])
+    p.add_argument('--n-clusters', default=10, type=int)
+    if kind == 'particles':
+        p.add_argument('--normalize', action='store_true')
+        p.add_argument('--crop', default=0, type=int)
+    p.add_argument('--in-channels', type=int, default=3 if kind == 'galaxy' else 1)
+    if kind == 'mnist':
+        p.add_argument('--image-dim', type=int, default=50)
+    p.add_argument('--activation', choices=['tanh', 'leakyrelu'], default='leakyrelu')
+    p.add_argument('--minibatch-size', type=int, default=100)
+    p.add_argument('-d', '--device', type=int, default=0)
+    # additions (do not change any reference flag)
+    p.add_argument('--seed', type=int, default=None, help='seed of the k-means++ initialisation (reference: unseeded)')
+    p.add_argument('--n-init', type=int, default=100, help='k-means restarts (the reference hard-codes 100)')
+    p.add_argument('--out-dir', default=None, help='where results.txt and the .npy files go (default: the directory '
+                                                   'of the encoder, as in the reference)')
+    return p
+
+
+def _load_stack(path):
+    if path.endswith('mrc') or path.endswith('mrcs'):
+        from src import mrc
+        return np.asarray(mrc.open_stack(path)[0], dtype=np.float32)
+    return np.load(path)
+
+
+def _load(kind, args):
+    """-> (images float tensor (N, Cin, n, m), labels or None, ground truth (r_gt, t_gt) | path | None)."""
+    if kind == 'mnist':
+        n = args.image_dim
+        if args.dataset == 'mnist':
+            try:
+                import torchvision
+            except ImportError as e:
+                raise SystemExit('--dataset mnist needs torchvision (not installed here); use mnist-U / mnist-N '
+                                 '(.npy) or --synthetic') from e
+            ds = torchvision.datasets.MNIST('data/', train=False, download=True)
+            arr = np.stack([np.asarray(ds[i][0]) for i in range(len(ds))]).astype(np.uint8)
+            truth = None                                   # no transformation on standard MNIST
+        else:
+            sub = {'mnist-U': 'mnist_U', 'mnist-N': 'mnist_N'}[args.dataset]
+            arr = np.load(f'data/{sub}/images_test.npy')
+            truth = f'data/{sub}/transforms_test.npy'
+        images = (torch.from_numpy(arr).float() / 255).view(-1, 1, n, n)
+        labels = torch.load(args.path_to_mnist_test, weights_only=False)[1]
+        return images, np.asarray(labels), truth
+    if kind == 'particles':
+        if not args.test_path:
+            raise SystemExit('please provide the test_path')
+        a = np.asarray(_load_stack(args.test_path), dtype=np.float32)
+        if args.crop > 0:
+            si, sj = (a.shape[-2] - args.crop) // 2, (a.shape[-1] - args.crop) // 2     # src/image.py: one offset per axis
+            a = a[..., si:si + args.crop, sj:sj + args.crop]
+            print('# cropped to:', args.crop, file=sys.stderr)
+        if args.normalize:                                  # per-image mean / std, as train_particles applies it
+            print('# normalizing particles', file=sys.stderr)
+            f = a.reshape(a.shape[0], -1)
+            a = (a - f.mean(1)[:, None, None]) / f.std(1)[:, None, None]
+        n, m = a.shape[1:]
+        images = torch.from_numpy(np.ascontiguousarray(a)).float().view(-1, 1, n, m)
+        return images, None, args.path_to_transformations
+    a = np.concatenate((np.load(args.train_path), np.load(args.test_path)))
+    images = torch.from_numpy(a).float()
+    if kind == 'galaxy':
+        n, m = images.shape[1:3]
+        return images.view(-1, args.in_channels, n, m), None, None
+    lab = np.concatenate((np.load(args.train_labels), np.load(args.test_labels)))
+    n, m = images.shape[1:]
+    # the shape column is the class the reference reads for the accuracy; columns 3 and 4: are rotation and translation
+    return images.view(-1, args.in_channels, n, m), lab[:, 1], (lab[:, 3:4], lab[:, 4:])
+
+
+def run(kind: str, argv=None):
+    args = build_parser(kind).parse_args(argv)
+    from src import models  # noqa: F401     (whole-module checkpoints unpickle as src.models.*)
+    if not args.path_to_encoder:
+        raise SystemExit('please provide --path-to-encoder')
+    if not torch.cuda.is_available() or args.device == -1:
+        raise SystemExit('the MI355X build has no CPU compute path (reference CPU mode -d -1 is not available)')
+    images, y_labels, truth = _load(kind, args)
+    torch.cuda.set_device(args.device)
+    device = torch.device('cuda', args.device)
+    print('# using device:', device, file=sys.stderr)
+    n, m = images.shape[-2:]
+    x_coord = torch.from_numpy(tables.image_coords(n, m)).to(device)
+    t_inf, r_inf = args.t_inf, args.r_inf
+    print('# clustering with z-dim:', args.z_dim, file=sys.stderr)
+    print('# translation inference is {}'.format(t_inf), file=sys.stderr)
+    print('# rotation inference is {}'.format(r_inf), file=sys.stderr)
+    path_to_encoder = args.path_to_encoder
+    encoder = torch.load(path_to_encoder, weights_only=False).to(device)
+    encoder.eval()
+    out_dir = args.out_dir if args.out_dir is not None else (os.path.dirname(path_to_encoder) or '.')
+    os.makedirs(out_dir, exist_ok=True)
+
+    mb = args.minibatch_size
+    z_values, rot_pred, tr_pred = latent.extract_latents(images, encoder, x_coord, t_inf, r_inf, mb, device)
+    if z_values.shape[1] != 2 * args.z_dim:
+        raise SystemExit(f'--z-dim {args.z_dim} does not match the encoder (z-dim {z_values.shape[1] // 2})')
+
+    rot_corr = tr_corr = None
+    if kind == 'mnist' and args.dataset != 'mnist':
+        # the digits of plain MNIST are slightly rotated and shifted themselves: the prediction on the untransformed test
+        # set is subtracted before the correlation (clustering_mnist.py:331-354)
+        print('# calculating the correlation for the rotation and translation ... ', file=sys.stderr)
+        plain = torch.load(args.path_to_mnist_test, weights_only=False)[0] / 255
+        pad = (n - plain[0].shape[1]) // 2
+        plain = torch.nn.functional.pad(plain, (pad, pad, pad, pad)).view(-1, 1, n, n)
+        _, rot0, tr0 = latent.extract_latents(plain, encoder, x_coord, t_inf, r_inf, mb, device)
+        rot_corr, tr_corr = cluster.measure_correlations(truth, (rot_pred - rot0).cpu(), (tr_pred - tr0).cpu())
+    elif kind == 'particles' and truth:
+        rot_corr, tr_corr = cluster.measure_correlations(truth, rot_pred.cpu(), tr_pred.cpu())
+    elif kind == 'dsprites':
+        rot_corr, tr_corr = cluster.measure_correlations(truth[0], truth[1], rot_pred.cpu(), tr_pred.cpu())
+
+    if args.clustering == 'agglomerative':
+        clusters = np.asarray(cluster.agglomerative(z_values.cpu().numpy(), args.n_clusters))
+    else:
+        res = cluster.kmeans(z_values, args.n_clusters, n_init=args.n_init, seed=args.seed)
+        clusters = res.labels.cpu().numpy()
+        print('# k-means: best of {} restarts is {} (inertia {}, {} iterations)'.format(
+            res.all_inertia.numel(), res.best, res.inertia, res.n_iter), file=sys.stderr)
+    acc = None
+    if y_labels is not None:
+        _, acc = cluster.cluster_acc(np.asarray(y_labels), clusters)
+    print('# the t-SNE, confusion-matrix and histogram figures of the reference are not built', file=sys.stderr)
+
+    np.save(os.path.join(out_dir, 'latents.npy'), z_values.cpu().numpy())
+    np.save(os.path.join(out_dir, 'rotations.npy'), rot_pred.cpu().numpy())
+    np.save(os.path.join(out_dir, 'translations.npy'), tr_pred.cpu().numpy())
+    np.save(os.path.join(out_dir, 'clusters.npy'), clusters)
+    with open(os.path.join(out_dir, 'results.txt'), 'w') as f:
+        f.write('using the encoder model from {}\n\n'.format(path_to_encoder))
+        if acc is not None:
+            f.write('The accuracy for clustering is {} \n'.format(acc))
+        if rot_corr is not None:
+            f.write('The circular correlation for the rotation is {}\n'.format(rot_corr))
+            f.write('The Pearson correlation for the x and y values in the translation is {}\n'.format(tr_corr))
+    return acc, rot_corr, tr_corr

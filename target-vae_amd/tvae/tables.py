@@ -118,9 +118,10 @@ def joint_log_prior(Ho: int, spacing: float, p_r: np.ndarray, dx_std: float = 0.
     return (joint - lse).astype(np.float32)
 
 
-def image_coords(n: int) -> np.ndarray:
-    """x_coord (n*n, 2) float32 (train_mnist.py:475-479)."""
-    xg = np.linspace(-1, 1, n)
+def image_coords(n: int, m: int | None = None) -> np.ndarray:
+    """x_coord (n*m, 2) float32 for images of n rows and m columns, m = n by default (train_mnist.py:475-479,
+    clustering_particles.py:240-243)."""
+    xg = np.linspace(-1, 1, n if m is None else m)
     yg = np.linspace(1, -1, n)
     x0, x1 = np.meshgrid(xg, yg)
     return np.stack([x0.ravel(), x1.ravel()], 1).astype(np.float32)
