@@ -1,4 +1,5 @@
-/* C ABI of libtvae_cluster.so: batched Lloyd k-means on the GPU (gfx950), the hot path of clustering_*.py.
+/* C ABI of libtvae_cluster.so: batched Lloyd k-means and Ward linkage on the GPU (gfx950), the hot paths of
+ * clustering_*.py.
  *
  * Same conventions as tvae_hip.h: raw device pointers and sizes, the stream as void*, `int` return = hipError_t.  The
  * entry points never allocate, free or synchronise and keep no process-wide state; the workspace is the caller's,
@@ -26,6 +27,7 @@ typedef void* tvae_stream_t;
 
 #define TVAE_KMEANS_MAX_RESTARTS 65535
 
+/* Still 1: the Ward entry points below were ADDED, no existing prototype or meaning changed. */
 int tvae_cluster_abi_version(void);          /* == 1 */
 
 /* floats of workspace for one assign / update pair: per restart G x (k*d sums, k counts, 1 changed count, 1 sum of
@@ -47,6 +49,49 @@ int tvae_kmeans_update(const float* ws, long ws_floats, const int* done, float* 
 /* the D^2 step of k-means++: D[r][n] = min(D[r][n], ||x_n - cnew[r]||^2), cnew[R][d] */
 int tvae_kmeans_mindist(const float* Xt, long ldx, const float* cnew, float* D, int N, int d, int R,
                         tvae_stream_t stream);
+
+/* ---- Ward agglomerative clustering without an N x N matrix ----------------------------------------------------------
+ *
+ * State of a round: M live clusters in slots 0 .. M-1, centroids FEATURE-major Ct[d][ld] (ld >= M; ld % 4 == 0 and a
+ * 16-byte aligned base take the vector loads, anything else a scalar instance with the same arithmetic), sizes cnt[M]
+ * as fp32 (exact up to 2^24), node ids id[M] and hmax[M] (fp64), the recorded height of the merge that made the slot (0
+ * for a leaf).
+ *
+ * Arithmetic: w(i,j) = (cnt_i * cnt_j) / (cnt_i + cnt_j) * sum_f (c_if - c_jf)^2, every operation rounded to fp32 on its
+ * own, the sum an FMA chain in ascending f.  It is bitwise symmetric, w(i,j) == w(j,i).  Ties go to the lowest j
+ * (strict < in ascending j, also where the partial minima of column ranges are combined; the split into ranges
+ * depends on (M, d) only).  Symmetry and the tie rule make the lexicographically least pair at the global minimum
+ * reciprocal, so a round over finite inputs merges at least one pair.  No float atomics; outputs are bitwise
+ * reproducible.
+ *
+ * Supported: 2 <= M <= 2^24, 1 <= d <= 256, M <= N <= 2^24; anything else returns hipErrorInvalidValue (1) and writes
+ * nothing. */
+
+/* floats of workspace of tvae_ward_nn: the partial (minimum, argmin) of tvae_ward_nn_splits(M, d) column ranges per
+ * row.  0 for unsupported arguments. */
+long tvae_ward_nn_ws_floats(int M, int d);
+int tvae_ward_nn_splits(int M, int d);
+/* ints of workspace of tvae_ward_merge (compacted position and pair rank per slot).  0 for unsupported arguments. */
+long tvae_ward_merge_ws_ints(int M, int d);
+
+/* nn[i] = argmin over j != i of w(i,j) and nd[i] = that minimum.  A row whose every w is +inf or NaN gets the lowest
+ * j != i and nd = +inf. */
+int tvae_ward_nn(const float* Ct, long ldc, const float* cnt, int* nn, float* nd, float* ws, long ws_floats, int M,
+                 int d, tvae_stream_t stream);
+
+/* One round of merges.  The centroids are kept in fp64, C[d][ld] (same layout); Ct_out receives their fp32 rounding,
+ * which is what tvae_ward_nn searches.  Every pair i < j with nn[i] == j and nn[j] == i is merged; its rank r counts
+ * such pairs by ascending i.  Record base + r: rec_ids[base + r] = (id_i then id_j) and rec_hs[base + r] = (height then
+ * cnt_i + cnt_j) with height = max(sqrt(2 w64(i j)) and hmax_i and hmax_j) where w64 is the formula above in fp64 on
+ * the fp64 centroids: heights never decrease from child to parent.  The merged cluster has the centroid
+ * (cnt_i c_i + cnt_j c_j) / (cnt_i + cnt_j) in fp64 and the temporary id N + base + r and takes the place of slot i.
+ * Survivors go to the *_out arrays compactly in ascending old slot order (ld_out >= M) and their number to *m_out.
+ * cap = records that rec_ids / rec_hs hold; base + M / 2 <= cap is required.  The *_out arrays must not overlap the
+ * inputs. */
+int tvae_ward_merge(const double* C_in, long ld_in, const float* cnt_in, const int* id_in, const double* hmax_in,
+                    const int* nn, double* C_out, float* Ct_out, long ld_out, float* cnt_out, int* id_out,
+                    double* hmax_out, int* rec_ids, double* rec_hs, int* m_out, int* ws, long ws_ints, int M, int d,
+                    int N, int base, int cap, tvae_stream_t stream);
 
 #ifdef __cplusplus
 }

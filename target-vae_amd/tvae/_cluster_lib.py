@@ -1,4 +1,5 @@
-"""ctypes binding of libtvae_cluster.so (C ABI declared in include/tvae_cluster.h): the batched k-means kernels.
+"""ctypes binding of libtvae_cluster.so (C ABI declared in include/tvae_cluster.h): the batched k-means and
+Ward linkage kernels.
 
 A library of its own beside libtvae_hip.so -- the ABI of the training kernels (tvae._lib.SIGNATURES, version 7) is not
 touched by the clustering half.  Same rules: no CPU fallback, tensors are checked by tvae._lib._ptr (GPU, contiguous,
@@ -24,11 +25,18 @@ SIGNATURES = {
     'tvae_kmeans_assign': 'plppppppliiii',    # Xt, ldx, C, done, labels, mind2, changed, ws, ws_floats, N, d, k, R
     'tvae_kmeans_update': 'plppppiiii',       # ws, ws_floats, done, C, inertia, shift, N, d, k, R
     'tvae_kmeans_mindist': 'plppiii',         # Xt, ldx, cnew, D, N, d, R
+    'tvae_ward_nn': 'plpppplii',              # Ct, ldc, cnt, nn, nd, ws, ws_floats, M, d
+    # C_in (fp64), ld_in, cnt_in, id_in, hmax_in (fp64), nn, C_out (fp64), Ct_out, ld_out, cnt_out, id_out,
+    # hmax_out (fp64), rec_ids, rec_hs (fp64), m_out, ws, ws_ints, M, d, N, base, cap
+    'tvae_ward_merge': 'plpppp' 'pplppp' 'pppp' 'l' 'iiiii',
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
     'tvae_kmeans_ws_floats': ('iiii', 'l'),
     'tvae_kmeans_groups': ('iii', 'i'),
+    'tvae_ward_nn_ws_floats': ('ii', 'l'),
+    'tvae_ward_nn_splits': ('ii', 'i'),
+    'tvae_ward_merge_ws_ints': ('ii', 'l'),
 }
 
 _cl = None

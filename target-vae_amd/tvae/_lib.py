@@ -285,6 +285,8 @@ def query(name, *args) -> int:
 # g_elbo / g_kld of tvae_elbo_reduce_bwd.  Every other pointer of those entry points is float* (a float64 `kl`
 # passed where float* is expected would be reinterpreted silently).
 _F64_OK = {('tvae_elbo_reduce', 3), ('tvae_elbo_reduce', 5), ('tvae_elbo_reduce_bwd', 0), ('tvae_elbo_reduce_bwd', 2)}
+# libtvae_cluster.so (tvae._cluster_lib): the fp64 centroids, heights and records of tvae_ward_merge
+_F64_OK |= {('tvae_ward_merge', p) for p in (0, 4, 6, 11, 13)}
 
 
 def _ptr(t, name, pos):

@@ -6,6 +6,10 @@ assign launch labels every point of every restart and leaves ordered per-cluster
 them into the new centroids, the inertia and the centre shift.  No float atomics: a run is bitwise reproducible and a
 restart's trajectory does not depend on which other restarts share the launch.  There is no CPU fallback.
 
+Ward agglomerative clustering (the default of the particles and galaxy scripts) runs on the same library: ward_linkage
+merges all reciprocal nearest neighbours per round from sizes and centroids alone, ward_cut numbers the flat clusters
+as sklearn does.  The reference's sklearn path stays for host arrays (agglomerative).
+
 The metrics (cluster_acc, circcorrcoef, measure_correlations) are host code like the reference's.
 """
 from __future__ import annotations
@@ -19,7 +23,9 @@ from . import _cluster_lib as CL
 from ._lib import TvaeHipError
 
 KMeansResult = namedtuple('KMeansResult', 'labels centers inertia n_iter all_inertia best')
+WardResult = namedtuple('WardResult', 'Z n_rounds')
 MAX_RESTARTS = 65535                 # TVAE_KMEANS_MAX_RESTARTS of include/tvae_cluster.h
+WARD_MAX_POINTS = 1 << 24            # cluster sizes are fp32 on the device, exact up to here
 CHECK_EVERY = 8                      # iterations between two host reads of the per-restart `done` flags
 
 
@@ -137,15 +143,144 @@ def kmeans(X, n_clusters, n_init=100, max_iter=300, tol=1e-4, seed=None, init=No
                         all_inertia, best)
 
 
+def _check_ward_points(X):
+    if not (torch.is_tensor(X) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 2):
+        raise TvaeHipError('ward_linkage: X must be a CUDA fp32 [N][d] tensor (no CPU fallback)')
+    N, d = X.shape
+    if not (2 <= N <= WARD_MAX_POINTS and 1 <= d <= 256):
+        raise TvaeHipError(f'ward_linkage: N={N}, d={d} outside the supported range (2 <= N <= 2^24, 1 <= d <= 256)')
+    return N, d
+
+
+def _check_finite(X):
+    if not bool(torch.isfinite(X).all()):
+        raise TvaeHipError('ward_linkage: X holds NaN or Inf')
+
+
+def ward_linkage(X):
+    """Ward linkage of the rows of X (CUDA fp32 [N][d]) on the GPU, without the N x N distance matrix.
+
+    The Ward distance of two clusters depends on their sizes and centroids alone, w(A,B) = |A||B| / (|A|+|B|) *
+    ||c_A - c_B||^2 (scipy's height is sqrt(2 w)), and Ward is a reducible linkage: two clusters that are each other's
+    nearest neighbour belong to the final dendrogram.  A round is therefore tvae_ward_nn (all-pairs nearest neighbour
+    of the M live centroids, O(M^2 d) work, O(M d) memory) and tvae_ward_merge (every reciprocal pair merged, the
+    survivors compacted into the other half of a ping-pong buffer), then one D2H copy of the new M.  The kernels make w
+    bitwise symmetric and send ties to the lowest index, so the lexicographically least pair at the global minimum is
+    always reciprocal: every round merges something, and a round that does not raises instead of looping.
+
+    X is centred first (per-feature mean in fp64 on the device; Ward is translation invariant) and must be finite: a
+    NaN would break the progress guarantee, so it is refused before any launch.  The centroids are kept in fp64 beside
+    the fp32 copy that the search reads, and the recorded heights are fp64: merges whose heights differ by less than an
+    fp32 ulp (a few per thousand points) would otherwise sort, and so be numbered, differently from an fp64 linkage.
+
+    Returns WardResult(Z, n_rounds): Z is the fp64 numpy [N-1][4] array of scipy.cluster.hierarchy.linkage (children
+    min / max, height, size; rows sorted by height, ties in creation order; node N + r made by row r)."""
+    N, d = _check_ward_points(X)
+    _check_finite(X)
+    dev = X.device
+    X64 = X.double()
+    ldc = (N + 3) // 4 * 4
+    C64 = torch.zeros(2, d, ldc, dtype=torch.float64, device=dev)
+    C64[0, :, :N] = (X64 - X64.mean(dim=0, keepdim=True)).t()
+    Ct = torch.zeros(2, d, ldc, dtype=torch.float32, device=dev)
+    Ct[0] = C64[0]
+    cnt = torch.ones(2, ldc, dtype=torch.float32, device=dev)
+    ids = torch.zeros(2, N, dtype=torch.int32, device=dev)
+    ids[0] = torch.arange(N, dtype=torch.int32, device=dev)
+    hmax = torch.zeros(2, N, dtype=torch.float64, device=dev)
+    nn = torch.zeros(N, dtype=torch.int32, device=dev)
+    nd = torch.zeros(N, dtype=torch.float32, device=dev)
+    rec_ids = torch.zeros(N - 1, 2, dtype=torch.int32, device=dev)
+    rec_hs = torch.zeros(N - 1, 2, dtype=torch.float64, device=dev)
+    m_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+    wsm_ints = CL.query('tvae_ward_merge_ws_ints', N, d)
+    wsm = torch.empty(wsm_ints, dtype=torch.int32, device=dev)
+    ws = None
+
+    M, base, cur, rounds = N, 0, 0, 0
+    while M > 1:
+        need = CL.query('tvae_ward_nn_ws_floats', M, d)               # not monotone in M: the column split changes
+        if need <= 0:
+            raise TvaeHipError(f'ward_linkage: M={M}, d={d} is not supported by libtvae_cluster.so')
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.float32, device=dev)
+        nxt = 1 - cur
+        CL.call('tvae_ward_nn', Ct[cur], ldc, cnt[cur], nn, nd, ws, ws.numel(), M, d)
+        CL.call('tvae_ward_merge', C64[cur], ldc, cnt[cur], ids[cur], hmax[cur], nn, C64[nxt], Ct[nxt], ldc, cnt[nxt],
+                ids[nxt], hmax[nxt], rec_ids, rec_hs, m_dev, wsm, wsm_ints, M, d, N, base, N - 1)
+        m_new = int(m_dev.item())
+        if not 1 <= m_new < M:
+            raise TvaeHipError(f'ward_linkage: round {rounds} merged nothing (M = {M} -> {m_new}); non-finite distances?')
+        base += M - m_new
+        M, cur, rounds = m_new, nxt, rounds + 1
+    assert base == N - 1
+
+    # creation order -> scipy's order: stable sort by height, temporary ids N + creation index -> N + rank
+    order = torch.sort(rec_hs[:, 0], stable=True).indices
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(N - 1, device=dev)
+    ch = rec_ids.to(torch.int64)
+    ch = torch.where(ch >= N, N + rank[(ch - N).clamp_(min=0)], ch)[order]
+    Z = torch.empty(N - 1, 4, dtype=torch.float64, device=dev)
+    Z[:, 0] = ch.min(dim=1).values
+    Z[:, 1] = ch.max(dim=1).values
+    Z[:, 2:] = rec_hs[order]
+    return WardResult(Z.cpu().numpy(), rounds)
+
+
+def ward_cut(Z, n_clusters):
+    """Flat clusters of a linkage matrix Z (scipy convention), numbered as sklearn's AgglomerativeClustering numbers
+    them -> int64 labels [N].
+
+    A min-heap of negated node ids starts with the root; n_clusters - 1 times its top node (the highest id = the
+    last merge still whole) is split: the first child is pushed, the second one pushed while the top is popped.  Label
+    i goes to the leaves under the i-th entry of the heap in its ARRAY order.  The labels reach the leaves by pointer
+    jumping over the parent array (log2(depth) array operations, no Python loop over N)."""
+    import heapq
+    Z = np.asarray(Z)
+    N = Z.shape[0] + 1
+    k = int(n_clusters)
+    if not (Z.ndim == 2 and Z.shape[1] == 4 and N >= 2):
+        raise ValueError('ward_cut: Z must be an [N-1][4] linkage matrix')
+    if not 1 <= k <= N:
+        raise ValueError(f'ward_cut: n_clusters = {k} must be in [1, {N}]')
+    children = Z[:, :2].astype(np.int64)
+    heap = [-(2 * N - 2)]
+    for _ in range(k - 1):
+        a, b = children[-heap[0] - N]
+        heapq.heappush(heap, -int(a))
+        heapq.heappushpop(heap, -int(b))
+    cut = -np.asarray(heap, dtype=np.int64)
+    anc = np.arange(2 * N - 1, dtype=np.int64)                        # the root and the cut nodes point at themselves
+    parent = np.arange(N, 2 * N - 1, dtype=np.int64)
+    anc[children[:, 0]] = parent
+    anc[children[:, 1]] = parent
+    anc[cut] = cut
+    while True:
+        nxt = anc[anc]
+        if np.array_equal(nxt, anc):
+            break
+        anc = nxt
+    label_of = np.full(2 * N - 1, -1, dtype=np.int64)
+    label_of[cut] = np.arange(k)
+    labels = label_of[anc[:N]]
+    assert (labels >= 0).all()
+    return labels
+
+
 def agglomerative(z_values, n_clusters):
-    """The reference's default for particles and galaxy: Ward linkage on the host (sklearn), as in clustering_*.py."""
+    """Ward agglomerative clustering, the reference's default for particles and galaxy.  A CUDA tensor is clustered on
+    the GPU (ward_linkage + ward_cut, the numbering of sklearn's fit_predict); a numpy array or a CPU tensor takes the
+    reference's own host path, sklearn's AgglomerativeClustering, which builds the N (N - 1) / 2 distance matrix."""
+    if torch.is_tensor(z_values) and z_values.is_cuda:
+        return ward_cut(ward_linkage(z_values.float().contiguous()).Z, n_clusters)
     try:
         from sklearn.cluster import AgglomerativeClustering
     except ImportError as e:
-        raise SystemExit('--clustering agglomerative needs scikit-learn (not installed here); use --clustering '
-                         'k-means, which runs on the GPU') from e
+        raise SystemExit('--clustering agglomerative on the host needs scikit-learn (not installed here); pass the '
+                         'latents as a CUDA tensor, or use --clustering k-means') from e
     ac = AgglomerativeClustering(n_clusters=n_clusters, linkage='ward', compute_full_tree=True)
-    return ac.fit_predict(np.asarray(z_values))
+    return ac.fit_predict(_np(z_values))
 
 
 def cluster_acc(y_true, y_pred):

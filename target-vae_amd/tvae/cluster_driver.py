@@ -3,7 +3,8 @@
 Keeps the reference command lines (flags and defaults of the four clustering_*.py parsers, tests/golden/
 cli_flags_clustering.json), their default data paths, the whole-module torch.load of the saved encoder and the wording
 of results.txt.  The latents of the whole stack are extracted on the device (tvae.latent.extract_latents) and k-means
-runs on the HIP kernels (tvae.cluster.kmeans); agglomerative clustering stays on the host as in the reference.
+runs on the HIP kernels (tvae.cluster.kmeans), and so does Ward agglomerative clustering (tvae.cluster.ward_linkage;
+TVAE_WARD=host selects the reference's sklearn path).
 New optional flags: --seed, --n-init, --out-dir.  Besides results.txt the run writes latents.npy, rotations.npy,
 translations.npy and clusters.npy.  The plots of the reference (t-SNE, confusion matrix, histograms) are not built.
 """
@@ -164,7 +165,10 @@ def run(kind: str, argv=None):
         rot_corr, tr_corr = cluster.measure_correlations(truth[0], truth[1], rot_pred.cpu(), tr_pred.cpu())
 
     if args.clustering == 'agglomerative':
-        clusters = np.asarray(cluster.agglomerative(z_values.cpu().numpy(), args.n_clusters))
+        # TVAE_WARD=host: the reference's sklearn path on a host copy (needs the N x N matrix); default: the GPU kernels
+        on_host = os.environ.get('TVAE_WARD', '') == 'host'
+        print('# ward linkage on the host (sklearn)' if on_host else '# ward linkage on the GPU', file=sys.stderr)
+        clusters = np.asarray(cluster.agglomerative(z_values.cpu().numpy() if on_host else z_values, args.n_clusters))
     else:
         res = cluster.kmeans(z_values, args.n_clusters, n_init=args.n_init, seed=args.seed)
         clusters = res.labels.cpu().numpy()
