@@ -41,7 +41,7 @@ with torch.no_grad():
     outs = {}
     for mode in ('f32', 'x6'):
         with _lib.arithmetic(mode):
-            outs[mode] = ops.conv1_forward(y, enc.conv1.weight, enc.conv1.bias, 128, R, 64, 32, 1)
+            outs[mode], _ = ops.conv1_forward(y, enc.conv1.weight, enc.conv1.bias, 128, R, 64, 32, 1)
     d = (outs['x6'] - outs['f32']).double()
     print('conv1 output: relative Frobenius difference x6(DFT) vs f32 %.3e, max abs %.3e (max |out| %.3e)' % (
         float(d.norm() / outs['f32'].double().norm()), float(d.abs().max()), float(outs['f32'].abs().max())))

@@ -348,9 +348,10 @@ def _use_dft(B, Cin, n, k, pad, C, R) -> bool:
     return CONV_DFT and split_pipe() and bool(query('tvae_conv1_dft_supported', B, Cin, n, k, pad, C, R))
 
 
-def conv1_forward(y, weight, bias, C, R, k, pad, act, keep=None, bank=None):
-    """Rotated bank + lifting convolution.  `keep` (a dict) receives what the weight gradient can reuse.  `bank`: a ready
-    [C*R][Cin*k*k] bank (the plain convolution of --groupconv 0 is the R = 1 case with the weight itself as the bank)."""
+def conv1_forward(y, weight, bias, C, R, k, pad, act, bank=None):
+    """Rotated bank + lifting convolution: returns (out, at), `at` being what the frequency-domain path keeps for the weight
+    gradient (A^T, then max |out| per channel: conv1_out_max) and None on the other paths.  `bank`: a ready [C*R][Cin*k*k]
+    bank (the plain convolution of --groupconv 0 is the R = 1 case with the weight itself as the bank)."""
     B, Cin, n, _ = y.shape
     Ho = n + 2 * pad - k + 1
     if bank is None:
@@ -367,26 +368,29 @@ def conv1_forward(y, weight, bias, C, R, k, pad, act, keep=None, bank=None):
         with _timed('tvae_conv1_fwd', parts()):
             call('tvae_conv1_fwd_dft', y, bank, bias, out, at, ws, ws.numel(), B, Cin, n, k, pad, C, R, act,
                  LRELU_SLOPE, parts())
-        if keep is not None:
-            keep['at'] = at
-            keep['out_max'] = at[-C:]      # max |out| per channel, left by the output transform (h3 scales of the encoder tail)
-        return out
+        return out, at
     if _use_x6(Cin, n, k, pad):
         a3 = _scratch(y.device, 'x6_bank', query('tvae_conv1_x6_bank_bytes', C, R, Cin, k) // 4)
         call('tvae_bank_split3', bank, a3, a3.numel() * 4, C, R, Cin, k)
         _note('conv1.x6')
         with _timed('tvae_conv1_fwd', 3):
             call('tvae_conv1_fwd_x6', y, a3, bias, out, B, Cin, n, k, pad, C, R, act, LRELU_SLOPE)
-        return out
+        return out, None
     _note('conv1.f32')
     with _timed('tvae_conv1_fwd'):
         call('tvae_conv1_fwd', y, bank, bias, out, B, Cin, n, k, pad, C, R, act, LRELU_SLOPE)
-    return out
+    return out, None
+
+
+def conv1_out_max(at: torch.Tensor, C: int) -> torch.Tensor:
+    """max |out| per channel, left behind A^T by the output transform of the frequency-domain convolution (a view of `at`):
+    the h3 scales of the encoder tail."""
+    return at[-C:]
 
 
 def conv1_wgrad(y, dpre, C, R, k, pad, at=None, dbias=None):
-    """Weight gradient of the lifting convolution.  With the frequency-domain path (`at` from the forward call) the bias
-    gradient is a by-product: pass `dbias` (C floats) to receive it; returns (dbank, bias_done)."""
+    """Weight gradient of the lifting convolution: returns dbank.  With the frequency-domain path (`at` from the forward
+    call) the bias gradient is a by-product: pass `dbias` (C floats) to receive it."""
     B, Cin, n, _ = y.shape
     dbank = torch.empty(C * R, Cin * k * k, dtype=torch.float32, device=y.device)
     if at is not None:
@@ -404,6 +408,13 @@ def conv1_wgrad(y, dpre, C, R, k, pad, at=None, dbias=None):
     with _timed('tvae_conv1_wgrad'):
         call('tvae_conv1_wgrad', y, dpre, dbank, ws, ws.numel(), B, Cin, n, k, pad, C, R)
     return dbank
+
+
+def conv1_backward(y, dA1, C, R, k, pad, at):
+    """(dbank, db1) of the lifting convolution from the gradient dA1 [C][N] of its pre-activation.  The bias gradient is a
+    by-product of the frequency-domain weight gradient (`at` kept by the forward), a row sum of dA1 otherwise."""
+    db1 = torch.empty(C, dtype=torch.float32, device=y.device) if at is not None else _rowsum(dA1, C, dA1.shape[1])
+    return conv1_wgrad(y, dA1, C, R, k, pad, at, db1 if at is not None else None), db1
 
 
 class BankFn(torch.autograd.Function):
@@ -430,11 +441,9 @@ class GroupConvFn(torch.autograd.Function):
         y = y.contiguous().view(y.shape[0], Cin, y.shape[-2], y.shape[-1])
         B, n = y.shape[0], y.shape[-1]
         Ho = n + 2 * pad - k + 1
-        keep = {}
-        out = conv1_forward(y, weight, bias, C, R, k, pad, ACT_NONE, keep)
+        out, ctx.at = conv1_forward(y, weight, bias, C, R, k, pad, ACT_NONE)
         ctx.arith = get_gemm_mode()
         ctx.save_for_backward(y)
-        ctx.at = keep.get('at')
         ctx.cfg = (C, Cin, k, R, pad, B, Ho, bias is not None)
         return out.view(C, B, R, Ho, Ho).permute(1, 0, 2, 3, 4)
 
@@ -446,7 +455,7 @@ class GroupConvFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             raise NotImplementedError('GroupConv input gradient is not part of the hot path (input is data)')
         dpre = g.permute(1, 0, 2, 3, 4).contiguous().view(C, B * R * Ho * Ho)
-        db = None
+        db = None                                        # (optional here, and summed after the bank: not conv1_backward)
         if has_bias and ctx.at is not None:
             db = torch.empty(C, dtype=torch.float32, device=y.device)
         dbank = conv1_wgrad(y, dpre, C, R, k, pad, ctx.at, db)
@@ -466,21 +475,67 @@ def _enc_tail_perm(device) -> torch.Tensor:
     return _dev_table(('enc_tail_perm',), device, build)[0]
 
 
+ENC_TAIL_FUSED_MAX_ROWS = 7      # head rows of tvae_enc_tail_*_x6 (enc_tail_x6_kernels.hpp)
+ENC_TAIL_WIDE_MAX_ROWS = 128     # ... of tvae_enc_tail_*_wide, which take over at SKINNY_MAX (enc_tail_wide_kernels.hpp)
 ENC_TAIL_MAX_COLS = 1 << 25      # the fused kernels index 32 rows with 32-bit byte offsets (abi_enc_tail_x6.hip: ET_MAX_LD)
 
 
-def _enc_tail_fused(C: int, C2: int, nh: int, N: int = 0) -> bool:
-    """Fused encoder tail (enc_tail_x6_kernels.hpp): the reference's default 128 channels, <= 7 head rows, split pipe,
-    fewer than 2^25 columns (beyond that the unfused path with 64-bit indexing takes over)."""
-    return FUSE_ENC_TAIL and split_pipe() and C == 128 and C2 == 128 and nh <= 7 and N < ENC_TAIL_MAX_COLS
+class EncoderRoute(NamedTuple):
+    """Every structural decision of EncoderFn's tail (conv2 + the stacked head projection), taken once by encoder_route()
+    in the forward and kept on ctx: the backward routes by it, so the two passes cannot disagree about what was stored."""
+    tail: str            # 'fused': conv2 + heads in one pass over A1 and one over H (tvae_enc_tail_*_x6); 'wide': as two chained
+    #                      GEMMs per 32-column chunk, H handed over in registers (tvae_enc_tail_*_wide); 'plain': separate launches
+    parts: int           # `parts` of the tail's forward launch (0: 'plain')
+    h3: bool             # the tail launches take max |A1| per channel (left by the frequency-domain conv1) as their h3 scales
+    bits: bool           # sign words of H and A1 are stored: the data gradient is the tail kernel's, from them alone
+    wgrad: str           # 'x6': dW2 from A1, dheads and the sign words (tvae_enc_tail_wgrad_x6; dH is never written); 'wide': dWh
+    #                      and dW2 as two tvae_enc_tail_wgrad_wide launches over stored operands; 'plain': the generic GEMMs
+    infer: bool          # inference-mode forward: head rows only, nothing is kept for a backward
 
 
-def _enc_tail_wide(C: int, C2: int, nh: int, N: int, have_a1max: bool) -> bool:
-    """Round 6: the encoder tail with 8 .. 128 head rows (z_dim > 2: the galaxy configuration's z_dim = 50 gives 103) as two
-    chained split-pipe GEMMs per direction (enc_tail_wide_kernels.hpp) instead of separate fp32-MFMA GEMMs.  h3 or bf16
-    arithmetic (both weights stay in LDS; the exact three-part split does not fit), the reference's 128 channels."""
-    return (FUSE_ENC_TAIL and split_pipe() and parts() in (1, 2) and C == 128 and C2 == 128 and SKINNY_MAX <= nh <= 128 and
-            N < ENC_TAIL_MAX_COLS and (parts() == 1 or have_a1max))
+def encoder_route(C: int, C2: int, nh: int, N: int, act: int, out_max: bool, infer: bool) -> EncoderRoute:
+    """The route of EncoderFn's tail for C -> C2 channels, nh head rows and N columns in the current arithmetic; out_max:
+    conv1 took the frequency-domain path and left max |A1| per channel (conv1_out_max).  Pure: no tensor, no launch.
+    The fused kernels are built for the reference's 128 channels on the split pipe and fewer than 2^25 columns (beyond that
+    the plain path with 64-bit indexing takes over); the wide ones keep both weights in LDS, which the exact three-part
+    split does not fit: h3 (needs the bounds of A1) or bf16 arithmetic."""
+    p = parts()
+    tail = 'plain'
+    if FUSE_ENC_TAIL and split_pipe() and C == 128 and C2 == 128 and N < ENC_TAIL_MAX_COLS:
+        if nh <= ENC_TAIL_FUSED_MAX_ROWS:
+            tail = 'fused'
+        elif SKINNY_MAX <= nh <= ENC_TAIL_WIDE_MAX_ROWS and (p == 1 or (p == 2 and out_max)):
+            tail = 'wide'
+    h3 = tail != 'plain' and p == 2 and out_max
+    bits = tail != 'plain' and act == ACT_LRELU and not infer
+    # the fused weight gradients reduce over 32-column chunks; the wide one exists in h3 only (bounds of both operands)
+    wgrad = 'plain' if not (bits and N % 32 == 0) else 'x6' if tail == 'fused' else 'wide' if h3 else 'plain'
+    return EncoderRoute(tail=tail, parts={'plain': 0, 'wide': p, 'fused': 2 if h3 else _p3()}[tail], h3=h3, bits=bits,
+                        wgrad=wgrad, infer=infer)
+
+
+def _heads_forward(Wh, bh, H, heads, nh, C2, N):
+    """heads = Wh H + bh, the stacked head projection on its own: streaming kernel or GEMM (SKINNY_MAX)."""
+    if nh <= SKINNY_MAX:
+        call('tvae_heads_fwd', Wh.contiguous(), H, N, bh, heads, N, nh, C2, N)
+    else:
+        call('tvae_linear_fwd', Wh.contiguous(), H, bh, None, 1, None, heads, nh, N, C2, N, N, ACT_NONE, LRELU_SLOPE)
+
+
+def _heads_backward(Wh, dheads, H, dH, nh, C2, N, act):
+    """Backward of the head projection through the activation that produced H: returns (dWh, db2) and fills
+    dH = act'(H) . Wh^T dheads.  dH = None (nh <= SKINNY_MAX only): the sums alone."""
+    if nh <= SKINNY_MAX:
+        # one pass over H: masked dgrad + dWh + the row sums of dH (= db2)
+        npan = (N + 511) // 512
+        part = workspace(H.device, npan * C2 * (nh + 1) + 4 + 64 * C2 * (nh + 1))      # + room for the two-stage total
+        tot = torch.empty(nh + 1, C2, dtype=torch.float32, device=H.device)
+        call('tvae_heads_bwd', Wh.contiguous(), dheads, N, H, N, dH, N, nh, C2, N, act, LRELU_SLOPE, part,
+             part.numel(), tot)
+        return tot[:nh], tot[nh]
+    dWh = _wgrad(dheads, H, nh, N, C2)
+    call('tvae_linear_dgrad', Wh.contiguous(), dheads, None, H, dH, nh, N, C2, N, N, act, LRELU_SLOPE)
+    return dWh, _rowsum(dH, C2, N)
 
 
 class EncoderFn(torch.autograd.Function):
@@ -503,61 +558,36 @@ class EncoderFn(torch.autograd.Function):
         C2, nh = W2.shape[0], Wh.shape[0]
         _expect(tuple(W2.shape) == (C2, C) and tuple(Wh.shape) == (nh, C2) and b1.numel() == C and
                 b2.numel() == C2 and bh.numel() == nh, 'encoder parameter shapes are inconsistent')
-        keep = {}
-        infer = _INFER
-        A1 = conv1_forward(y, w1, b1, C, R, k, pad, act, keep)
-        ctx.at = None if infer else keep.get('at')
-        fused = _enc_tail_fused(C, C2, nh, N)
-        wide = not fused and _enc_tail_wide(C, C2, nh, N, keep.get('out_max') is not None)
-        # inference: the fused tail writes the head rows only -- H is neither allocated nor stored (include/tvae_hip.h, ABI 6)
-        H = None if (infer and (fused or wide)) else torch.empty(C2, N, dtype=torch.float32, device=y.device)
+        A1, at = conv1_forward(y, w1, b1, C, R, k, pad, act)
+        rt = encoder_route(C, C2, nh, N, act, at is not None, _INFER)
+        # inference: the fused tails write the head rows only -- H is neither allocated nor stored (include/tvae_hip.h, ABI 6)
+        H = None if (rt.infer and rt.tail != 'plain') else torch.empty(C2, N, dtype=torch.float32, device=y.device)
         heads = torch.empty(nh, N, dtype=torch.float32, device=y.device)
-        bits = None
-        a1max = None
-        if infer:
+        a1max = conv1_out_max(at, C) if rt.h3 else None
+        # sign words of H and A1: all the fused data gradient reads of them
+        bits = torch.empty(2, N, 4, dtype=torch.int32, device=y.device) if rt.bits else (None, None)
+        if rt.infer:
             _note('enc.inference')
-        if wide:
-            # conv2 + the stacked head projection as two chained GEMMs per 32-column chunk (H handed over in registers)
-            p_f = parts()
-            a1max = keep.get('out_max') if p_f == 2 else None
-            w3 = _split_weight(W2, C2, C, False, 'enc_w2', nparts=p_f)
-            whp = _split_weight(Wh[:, _enc_tail_perm(y.device)], nh, C2, False, 'enc_whp', nparts=p_f)
-            _note('enc.tail_fwd_wide')
-            if act == ACT_LRELU and not infer:
-                bits = torch.empty(2, N, 4, dtype=torch.int32, device=y.device)
-            with _timed('tvae_enc_tail_fwd_wide', p_f):
-                call('tvae_enc_tail_fwd_wide', w3, whp, A1, N, b2, bh.contiguous(), nh, H, N, heads, N,
-                     bits[0] if bits is not None else None, bits[1] if bits is not None else None, C, N, act, LRELU_SLOPE,
-                     p_f, a1max)
-        elif fused:
-            # conv2 + the stacked head projection in one pass over A1 and one over H, on the split pipe
-            # h3 instance: needs max |A1| from A1's producer -- the output transform of the frequency-domain convolution leaves
-            # it in the last word behind A^T (keep['at'])
-            a1max = keep.get('out_max') if parts() == 2 else None
-            p_f = 2 if a1max is not None else _p3()
-            w3 = _split_weight(W2, C2, C, False, 'enc_w2', nparts=p_f)
-            _note('enc.tail_fwd_x6')
-            if act == ACT_LRELU and not infer:           # sign words of H and A1: all the fused data gradient reads of them
-                bits = torch.empty(2, N, 4, dtype=torch.int32, device=y.device)
-            with _timed('tvae_enc_tail_fwd_x6', p_f):
-                call('tvae_enc_tail_fwd_x6', w3, A1, N, b2, Wh.contiguous(), bh.contiguous(), nh, H, N, heads, N,
-                     bits[0] if bits is not None else None, bits[1] if bits is not None else None, C, N, act,
-                     LRELU_SLOPE, p_f, a1max)
-        else:
+        if rt.tail == 'plain':
             call('tvae_linear_fwd', W2.contiguous(), A1, b2, None, 1, None, H, C2, N, C, N, N, act, LRELU_SLOPE)
-            if nh <= SKINNY_MAX:
-                call('tvae_heads_fwd', Wh.contiguous(), H, N, bh, heads, N, nh, C2, N)
+            _heads_forward(Wh, bh, H, heads, nh, C2, N)
+        else:
+            w3 = _split_weight(W2, C2, C, False, 'enc_w2', nparts=rt.parts)
+            if rt.tail == 'wide':
+                wh = _split_weight(Wh[:, _enc_tail_perm(y.device)], nh, C2, False, 'enc_whp', nparts=rt.parts)
+                name, args = 'tvae_enc_tail_fwd_wide', (w3, wh, A1, N, b2, bh.contiguous())
             else:
-                call('tvae_linear_fwd', Wh.contiguous(), H, bh, None, 1, None, heads, nh, N, C2, N, N, ACT_NONE,
-                     LRELU_SLOPE)
-        if infer:
+                name, args = 'tvae_enc_tail_fwd_x6', (w3, A1, N, b2, Wh.contiguous(), bh.contiguous())
+            _note('enc.tail_fwd_wide' if rt.tail == 'wide' else 'enc.tail_fwd_x6')
+            with _timed(name, rt.parts):
+                call(name, *args, nh, H, N, heads, N, bits[0], bits[1], C, N, act, LRELU_SLOPE, rt.parts, a1max)
+        if rt.infer:
             return heads
         ctx.save_for_backward(y, W2, Wh, A1, H)
-        ctx.bits = bits
-        ctx.wide = wide
-        ctx.a1max = a1max if (fused or wide) else None      # (a view of keep['at']: max |A1| per channel for the h3 weight gradients)
+        ctx.route, ctx.at, ctx.bits = rt, at, bits
+        ctx.a1max = a1max                                # (a view of `at`: the h3 scales of the weight gradients, too)
         # wide tail, h3: bound per row of H = act(W2 A1 + b2) for the weight gradient that streams H (|act(x)| <= |x|)
-        ctx.hrows = torch.addmv(b2.detach().abs(), W2.detach().abs(), a1max) if (wide and a1max is not None) else None
+        ctx.hrows = torch.addmv(b2.detach().abs(), W2.detach().abs(), a1max) if (rt.tail == 'wide' and rt.h3) else None
         ctx.arith = get_gemm_mode()
         ctx.cfg = (C, Cin, k, R, pad, B, Ho, act)
         return heads
@@ -567,87 +597,72 @@ class EncoderFn(torch.autograd.Function):
     def backward(ctx, dheads):
         y, W2, Wh, A1, H = ctx.saved_tensors
         C, Cin, k, R, pad, B, Ho, act = ctx.cfg
+        rt = ctx.route
         N = B * R * Ho * Ho
         C2, nh = W2.shape[0], Wh.shape[0]
+        dev = y.device
         dheads = dheads.contiguous()
-        wide_bw = ctx.wide and ctx.bits is not None
-        words = torch.zeros(2, dtype=torch.float32, device=y.device) if (wide_bw and parts() == 2) else None
-        dmax, dhmax = (words[0:1], words[1:2]) if words is not None else (None, None)
-        dbh = _rowsum(dheads, nh, N, amax=dmax)          # (+ max |dheads| by the way: the h3 bound of the wide data gradient)
-        dA1 = None
+        wide_bw = rt.tail == 'wide' and rt.bits
+        # h3 bounds of the wide backward: max |dheads| (by the way of its row sums) and max |dH| (of those of dH)
+        dmax, dhmax = torch.zeros(2, dtype=torch.float32, device=dev).split(1) if (wide_bw and rt.h3) else (None, None)
+        dbh = _rowsum(dheads, nh, N, amax=dmax)
+        # data gradient of the tail from the sign words (the dgrad launches have an h3 instance whatever the forward ran in)
         dH = None
         if wide_bw:
             # dH = act'(H) . Wh^T dheads and dA1 = act'(A1) . W2^T dH in one launch (dH handed over in registers and stored
             # once for the two weight gradients below)
-            p_e = parts()
-            wht = _split_weight(Wh, C2, nh, True, 'enc_wht', nparts=p_e)
-            w3p = _split_weight(W2.t()[:, _enc_tail_perm(y.device)], C, C2, False, 'enc_w2p', nparts=p_e)
-            dH = torch.empty(C2, N, dtype=torch.float32, device=y.device)
-            dA1 = torch.empty(C, N, dtype=torch.float32, device=y.device)
+            wht = _split_weight(Wh, C2, nh, True, 'enc_wht', nparts=parts())
+            w3p = _split_weight(W2.t()[:, _enc_tail_perm(dev)], C, C2, False, 'enc_w2p', nparts=parts())
+            dH = torch.empty(C2, N, dtype=torch.float32, device=dev)
+            dA1 = torch.empty(C, N, dtype=torch.float32, device=dev)
             _note('enc.tail_dgrad_wide')
-            with _timed('tvae_enc_tail_dgrad_wide', p_e):
+            with _timed('tvae_enc_tail_dgrad_wide', parts()):
                 call('tvae_enc_tail_dgrad_wide', wht, w3p, dheads, N, nh, ctx.bits[0], ctx.bits[1], dH, N, dA1, N, C, N,
-                     LRELU_SLOPE, p_e, dmax)
-        elif ctx.bits is not None:
-            # dA1 straight from the head gradients and the sign words (dH is formed in registers, never stored)
-            p_e = 2 if parts() == 2 else _p3()      # h3 instance: 128 x 128 GEMM on two fp16 parts, scale per 32-column chunk
-            w3p = _split_weight(W2.t()[:, _enc_tail_perm(y.device)], C, C2, False, 'enc_w2p', nparts=p_e)
-            wh3 = _scratch(y.device, 'enc_wh3', query('tvae_dense_x6_bytes', C2, nh) // 4)
+                     LRELU_SLOPE, parts(), dmax)
+        elif rt.bits:
+            # dA1 straight from the head gradients and the sign words (dH is formed in registers, never stored); h3
+            # instance: 128 x 128 GEMM on two fp16 parts, scale per 32-column chunk
+            w3p = _split_weight(W2.t()[:, _enc_tail_perm(dev)], C, C2, False, 'enc_w2p', nparts=parts())
+            wh3 = _scratch(dev, 'enc_wh3', query('tvae_dense_x6_bytes', C2, nh) // 4)
             call('tvae_dense_split3', Wh.contiguous(), C2, wh3, wh3.numel() * 4, C2, nh, 1, None, None)
-            dA1 = torch.empty(C, N, dtype=torch.float32, device=y.device)
+            dA1 = torch.empty(C, N, dtype=torch.float32, device=dev)
             _note('enc.tail_dgrad_x6')
-            with _timed('tvae_enc_tail_dgrad_x6', p_e):
+            with _timed('tvae_enc_tail_dgrad_x6', parts()):
                 call('tvae_enc_tail_dgrad_x6', w3p, wh3, dheads, N, nh, ctx.bits[0], ctx.bits[1], dA1, N, C, N,
-                     LRELU_SLOPE, p_e)
-        # conv2's weight gradient in one pass from A1, the head gradients and the sign words of H (dH is formed inside the
-        # GEMM's operand build and never written); dWh / db2 from a sums-only pass over H
-        fuse_w = ctx.bits is not None and nh <= SKINNY_MAX and N % 32 == 0 and not wide_bw
-        if not fuse_w and dH is None:
-            dH = torch.empty(C2, N, dtype=torch.float32, device=y.device)
-        # wide tail in h3: both weight gradients as cooperative reductions over two stored operands (enc_tail_wgrad_plain_kernel)
-        wide_w = wide_bw and dmax is not None and ctx.hrows is not None and ctx.a1max is not None and N % 32 == 0
-        if wide_w:
+                     LRELU_SLOPE, parts())
+        # weight gradients of the head projection and of conv2
+        if rt.wgrad == 'wide':
+            # both as cooperative reductions over two stored operands (enc_tail_wgrad_plain_kernel)
             _note('enc.tail_wgrad_wide')
-            wsw = _scratch(y.device, 'enc_wgrad_slabs', query('tvae_enc_tail_wgrad_x6_ws_floats', N))
-            dWf = torch.empty(2, C2, C, dtype=torch.float32, device=y.device)
+            wsw = _scratch(dev, 'enc_wgrad_slabs', query('tvae_enc_tail_wgrad_x6_ws_floats', N))
+            dWf = torch.empty(2, C2, C, dtype=torch.float32, device=dev)
             with _timed('tvae_enc_tail_wgrad_wide', 2):
                 call('tvae_enc_tail_wgrad_wide', dheads, N, nh, H, N, dWf[0], wsw, wsw.numel(), C2, N, dmax, ctx.hrows)
-            dWh = dWf[0, :nh]
-            db2 = _rowsum(dH, C2, N, amax=dhmax)         # (+ max |dH|: the bound of the launch below)
+            db2 = _rowsum(dH, C2, N, amax=dhmax)
             with _timed('tvae_enc_tail_wgrad_wide', 2):
                 call('tvae_enc_tail_wgrad_wide', dH, N, C2, A1, N, dWf[1], wsw, wsw.numel(), C, N, dhmax, ctx.a1max)
-            dW2 = dWf[1]
+            dWh, dW2 = dWf[0, :nh], dWf[1]
         elif wide_bw:
-            dWh = _wgrad(dheads, H, nh, N, C2)
-            db2 = _rowsum(dH, C2, N)
-        elif nh <= SKINNY_MAX:
-            # one pass over H: masked dgrad + dWh + the row sums of dH (= db2)
-            npan = (N + 511) // 512
-            part = workspace(y.device, npan * C2 * (nh + 1) + 4 + 64 * C2 * (nh + 1))      # + room for the two-stage total
-            tot = torch.empty(nh + 1, C2, dtype=torch.float32, device=y.device)
-            call('tvae_heads_bwd', Wh.contiguous(), dheads, N, H, N, dH, N, nh, C2, N, act, LRELU_SLOPE, part,
-                 part.numel(), tot)
-            dWh, db2 = tot[:nh], tot[nh]
-        else:
-            dWh = _wgrad(dheads, H, nh, N, C2)
-            call('tvae_linear_dgrad', Wh.contiguous(), dheads, None, H, dH, nh, N, C2, N, N, act, LRELU_SLOPE)
-            db2 = _rowsum(dH, C2, N)
-        if fuse_w:
+            dWh, db2, dW2 = _wgrad(dheads, H, nh, N, C2), _rowsum(dH, C2, N), _wgrad(dH, A1, C2, N, C)
+        elif rt.wgrad == 'x6':
+            # conv2's in one pass from A1, the head gradients and the sign words of H (dH is formed inside the GEMM's operand
+            # build and never written); dWh / db2 from a sums-only pass over H
+            dWh, db2 = _heads_backward(Wh, dheads, H, None, nh, C2, N, act)
             _note('enc.tail_wgrad_x6')
-            dW2 = torch.empty(C2, C, dtype=torch.float32, device=y.device)
-            wsw = _scratch(y.device, 'enc_wgrad_slabs', query('tvae_enc_tail_wgrad_x6_ws_floats', N))
-            p_w = 2 if (parts() == 2 and ctx.a1max is not None) else _p3()
-            with _timed('tvae_enc_tail_wgrad_x6', p_w):
+            dW2 = torch.empty(C2, C, dtype=torch.float32, device=dev)
+            wsw = _scratch(dev, 'enc_wgrad_slabs', query('tvae_enc_tail_wgrad_x6_ws_floats', N))
+            with _timed('tvae_enc_tail_wgrad_x6', rt.parts):
                 call('tvae_enc_tail_wgrad_x6', A1, N, dheads, N, nh, ctx.bits[0], Wh.contiguous(), dW2, wsw, wsw.numel(), C,
-                     N, LRELU_SLOPE, p_w, ctx.a1max if p_w == 2 else None)
-        elif not wide_w:
+                     N, LRELU_SLOPE, rt.parts, ctx.a1max)
+        else:
+            dH = torch.empty(C2, N, dtype=torch.float32, device=dev)
+            dWh, db2 = _heads_backward(Wh, dheads, H, dH, nh, C2, N, act)
             dW2 = _wgrad(dH, A1, C2, N, C)
-        if dA1 is None:
-            dA1 = torch.empty(C, N, dtype=torch.float32, device=y.device)
+        if not rt.bits:
+            dA1 = torch.empty(C, N, dtype=torch.float32, device=dev)
             call('tvae_linear_dgrad', W2.contiguous(), dH, None, A1, dA1, C2, N, C, N, N, act, LRELU_SLOPE)
         del dH
-        db1 = torch.empty(C, dtype=torch.float32, device=y.device) if ctx.at is not None else _rowsum(dA1, C, N)
-        dbank = conv1_wgrad(y, dA1, C, R, k, pad, ctx.at, db1 if ctx.at is not None else None)
+        dbank, db1 = conv1_backward(y, dA1, C, R, k, pad, ctx.at)
         dw1 = rotate_bank_bwd(dbank, C, Cin, k, R)
         return None, dw1, db1, dW2, db2, dWh, dbh, None, None, None
 
@@ -669,9 +684,8 @@ class TransAttnEncoderFn(torch.autograd.Function):
         _expect(Ho >= 1 and (plain or R in (4, 8, 16)), 'translation-attention encoder geometry')
         Re = 1 if plain else R
         P = Ho * Ho
-        keep = {}
-        A1 = conv1_forward(y, None if plain else w1, b1, C, Re, k, pad, act, keep,
-                           bank=w1.contiguous().view(C, Cin * k * k) if plain else None)
+        A1, ctx.at = conv1_forward(y, None if plain else w1, b1, C, Re, k, pad, act,
+                                   bank=w1.contiguous().view(C, Cin * k * k) if plain else None)
         _note('trans_attn.plain' if plain else 'trans_attn.rot_pool')
         if plain:
             X = A1                                       # [C][B*P]
@@ -683,12 +697,8 @@ class TransAttnEncoderFn(torch.autograd.Function):
         H = torch.empty(C2, N, dtype=torch.float32, device=y.device)
         call('tvae_linear_fwd', W2.contiguous(), X, b2, None, 1, None, H, C2, N, C, N, N, act, LRELU_SLOPE)
         heads = torch.empty(nh, N, dtype=torch.float32, device=y.device)
-        if nh <= SKINNY_MAX:
-            call('tvae_heads_fwd', Wh.contiguous(), H, N, bh, heads, N, nh, C2, N)
-        else:
-            call('tvae_linear_fwd', Wh.contiguous(), H, bh, None, 1, None, heads, nh, N, C2, N, N, ACT_NONE, LRELU_SLOPE)
+        _heads_forward(Wh, bh, H, heads, nh, C2, N)
         ctx.save_for_backward(y, w1, fw, W2, Wh, A1, X, H)
-        ctx.at = keep.get('at')
         ctx.cfg = (C, Cin, k, R, pad, B, Ho, act, plain)
         ctx.arith = get_gemm_mode()
         return heads
@@ -705,24 +715,13 @@ class TransAttnEncoderFn(torch.autograd.Function):
         dheads = dheads.contiguous()
         dbh = _rowsum(dheads, nh, N)
         dH = torch.empty(C2, N, dtype=torch.float32, device=dev)
-        if nh <= SKINNY_MAX:
-            npan = (N + 511) // 512
-            part = workspace(dev, npan * C2 * (nh + 1) + 4 + 64 * C2 * (nh + 1))      # + room for the two-stage total
-            tot = torch.empty(nh + 1, C2, dtype=torch.float32, device=dev)
-            call('tvae_heads_bwd', Wh.contiguous(), dheads, N, H, N, dH, N, nh, C2, N, act, LRELU_SLOPE, part,
-                 part.numel(), tot)
-            dWh, db2 = tot[:nh], tot[nh]
-        else:
-            dWh = _wgrad(dheads, H, nh, N, C2)
-            call('tvae_linear_dgrad', Wh.contiguous(), dheads, None, H, dH, nh, N, C2, N, N, act, LRELU_SLOPE)
-            db2 = _rowsum(dH, C2, N)
+        dWh, db2 = _heads_backward(Wh, dheads, H, dH, nh, C2, N, act)
         dW2 = _wgrad(dH, X, C2, N, C)
         dX = torch.empty(C, N, dtype=torch.float32, device=dev)
         # the pooled tensor is not an activation output: plain data gradient (groupconv 0: X = act(conv1), masked)
         call('tvae_linear_dgrad', W2.contiguous(), dH, None, A1 if plain else None, dX, C2, N, C, N, N,
              act if plain else ACT_NONE, LRELU_SLOPE)
         dfw = dfb = None
-        Re = 1 if plain else R
         if plain:
             dA1 = dX
         else:
@@ -733,8 +732,7 @@ class TransAttnEncoderFn(torch.autograd.Function):
             call('tvae_rot_pool_bwd', A1, dX, fw.contiguous().view(-1), dA1, partp, partp.numel(), dtot, C, B, R, P, act,
                  LRELU_SLOPE)
             dfw, dfb = dtot[:R].view(1, R), dtot[R:]
-        db1 = torch.empty(C, dtype=torch.float32, device=dev) if ctx.at is not None else _rowsum(dA1, C, dA1.shape[1])
-        dbank = conv1_wgrad(y, dA1, C, Re, k, pad, ctx.at, db1 if ctx.at is not None else None)
+        dbank, db1 = conv1_backward(y, dA1, C, 1 if plain else R, k, pad, ctx.at)
         dw1 = dbank.view(C, Cin, k, k) if plain else rotate_bank_bwd(dbank, C, Cin, k, R)
         return None, dw1, db1, dfw, dfb, dW2, db2, dWh, dbh, None, None, None
 

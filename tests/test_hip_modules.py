@@ -117,12 +117,15 @@ def test_encoder_golden(name):
     assert_encoder_grads(enc, fx, GRAD_TOL, prefix='g.', name='', elbo_loss=False)
 
 
-@pytest.mark.parametrize('actname', ['leakyrelu', 'tanh'])
-def test_encoder_tail_paths_agree(actname):
+@pytest.mark.parametrize('actname,batch', [pytest.param('leakyrelu', 6, id='leakyrelu'), pytest.param('tanh', 6, id='tanh'),
+                                           pytest.param('leakyrelu', 8, id='leakyrelu-B8'),
+                                           pytest.param('tanh', 8, id='tanh-B8')])
+def test_encoder_tail_paths_agree(actname, batch):
     """128-channel encoder in the default arithmetic: the fused tail (conv2 + heads in one kernel; LeakyReLU: fused data
     gradient from the sign words; tanh: fused forward, unfused backward) against the unfused kernels on the same input --
     head outputs within 1e-5, every encoder gradient within 2e-4 (LeakyReLU rows with a flipped kink allowed as in
-    assert_grad_close)."""
+    assert_grad_close).  The fused conv2 weight gradient reduces over 32-column chunks: 6 images give N = 40 368 columns
+    (not a multiple of 32: generic weight gradient), 8 give 53 824 = 32 x 1 682 (tvae_enc_tail_wgrad_x6)."""
     import src.models as M
     from tvae import _lib, ops
     torch.manual_seed(4)
@@ -130,8 +133,9 @@ def test_encoder_tail_paths_agree(actname):
     enc = M.InferenceNetwork_AttentionTranslation_AttentionRotation(
         28, 1, 2, kernels_num=128, kernels_size=28, padding=14, groupconv=8, rot_refinement=True, theta_prior=np.pi,
         normal_prior_over_r=False, activation=act).to(dev())
-    y = torch.randn(6, 1, 28, 28, device=dev())
-    w = torch.randn(7, 6 * 8 * 29 * 29, device=dev())
+    N = batch * 8 * 29 * 29
+    y = torch.randn(batch, 1, 28, 28, device=dev())
+    w = torch.randn(7, N, device=dev())
 
     def run(fused):
         for p in enc.parameters():
@@ -149,6 +153,7 @@ def test_encoder_tail_paths_agree(actname):
     h0, g0, t0 = run(False)
     assert 'enc.tail_fwd_x6' in t1 and 'enc.tail_fwd_x6' not in t0
     assert ('enc.tail_dgrad_x6' in t1) == (actname == 'leakyrelu')
+    assert ('enc.tail_wgrad_x6' in t1) == (actname == 'leakyrelu' and N % 32 == 0)
     assert rel_err(h1, h0) < 1e-5
     assert set(g1) == set(g0) and len(g1) >= 6
     for k_ in g0:

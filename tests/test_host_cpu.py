@@ -2,6 +2,7 @@
 host tables equal the oracle's, the drop-in classes reproduce the reference's parameter names / shapes /
 default initialisation, checkpoints pickle as `src.models.*`, and the product path refuses CPU tensors."""
 import io
+import itertools
 import os
 import pickle
 import re
@@ -417,6 +418,122 @@ def test_decoder_route_of_named_configurations(name, mode):
             want = {f: split and f in fields for f in ops.DecoderRoute._fields}
             want.update(ldn=B * Np + (pad if split else 0), h3=split and mode == 'h3' and 'split' in fields, infer=infer)
             assert ops.decoder_route(B, Np, F_, nh, n_out, act, resid, Ff, infer)._asdict() == want
+
+
+# (arithmetic, head rows, LeakyReLU, N % 32 == 0, conv1 left max |A1|) -> (tail, parts, h3, bits, wgrad) of ops.encoder_route
+# in training, C = C2 = 128, N < 2^25; None = whatever.  In inference: the same tail / parts / h3, no bits, wgrad 'plain'.
+_PLAIN = ('plain', 0, False, False, 'plain')
+ENCODER_ROUTES = [
+    (('f32', None, None, None, None), _PLAIN),
+    (('x6', 7, True, True, None), ('fused', 3, False, True, 'x6')),
+    (('x6', 7, True, False, None), ('fused', 3, False, True, 'plain')),
+    (('x6', 7, False, None, None), ('fused', 3, False, False, 'plain')),
+    (('x6', (8, 23, 103, 128), None, None, None), _PLAIN),
+    (('h3', 7, True, True, True), ('fused', 2, True, True, 'x6')),
+    (('h3', 7, True, True, False), ('fused', 3, False, True, 'x6')),
+    (('h3', (8, 23, 128), True, True, True), ('wide', 2, True, True, 'wide')),
+    (('h3', 23, True, False, True), ('wide', 2, True, True, 'plain')),
+    (('h3', 23, False, None, True), ('wide', 2, True, False, 'plain')),
+    (('h3', 23, None, None, False), _PLAIN),
+    (('h3', 129, None, None, None), _PLAIN),
+    (('bf16', 7, True, True, None), ('fused', 1, False, True, 'x6')),
+    (('bf16', 23, True, None, None), ('wide', 1, False, True, 'plain')),
+]
+
+
+def _encoder_route_cases():
+    """ENCODER_ROUTES with every None expanded: (mode, nh, act, N, out_max, expected training route)."""
+    from tvae import ops
+    for (mode, nh, lrelu, n32, out_max), want in ENCODER_ROUTES:
+        for nh_, lrelu_, n32_, out_max_ in itertools.product(
+                (3, 7, 8, 23, 128, 129) if nh is None else nh if isinstance(nh, tuple) else (nh,),
+                (True, False) if lrelu is None else (lrelu,), (True, False) if n32 is None else (n32,),
+                (True, False) if out_max is None else (out_max,)):
+            yield (mode, nh_, ops.ACT_LRELU if lrelu_ else ops.ACT_TANH, 8 * 8 * 29 * 29 if n32_ else 6 * 8 * 29 * 29, out_max_,
+                   dict(zip(('tail', 'parts', 'h3', 'bits', 'wgrad'), want)))
+
+
+def test_encoder_route_of_named_configurations():
+    """ops.encoder_route -- every structural decision of the encoder tail, taken once in the forward and kept for the
+    backward -- against the table of configurations in each arithmetic, in training and in inference; the limits (128
+    channels, 2^25 columns, 7 | 8 and 128 | 129 head rows) and the FUSE_ENC_TAIL switch (host only: no library, no GPU)."""
+    from tvae import ops
+    from tvae._lib import arithmetic
+    L = ops.ACT_LRELU
+    cases = list(_encoder_route_cases())
+    assert {c[0] for c in cases} == {'f32', 'x6', 'h3', 'bf16'} and len(cases) > 60
+    for mode, nh, act, N, out_max, want in cases:
+        with arithmetic(mode):
+            assert ops.encoder_route(128, 128, nh, N, act, out_max, False)._asdict() == dict(want, infer=False), (mode, nh)
+            assert ops.encoder_route(128, 128, nh, N, act, out_max, True)._asdict() == \
+                dict(want, bits=False, wgrad='plain', infer=True), (mode, nh)
+    plain = dict(zip(('tail', 'parts', 'h3', 'bits', 'wgrad'), _PLAIN), infer=False)
+    N = 8 * 8 * 29 * 29
+    for mode in ('x6', 'h3', 'bf16'):
+        with arithmetic(mode):
+            for nh in (7, 23) if mode != 'x6' else (7,):         # fused / wide; each of the one-offs changes one thing
+                assert ops.encoder_route(128, 128, nh, (1 << 25) - 32, L, True, False).tail == ('fused' if nh == 7 else 'wide')
+                assert ops.encoder_route(128, 128, nh, 1 << 25, L, True, False)._asdict() == plain
+                for C, C2 in ((64, 128), (128, 64), (64, 64)):
+                    assert ops.encoder_route(C, C2, nh, N, L, True, False)._asdict() == plain
+            wide = 'plain' if mode == 'x6' else 'wide'
+            tails = [ops.encoder_route(128, 128, nh, N, L, True, False).tail for nh in (7, 8, 128, 129)]
+            assert tails == ['fused', wide, wide, 'plain']
+    old, ops.FUSE_ENC_TAIL = ops.FUSE_ENC_TAIL, False
+    try:
+        for mode, nh, act, N, out_max, _ in cases:
+            with arithmetic(mode):
+                for infer in (False, True):
+                    assert ops.encoder_route(128, 128, nh, N, act, out_max, infer)._asdict() == dict(plain, infer=infer)
+    finally:
+        ops.FUSE_ENC_TAIL = old
+
+
+# (arithmetic, head rows, LeakyReLU, image side = Ho of launch_trace: N = 512 | 392, conv1 path, inference) -> entry points of
+# EncoderFn's forward + backward in order, `tvae_` dropped; recorded on the tree BEFORE EncoderRoute existed
+ENCODER_LAUNCHES = {
+    ('f32', 7, True, 8, 'dft', False):
+        'rotate_bank_fwd conv1_fwd linear_fwd heads_fwd rowdot_seg seg_sum heads_bwd linear_wgrad linear_dgrad rowdot_seg '
+        'seg_sum conv1_wgrad rotate_bank_bwd',
+    ('x6', 7, True, 8, 'dft', False):
+        'rotate_bank_fwd conv1_fwd_dft dense_split3 enc_tail_fwd_x6 rowdot_seg seg_sum dense_split3 dense_split3 '
+        'enc_tail_dgrad_x6 heads_bwd enc_tail_wgrad_x6 conv1_wgrad_dft rotate_bank_bwd',
+    ('x6', 7, False, 7, 'x6', False):
+        'rotate_bank_fwd bank_split3 conv1_fwd_x6 dense_split3 enc_tail_fwd_x6 rowdot_seg seg_sum heads_bwd linear_wgrad '
+        'linear_dgrad rowdot_seg seg_sum dy_split3 conv1_wgrad_x6 rotate_bank_bwd',
+    ('h3', 7, True, 8, 'dft', False):
+        'rotate_bank_fwd conv1_fwd_dft dense_split2h enc_tail_fwd_x6 rowdot_seg seg_sum dense_split2h dense_split3 '
+        'enc_tail_dgrad_x6 heads_bwd enc_tail_wgrad_x6 conv1_wgrad_dft rotate_bank_bwd',
+    ('h3', 23, True, 8, 'dft', False):
+        'rotate_bank_fwd conv1_fwd_dft dense_split2h dense_split2h enc_tail_fwd_wide rowdot_seg seg_sum dense_split2h '
+        'dense_split2h enc_tail_dgrad_wide enc_tail_wgrad_wide rowdot_seg seg_sum enc_tail_wgrad_wide conv1_wgrad_dft '
+        'rotate_bank_bwd',
+    ('h3', 23, True, 7, 'dft', False):
+        'rotate_bank_fwd conv1_fwd_dft dense_split2h dense_split2h enc_tail_fwd_wide rowdot_seg seg_sum dense_split2h '
+        'dense_split2h enc_tail_dgrad_wide linear_wgrad rowdot_seg seg_sum linear_wgrad conv1_wgrad_dft rotate_bank_bwd',
+    ('h3', 23, True, 8, 'x6', False):
+        'rotate_bank_fwd bank_split3 conv1_fwd_x6 linear_fwd linear_fwd rowdot_seg seg_sum linear_wgrad linear_dgrad '
+        'rowdot_seg seg_sum linear_wgrad linear_dgrad rowdot_seg seg_sum dy_split3 conv1_wgrad_x6 rotate_bank_bwd',
+    ('bf16', 23, True, 8, 'dft', False):
+        'rotate_bank_fwd conv1_fwd_dft dense_split3 dense_split3 enc_tail_fwd_wide rowdot_seg seg_sum dense_split3 '
+        'dense_split3 enc_tail_dgrad_wide linear_wgrad rowdot_seg seg_sum linear_wgrad conv1_wgrad_dft rotate_bank_bwd',
+    ('h3', 7, True, 8, 'dft', True): 'rotate_bank_fwd conv1_fwd_dft dense_split2h enc_tail_fwd_x6',
+}
+
+
+@pytest.mark.parametrize('row', sorted(ENCODER_LAUNCHES), ids=lambda r: '-'.join(str(v) for v in r))
+def test_encoder_launches_of_named_configurations(row):
+    """The entry points EncoderFn launches, forward then backward, for rows of the route table: run on CPU tensors with
+    `ops.call` recorded and `ops.query` stubbed (profiles/tools/launch_trace.py; host only: no library, no GPU)."""
+    import importlib.util
+    from tvae import ops
+    spec = importlib.util.spec_from_file_location(
+        'launch_trace', os.path.join(ROOT, 'profiles', 'tools', 'launch_trace.py'))
+    lt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(lt)
+    mode, nh, lrelu, n, conv, infer = row
+    rec = lt.trace('encoder', mode, nh, ops.ACT_LRELU if lrelu else ops.ACT_TANH, n, conv, 128, infer)
+    assert lt.names(rec) == ['tvae_' + e for e in ENCODER_LAUNCHES[row].split()]
 
 
 def test_scratch_buffers_outlive_a_captured_graph():
