@@ -1,5 +1,5 @@
-/* C ABI of libtvae_cluster.so: batched Lloyd k-means and Ward linkage on the GPU (gfx950), the hot paths of
- * clustering_*.py.
+/* C ABI of libtvae_cluster.so: batched Lloyd k-means, Ward linkage and exact t-SNE on the GPU (gfx950), the hot paths
+ * of clustering_*.py.
  *
  * Same conventions as tvae_hip.h: raw device pointers and sizes, the stream as void*, `int` return = hipError_t.  The
  * entry points never allocate, free or synchronise and keep no process-wide state; the workspace is the caller's,
@@ -27,7 +27,7 @@ typedef void* tvae_stream_t;
 
 #define TVAE_KMEANS_MAX_RESTARTS 65535
 
-/* Still 1: the Ward entry points below were ADDED, no existing prototype or meaning changed. */
+/* Still 1: the Ward and t-SNE entry points below were ADDED, no existing prototype or meaning changed. */
 int tvae_cluster_abi_version(void);          /* == 1 */
 
 /* floats of workspace for one assign / update pair: per restart G x (k*d sums, k counts, 1 changed count, 1 sum of
@@ -92,6 +92,50 @@ int tvae_ward_merge(const double* C_in, long ld_in, const float* cnt_in, const i
                     const int* nn, double* C_out, float* Ct_out, long ld_out, float* cnt_out, int* id_out,
                     double* hmax_out, int* rec_ids, double* rec_hs, int* m_out, int* ws, long ws_ints, int M, int d,
                     int N, int base, int cap, tvae_stream_t stream);
+
+/* ---- t-SNE of the latents: sparse input similarities from brute-force kNN, exact all-pairs repulsion -----------------
+ *
+ * Points FEATURE-major as above, Xt[d][ldx]; the 2-D embedding, its gains, its last update and the repulsion sums share
+ * one layout, [2][ldy] (ldy >= N; ldy % 4 == 0 and a 16-byte aligned base take the vector loads, anything else a scalar
+ * instance with the same arithmetic).  P is CSR: rowptr[N + 1], col[nnz], val[nnz] (fp32); entries outside [0, nnz) and
+ * columns outside [0, N) are skipped, never dereferenced.  q_ij = 1 / (1 + |y_i - y_j|^2) in fp32 (reciprocal
+ * instruction, 1 ulp); j == i is excluded BY INDEX, so a duplicate of point i is an ordinary neighbour at distance 0.
+ * No float atomics: every output is a pure function of the inputs, bitwise reproducible; the split of the columns into
+ * ranges depends on N only.  Sums that cross rows (Z, the KL divergence, |grad|^2) are fp64 in a fixed order.
+ *
+ * Supported: 2 <= N <= 2^24; tvae_knn also 1 <= d <= 256 and 1 <= K <= 256 with K < N; 1 <= nnz < 2^31; anything else
+ * returns hipErrorInvalidValue (1) and writes nothing. */
+
+/* workgroups of 256 rows: the number of |grad|^2 partials of tvae_tsne_step and of fp64 workspace words of
+ * tvae_tsne_kl.  0 for unsupported arguments. */
+int tvae_tsne_groups(int N);
+/* floats of workspace of tvae_tsne_repulsion (8-byte aligned): per-workgroup fp64 partials of Z and per column range
+ * three fp32 partials per row.  0 for unsupported arguments. */
+long tvae_tsne_repulsion_ws_floats(int N);
+
+/* idx[N][K] and d2[N][K]: the K nearest neighbours of every point other than itself and their squared distances in the
+ * direct form sum_f (x_f - c_f)^2 (fp32 FMA chain in ascending f), each row sorted ascending by (d2 then index).  A
+ * non-finite distance is never selected (a row without K finite ones keeps idx = -1 and d2 = +inf at its end). */
+int tvae_knn(const float* Xt, long ldx, int* idx, float* d2, int N, int d, int K, tvae_stream_t stream);
+
+/* rep[c][i] = sum over j != i of q_ij^2 (y_ci - y_cj) (fp32 row sums) and Z[0] = sum over i != j of q_ij (fp32 per row
+ * and column range, everything above that in fp64). */
+int tvae_tsne_repulsion(const float* Yt, long ldy, float* rep, double* Z, float* ws, long ws_floats, int N,
+                        tvae_stream_t stream);
+
+/* One gradient-descent step.  grad_i = 4 (exaggeration * sum_e val_e q_ie (y_i - y_col(e)) - rep_i / Z); sklearn's rule:
+ * gains += 0.2 where update * grad < 0 and *= 0.8 elsewhere with floor 0.01; update = momentum * update - learning_rate *
+ * gains * grad; Yt_out = Yt + update.  gains and update are updated in place (a row only touches its own), the
+ * embedding is NOT: Yt_out must be a second buffer, other rows still read the old Yt.  grad (may be NULL) receives the
+ * gradient; gnorm2[tvae_tsne_groups(N)] the fp64 sum of |grad_i|^2 of every 256 rows. */
+int tvae_tsne_step(const int* rowptr, const int* col, const float* val, long nnz, const float* Yt, const float* rep,
+                   const double* Z, float* gains, float* update, float* Yt_out, float* grad, double* gnorm2, long ldy,
+                   int N, float exaggeration, float momentum, float learning_rate, tvae_stream_t stream);
+
+/* kl[0] = sum over the CSR entries of val ln(max(val, eps) / max(q / Z, eps)) with eps = 2^-52, in fp64 throughout;
+ * ws holds tvae_tsne_groups(N) fp64 words. */
+int tvae_tsne_kl(const int* rowptr, const int* col, const float* val, long nnz, const float* Yt, long ldy,
+                 const double* Z, double* kl, double* ws, long ws_doubles, int N, tvae_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
-"""ctypes binding of libtvae_cluster.so (C ABI declared in include/tvae_cluster.h): the batched k-means and
-Ward linkage kernels.
+"""ctypes binding of libtvae_cluster.so (C ABI declared in include/tvae_cluster.h): the batched k-means, Ward
+linkage and t-SNE kernels.
 
 A library of its own beside libtvae_hip.so -- the ABI of the training kernels (tvae._lib.SIGNATURES, version 7) is not
 touched by the clustering half.  Same rules: no CPU fallback, tensors are checked by tvae._lib._ptr (GPU, contiguous,
@@ -29,6 +29,12 @@ SIGNATURES = {
     # C_in (fp64), ld_in, cnt_in, id_in, hmax_in (fp64), nn, C_out (fp64), Ct_out, ld_out, cnt_out, id_out,
     # hmax_out (fp64), rec_ids, rec_hs (fp64), m_out, ws, ws_ints, M, d, N, base, cap
     'tvae_ward_merge': 'plpppp' 'pplppp' 'pppp' 'l' 'iiiii',
+    'tvae_knn': 'plppiii',                    # Xt, ldx, idx, d2, N, d, K
+    'tvae_tsne_repulsion': 'plpppli',         # Yt, ldy, rep, Z (fp64), ws, ws_floats, N
+    # rowptr, col, val, nnz, Yt, rep, Z (fp64), gains, update, Yt_out, grad (or None), gnorm2 (fp64), ldy, N,
+    # exaggeration, momentum, learning_rate
+    'tvae_tsne_step': 'ppplpppppppplifff',
+    'tvae_tsne_kl': 'ppplplpppli',            # rowptr, col, val, nnz, Yt, ldy, Z, kl, ws (fp64 all three), ws_doubles, N
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
@@ -37,6 +43,8 @@ QUERIES = {
     'tvae_ward_nn_ws_floats': ('ii', 'l'),
     'tvae_ward_nn_splits': ('ii', 'i'),
     'tvae_ward_merge_ws_ints': ('ii', 'l'),
+    'tvae_tsne_groups': ('i', 'i'),
+    'tvae_tsne_repulsion_ws_floats': ('i', 'l'),
 }
 
 _cl = None

@@ -287,6 +287,9 @@ def query(name, *args) -> int:
 _F64_OK = {('tvae_elbo_reduce', 3), ('tvae_elbo_reduce', 5), ('tvae_elbo_reduce_bwd', 0), ('tvae_elbo_reduce_bwd', 2)}
 # libtvae_cluster.so (tvae._cluster_lib): the fp64 centroids, heights and records of tvae_ward_merge
 _F64_OK |= {('tvae_ward_merge', p) for p in (0, 4, 6, 11, 13)}
+# ... and Z, the |grad|^2 partials, the KL divergence and its workspace of the t-SNE entry points
+_F64_OK |= {('tvae_tsne_repulsion', 3), ('tvae_tsne_step', 6), ('tvae_tsne_step', 11)}
+_F64_OK |= {('tvae_tsne_kl', p) for p in (6, 7, 8)}
 
 
 def _ptr(t, name, pos):

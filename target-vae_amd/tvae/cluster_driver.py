@@ -6,7 +6,14 @@ of results.txt.  The latents of the whole stack are extracted on the device (tva
 runs on the HIP kernels (tvae.cluster.kmeans), and so does Ward agglomerative clustering (tvae.cluster.ward_linkage;
 TVAE_WARD=host selects the reference's sklearn path).
 New optional flags: --seed, --n-init, --out-dir.  Besides results.txt the run writes latents.npy, rotations.npy,
-translations.npy and clusters.npy.  The plots of the reference (t-SNE, confusion matrix, histograms) are not built.
+translations.npy and clusters.npy.
+
+TVAE_FIGURES=1 adds the last step of the reference scripts: the t-SNE of the latents (tvae.tsne on the GPU, exact
+repulsion, seeded by --seed; saved as tsne.npy and tsne.jpg) and the figures of tvae.figures under the reference's file
+names -- confusion_matrix.jpg (mnist, dsprites), z_vals.jpg (galaxy with --z-dim 2; written INTO the output directory,
+the reference drops the path separator there), the three predicted_*_vals.jpg histograms (particles).  Without
+matplotlib tsne.npy is still written and stderr says that the figures were skipped.  With the switch unset a run is
+what it was before the figures existed, the line on stderr that says so included.
 """
 from __future__ import annotations
 
@@ -121,6 +128,42 @@ def _load(kind, args):
     return images.view(-1, args.in_channels, n, m), lab[:, 1], (lab[:, 3:4], lab[:, 4:])
 
 
+def _figures(kind, args, out_dir, z_values, rot_pred, tr_pred, clusters, y_labels, mapping):
+    """TVAE_FIGURES=1: tsne.npy and the figures of the reference script `kind` (module docstring)."""
+    from . import tsne as tsne_mod
+    try:
+        from . import figures
+        figures._plt()
+    except ImportError as e:
+        figures = None
+        print('# matplotlib is not available ({}): the figures are skipped, tsne.npy is still written'.format(e),
+              file=sys.stderr)
+    print('# saving tsne figure ... ', file=sys.stderr)
+    if z_values.shape[0] > 30:
+        res = tsne_mod.tsne(z_values.float().contiguous(), learning_rate=200.0, seed=args.seed)
+        emb = res.embedding.cpu().numpy()
+        print('# t-SNE on the GPU: {} iterations, KL divergence {}'.format(res.n_iter, res.kl_divergence), file=sys.stderr)
+        np.save(os.path.join(out_dir, 'tsne.npy'), emb)
+        if figures is not None:
+            # as the reference: coloured by the true labels (mnist, dsprites), one colour for particles.  Its galaxy script
+            # names labels it never loads; the clusters colour that scatter here
+            colour = y_labels if y_labels is not None else (None if kind == 'particles' else clusters)
+            figures.save_tsne(out_dir, emb, None if colour is None else np.asarray(colour))
+    else:
+        print('# t-SNE skipped: perplexity 30 needs more than 30 points, there are {}'.format(z_values.shape[0]),
+              file=sys.stderr)
+    if figures is None:
+        return
+    if kind in ('mnist', 'dsprites') and y_labels is not None:
+        print('# saving confusion matrix ... ', file=sys.stderr)
+        figures.save_confusion_matrix(out_dir, np.asarray(y_labels), clusters, mapping[1])
+    if kind == 'galaxy' and args.z_dim == 2:
+        figures.save_z_vals(out_dir, z_values.cpu().numpy(), clusters)
+    if kind == 'particles':
+        print('# saving histograms ... ', file=sys.stderr)
+        figures.save_histograms(out_dir, rot_pred.cpu().numpy(), tr_pred.cpu().numpy())
+
+
 def run(kind: str, argv=None):
     args = build_parser(kind).parse_args(argv)
     from src import models  # noqa: F401     (whole-module checkpoints unpickle as src.models.*)
@@ -174,10 +217,13 @@ def run(kind: str, argv=None):
         clusters = res.labels.cpu().numpy()
         print('# k-means: best of {} restarts is {} (inertia {}, {} iterations)'.format(
             res.all_inertia.numel(), res.best, res.inertia, res.n_iter), file=sys.stderr)
-    acc = None
+    acc = mapping = None
     if y_labels is not None:
-        _, acc = cluster.cluster_acc(np.asarray(y_labels), clusters)
-    print('# the t-SNE, confusion-matrix and histogram figures of the reference are not built', file=sys.stderr)
+        mapping, acc = cluster.cluster_acc(np.asarray(y_labels), clusters)
+    if os.environ.get('TVAE_FIGURES', '') == '1':
+        _figures(kind, args, out_dir, z_values, rot_pred, tr_pred, clusters, y_labels, mapping)
+    else:
+        print('# the t-SNE, confusion-matrix and histogram figures of the reference are not built', file=sys.stderr)
 
     np.save(os.path.join(out_dir, 'latents.npy'), z_values.cpu().numpy())
     np.save(os.path.join(out_dir, 'rotations.npy'), rot_pred.cpu().numpy())

@@ -1,0 +1,115 @@
+"""The figures of the reference clustering_*.py, drawn from host arrays alone (matplotlib, Agg backend; no GPU, no
+seaborn): tsne.jpg, confusion_matrix.jpg, z_vals.jpg and the three histograms of clustering_particles.py.  File names,
+figure sizes, colour maps and axis labels are the reference's; every function returns the path it wrote.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+
+def _plt():
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    return plt
+
+
+def _rainbow_norm(plt):
+    from matplotlib import colors
+    cmap = plt.cm.rainbow
+    return cmap, colors.BoundaryNorm(np.arange(0, 11, 1), cmap.N)
+
+
+def save_tsne(out_dir, embedding, labels=None):
+    """Scatter of the [N][2] embedding coloured by `labels`, with the reference's thin colour bar whose ticks sit in the
+    middle of each class; None draws one colour and no bar (what the reference's particles scatter shows: it passes no
+    `c`).  The caller chooses: true labels for mnist and dsprites as in the reference, None for particles, the clusters
+    for galaxy, whose reference script names labels that it never loads."""
+    from mpl_toolkits.axes_grid1 import make_axes_locatable
+    plt = _plt()
+    Y = np.asarray(embedding)
+    fig = plt.figure(figsize=(10, 10))
+    cmap, norm = _rainbow_norm(plt)
+    if labels is None:
+        plt.scatter(Y[:, 0], Y[:, 1], s=2)
+    else:
+        plt.scatter(Y[:, 0], Y[:, 1], c=np.asarray(labels), cmap=cmap, norm=norm, s=2)
+        cax = make_axes_locatable(plt.gca()).append_axes('right', size='2%', pad=0.2)
+        cb = plt.colorbar(cax=cax)
+        ticks = np.arange(0, 10, 1)
+        cb.set_ticks(ticks + .5)
+        cb.set_ticklabels(ticks)
+    path = os.path.join(out_dir, 'tsne.jpg')
+    plt.savefig(path)
+    plt.close(fig)
+    return path
+
+
+def confusion_counts(y_true, y_pred):
+    """sklearn's confusion_matrix over the sorted union of the labels: rows = true labels, columns = clusters."""
+    y_true, y_pred = np.asarray(y_true).astype(np.int64), np.asarray(y_pred).astype(np.int64)
+    classes = np.unique(np.concatenate([y_true, y_pred]))
+    cm = np.zeros((classes.size, classes.size), dtype=np.int64)
+    np.add.at(cm, (np.searchsorted(classes, y_true), np.searchsorted(classes, y_pred)), 1)
+    return cm
+
+
+def save_confusion_matrix(out_dir, y_true, y_pred, mapping_cols=None):
+    """Heat map (Blues, annotated counts) of the confusion matrix with its columns permuted by the cluster_acc mapping
+    (mapping[1]), so that a good clustering shows on the diagonal.  The permutation is applied when it fits the matrix, as
+    it does whenever labels and clusters are numbered from 0 without gaps (the reference's situation)."""
+    plt = _plt()
+    cm = confusion_counts(y_true, y_pred)
+    if mapping_cols is not None and sorted(np.asarray(mapping_cols).tolist()) == list(range(cm.shape[1])):
+        cm = cm[:, np.asarray(mapping_cols)]
+    n = cm.shape[0]
+    fig = plt.figure(figsize=(10, 10))
+    ax = plt.gca()
+    im = ax.imshow(cm, cmap='Blues')
+    plt.colorbar(im, ax=ax, fraction=0.046, pad=0.04)
+    half = cm.max() / 2.0 if cm.size else 0
+    for r in range(n):
+        for c in range(cm.shape[1]):
+            ax.text(c, r, format(int(cm[r, c]), 'd'), ha='center', va='center',
+                    color='white' if cm[r, c] > half else 'black')
+    ax.set_xticks(np.arange(cm.shape[1]))
+    ax.set_xticklabels(np.arange(cm.shape[1]))
+    ax.set_yticks(np.arange(n))
+    ax.set(xlabel='clusters', ylabel='true_labels')
+    path = os.path.join(out_dir, 'confusion_matrix.jpg')
+    plt.savefig(path)
+    plt.close(fig)
+    return path
+
+
+def save_z_vals(out_dir, z_values, clusters):
+    """The first two latent coordinates coloured by cluster (clustering_galaxy.py when z_dim == 2)."""
+    plt = _plt()
+    z = np.asarray(z_values)
+    fig = plt.figure(figsize=(10, 10))
+    cmap, norm = _rainbow_norm(plt)
+    plt.scatter(z[:, 0], z[:, 1], c=np.asarray(clusters), cmap=cmap, norm=norm, s=0.1)
+    path = os.path.join(out_dir, 'z_vals.jpg')
+    plt.savefig(path)
+    plt.close(fig)
+    return path
+
+
+def save_histograms(out_dir, rot_pred, tr_pred):
+    """The three histograms of clustering_particles.py: predicted rotation, x and y translation."""
+    plt = _plt()
+    rot, tr = np.asarray(rot_pred), np.asarray(tr_pred)
+    paths = []
+    for values, label, name in ((rot.reshape(rot.shape[0], -1), 'predicted rotation angles', 'predicted_rotation_vals.jpg'),
+                                (tr[:, 0], 'predicted translation values for x', 'predicted_translation_x_vals.jpg'),
+                                (tr[:, 1], 'predicted translation values for y', 'predicted_translation_y_vals.jpg')):
+        fig = plt.figure(figsize=(10, 10))
+        plt.hist(values)
+        plt.xlabel(label)
+        plt.ylabel('samples')
+        paths.append(os.path.join(out_dir, name))
+        plt.savefig(paths[-1])
+        plt.close(fig)
+    return paths
