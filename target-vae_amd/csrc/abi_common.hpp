@@ -1,6 +1,9 @@
 // Host-side helpers shared by the translation units of libtvae_hip.so (one .hip file per kernel family, compiled in
-// parallel; every __global__ function in the kernel headers has internal linkage, so each unit carries exactly the
-// kernels it launches).  The library keeps NO process-wide state: the arithmetic a call runs in is chosen by WHICH
+// parallel).  Every __global__ function in the kernel headers has internal linkage: a template kernel is emitted where it is
+// instantiated, a non-template one by EVERY unit that sees its definition -- so those sit in headers that one unit alone
+// includes, and a kernel that several units launch has a TVAE_INTERNAL launcher in the unit that owns it.  Every kernel is thus
+// built once (tests/test_host_cpu.py: test_every_kernel_is_built_once).
+// The library keeps NO process-wide state: the arithmetic a call runs in is chosen by WHICH
 // entry point the caller invokes (tvae_linear_fwd vs tvae_linear_fwd_x6, ...), never by a global mode.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -55,5 +58,33 @@ static inline ConvGeom make_geom(int B, int Cin, int n, int ksz, int pad, int R)
 }
 
 static const size_t X6_LDS_MAX = 160 * 1024;       // whole LDS of a CU (one workgroup per CU by design)
+
+// splitk_finalize_kernel (compiled in abi_linear_f32.hip alone) over the M x N outputs of `splits` slabs; the launch's error
+TVAE_INTERNAL int splitk_finalize(const float* ws, int splits, int M, int N, const Epilogue& ep, hipStream_t stream);
+
+// Host-side launcher.  `splits_wanted` <= 1 means no split-K.  `ws_floats` is the capacity of ws.
+template <class AL, class BL>
+static hipError_t launch_gemm(AL al, BL bl, const Epilogue& ep, int M, int N, int K, int splits_wanted,
+                              float* ws, long ws_floats, hipStream_t stream) {
+    if (M <= 0 || N <= 0) return hipSuccess;
+    const int tilesM = cdiv(M, BM), tilesN = cdiv(N, BN);
+    int splits = splits_wanted < 1 ? 1 : splits_wanted;
+    if (splits > 1) {
+        const long per = (long)M * N;
+        const long cap = ws ? ws_floats / per : 0;
+        if (cap < 2) splits = 1; else if (splits > cap) splits = (int)cap;
+        if (splits > 65535) splits = 65535;
+    }
+    int kchunk = cdiv(cdiv(K > 0 ? K : 1, splits), BK) * BK;
+    splits = cdiv(K > 0 ? K : 1, kchunk);
+    const TileMap tm{tilesM, tilesN, splits};
+    float* wsp = splits > 1 ? ws : nullptr;
+    hipLaunchKernelGGL((gemm_f32_kernel<AL, BL>), dim3(tm.grid()), dim3(GEMM_THREADS), 0, stream, al, bl, ep, M, N, K,
+                       kchunk, wsp, tm);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (splits > 1) e = (hipError_t)splitk_finalize(ws, splits, M, N, ep, stream);
+    return e;
+}
 
 }  // namespace tvae

@@ -119,14 +119,7 @@ int tvae_conv1_wgrad(const float* y, const float* dpre, float* dbank, float* ws,
                                tilesN, rows, sp, tilesM * sp);
         }
         TVAE_CHECK_LAUNCH();
-        if (sp > 1) {
-            int blocks = cdiv(per, 64);
-            if (blocks > 16384) blocks = 16384;
-            hipLaunchKernelGGL(splitk_finalize_kernel, dim3(blocks), dim3(256), 0, S(stream), (const float*)ws, sp, M, N,
-                               ep);
-            TVAE_CHECK_LAUNCH();
-        }
-        return 0;
+        return sp > 1 ? splitk_finalize(ws, sp, M, N, ep, S(stream)) : 0;
     }
     LoadConvDY al{dpre, (long)B * R * g.P, M, R, g.P};
     LoadConvPatchWgrad bl{y, g, N};

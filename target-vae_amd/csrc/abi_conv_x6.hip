@@ -129,11 +129,7 @@ int tvae_conv1_wgrad_x6(const float* y, const void* d3, float* dbank, float* ws,
     TVAE_CHECK_LAUNCH();
     Epilogue ep;
     ep.C = dbank; ep.ldc = N;
-    int blocks = cdiv(per, 64);
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(splitk_finalize_kernel, dim3(blocks), dim3(256), 0, S(stream), (const float*)ws, sp, M, N, ep);
-    TVAE_CHECK_LAUNCH();
-    return 0;
+    return splitk_finalize(ws, sp, M, N, ep, S(stream));
 }
 
 }  // extern "C"

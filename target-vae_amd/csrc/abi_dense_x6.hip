@@ -1,11 +1,52 @@
 // libtvae_hip.so: forward / data-gradient GEMM of the wide dense layers on the bf16 matrix pipe with exactly split
-// operands (dense_x6_kernels.hpp: dense_x6_kernel; its three operand variants are compiled in abi_dense_x6_v{0,1,2}.hip),
-// plus the weight pre-pass.
+// operands (dense_x6_kernels.hpp: dense_x6_kernel; its instances are listed in dense_x6_instances.def and compiled one object
+// each from dense_x6_instance.hip), plus the weight pre-pass (dense_prepass_kernels.hpp).
 #include "abi_dense_x6.hpp"
+#include "dense_prepass_kernels.hpp"
 
 using namespace tvae;
 
+namespace {
+// the launcher of every listed instance, looked up by (xv, epi, parts); a triple that is not listed is an invalid value
+struct Dx6Instance {
+    int xv, epi, parts;
+    int (*launch)(TVAE_DX6_LAUNCH_ARGS);
+};
+const Dx6Instance DX6_INSTANCES[] = {
+#define TVAE_DX6(XV_, E_, NP_) {XV_, E_, NP_, dense_x6_launch<XV_, E_, NP_>},
+#include "dense_x6_instances.def"
+#undef TVAE_DX6
+};
+int dense_x6_dispatch(int xv, int epi, int parts, TVAE_DX6_LAUNCH_ARGS) {
+    for (const Dx6Instance& i : DX6_INSTANCES)
+        if (i.xv == xv && i.epi == epi && i.parts == parts)
+            return i.launch(a3, X, ldx, ep, M, Mpad, N, K, K8pad, tm, bt, cd, it, vg, va, st, hs);
+    return (int)hipErrorInvalidValue;
+}
+}  // namespace
+
 namespace tvae {
+int h3_zero_slots(float* p, int n, int threads, hipStream_t st) {
+    hipLaunchKernelGGL(h3_zero_slots_kernel, dim3(1), dim3(threads), 0, st, p, n);
+    return (int)hipGetLastError();
+}
+int dense_split2h(const float* W, long ldw, uint4* a3, int rows, int Rpad, int K, int K8pad, int transpose, const float* scale,
+                  const float* rowmax, hipStream_t st) {
+    if (!transpose && K8pad <= 48)
+        hipLaunchKernelGGL(dense_split2h_rows_kernel, dim3(Rpad / 32), dim3(256), (size_t)32 * K8pad * 32, st, W, ldw, a3, rows,
+                           Rpad, K, K8pad, scale, rowmax);
+    else
+        hipLaunchKernelGGL(dense_split2h_kernel, dim3(grid1d((long)K8pad * Rpad, 256)), dim3(256), 0, st, W, ldw, a3, rows, Rpad,
+                           K, K8pad, transpose, scale, rowmax);
+    return (int)hipGetLastError();
+}
+int dec_l0_bound(const float* xr, int N, const float* wc, const float* bc, const float* lb, long nlb, int K, float* slots,
+                 hipStream_t st) {
+    hipLaunchKernelGGL(dec_l0_bound_kernel, dim3(grid1d(N / 2, 256, 512)), dim3(256), 0, st, xr, 2L * N, wc, bc, lb, nlb, K,
+                       slots);
+    return (int)hipGetLastError();
+}
+
 int dense_x6_batched(const void* w3, const float* X, long ldx, const Epilogue& ep, int rows_per_problem, int rows_total,
                      int N, int K, const TileMap& tm, const DenseBatch& bt, int parts, hipStream_t st, H3Scale hs) {
     const int Rpad = x6_round_up(rows_total, DX6_ROWS), K8pad = dense_k8pad(K);
@@ -16,17 +57,11 @@ int dense_x6_batched(const void* w3, const float* X, long ldx, const Epilogue& e
     // generic one took ~40 % of these launches)
     const bool lean = !ep.bias && !ep.res && !ep.aux && ep.act == ACT_NONE && ep.mask == ACT_NONE && ep.ctile > 0 && ep.C &&
                       !ep.accumulate && !ep.amax_out && rows_per_problem % DX6_ROWS == 0 && ep.ldc * 8 * 4 < (1L << 31);
-    if (lean)
-        return TVAE_DX6_DISPATCH_E(0, 4, parts, (const uint4*)w3, X, ldx, ep, rows_per_problem, Rpad, N, K, K8pad, tm, bt,
-                                   ColDot{nullptr, nullptr, nullptr},
-                                   InTail{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1},
-                                   VirtGrad{nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0},
-                                   VirtAct{nullptr, nullptr, nullptr, nullptr, 1, 0, 0.f}, st, hs);
-    return TVAE_DX6_DISPATCH(0, parts, (const uint4*)w3, X, ldx, ep, rows_per_problem, Rpad, N, K, K8pad, tm, bt,
+    return dense_x6_dispatch(0, lean ? 4 : 0, parts, (const uint4*)w3, X, ldx, ep, rows_per_problem, Rpad, N, K, K8pad, tm, bt,
                              ColDot{nullptr, nullptr, nullptr},
                              InTail{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1},
-                             VirtGrad{nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0}, VirtAct{nullptr, nullptr, nullptr, nullptr, 1, 0, 0.f}, st,
-                             hs);
+                             VirtGrad{nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0},
+                             VirtAct{nullptr, nullptr, nullptr, nullptr, 1, 0, 0.f}, st, hs);
 }
 int dense_x6_batched4(const void* w3, const float* X, long ldx, const Epilogue& ep, int rows_per_problem, int rows_total,
                       int N, int K, const TileMap& tm, const DenseBatch& bt, int parts, hipStream_t st, H3Scale hs, bool out_bf16) {
@@ -135,17 +170,13 @@ static int dense_split(const float* W, long ldw, void* a3, long a3_bytes, int ro
         else             // row-major operand: one wave per row, lanes along k
             hipLaunchKernelGGL(dense_rowmax_rows_kernel, dim3(Rpad / 4), dim3(256), 0, S(stream), W, ldw, rows, Rpad, K, scale, tr);
         TVAE_CHECK_LAUNCH();
-        if (!transpose && K8pad <= 48)                   // both sides coalesced through LDS (32 rows per workgroup, <= 48 KB)
-            hipLaunchKernelGGL(dense_split2h_rows_kernel, dim3(Rpad / 32), dim3(256), (size_t)32 * K8pad * 32, S(stream), W, ldw,
-                               (uint4*)a3, rows, Rpad, K, K8pad, scale, (const float*)tr);
-        else
-            hipLaunchKernelGGL(dense_split2h_kernel, dim3(grid1d(total, 256)), dim3(256), 0, S(stream), W, ldw, (uint4*)a3, rows,
-                               Rpad, K, K8pad, transpose, scale, (const float*)tr);
+        const int rc = dense_split2h(W, ldw, (uint4*)a3, rows, Rpad, K, K8pad, transpose, scale, tr, S(stream));
+        if (rc) return rc;
     } else {
         hipLaunchKernelGGL(dense_split3_kernel, dim3(grid1d(total, 256)), dim3(256), 0, S(stream), W, ldw, (uint4*)a3, rows,
                            Rpad, K, K8pad, transpose, scale);
+        TVAE_CHECK_LAUNCH();
     }
-    TVAE_CHECK_LAUNCH();
     if (rowsum) {
         hipLaunchKernelGGL(dense_rowsum_kernel, dim3((rows + 63) / 64), dim3(1024), 0, S(stream), W, ldw, rows, K, transpose,
                            scale, rowsum);
@@ -181,12 +212,11 @@ static int launch_dense_x6(const void* a3, const float* X, long ldx, const Epilo
         hs.a_rows = 1;
         if (va.xr) {
             float* bw = tr + Rpad;                       // bound words of the recomputed operand: [4 + K]
-            hipLaunchKernelGGL(h3_zero_slots_kernel, dim3(1), dim3(256), 0, st, bw, 4 + K);
-            TVAE_CHECK_LAUNCH();
+            int rc = h3_zero_slots(bw, 4 + K, 256, st);
+            if (rc) return rc;
             const long nlb = va.lb ? (long)(N / va.Np) * K : 0;
-            hipLaunchKernelGGL(dec_l0_bound_kernel, dim3(grid1d(N / 2, 256, 512)), dim3(256), 0, st, va.xr, 2L * N, va.wc,
-                               va.bc, va.lb, nlb, K, bw);
-            TVAE_CHECK_LAUNCH();
+            rc = dec_l0_bound(va.xr, N, va.wc, va.bc, va.lb, nlb, K, bw, st);
+            if (rc) return rc;
             hs.amax_x = bw;
         } else if (x_amax && !vg.wo && !vg.csum) {
             // an operand streamed from memory: the caller supplies max |X| or an upper bound of it (one device word) -- e.g.
@@ -207,35 +237,35 @@ static int launch_dense_x6(const void* a3, const float* X, long ldx, const Epilo
         // the hot shape has its own lean instance: ONE full row tile, result not stored, fused first-layer backward with the
         // recomputed LeakyReLU mask, nothing else switched on
         if (rows == DX6_ROWS && !ep.C && it.xr && it.bc && !ep.res && ep.mask == ACT_LRELU && !cd.w && !cd.bits)
-            return TVAE_DX6_DISPATCH_E(5, 2, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+            return dense_x6_dispatch(5, 2, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
         // ... its result stored under the LeakyReLU mask of a saved activation (Fourier decoders), whole row tiles: lean store
         if (rows % DX6_ROWS == 0 && ep.C && !it.xr && !ep.res && ep.mask == ACT_LRELU && ep.aux && !cd.w && !cd.bits && !ep.ctile &&
             ep.ldc * 8 * 4 < (1L << 31) && ep.ldaux * 8 * 4 < (1L << 31))
-            return TVAE_DX6_DISPATCH_E(5, 3, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-        return TVAE_DX6_DISPATCH(5, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+            return dense_x6_dispatch(5, 3, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+        return dense_x6_dispatch(5, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
     }
     if (vg.csum && vg.rpart) {
         if (K > DX6_ROWS) return (int)hipErrorInvalidValue;              // the row sums live in one 512-row LDS table
-        return TVAE_DX6_DISPATCH(4, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+        return dense_x6_dispatch(4, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
     }
-    if (vg.csum) return TVAE_DX6_DISPATCH(3, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+    if (vg.csum) return dense_x6_dispatch(3, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
     // forward of the decoder's last hidden layer with its activation not stored: lean instance (one full row tile)
     // (cd.bits == nullptr with no output either: the inference-mode forward -- only the fused column dot leaves the launch)
     if (va.xr && rows == DX6_ROWS && !ep.C && cd.w && !it.xr && !ep.res && ep.mask == ACT_NONE && ep.act == ACT_LRELU)
-        return TVAE_DX6_DISPATCH_E(2, 1, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    if (va.xr) return TVAE_DX6_DISPATCH(2, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+        return dense_x6_dispatch(2, 1, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+    if (va.xr) return dense_x6_dispatch(2, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
     // the same layer with its input read from memory (28 x 28 shapes, Fourier decoders): lean instance of the plain operand
     if (!vg.wo && X && rows == DX6_ROWS && N % 128 == 0 && !ep.C && cd.w && !it.xr && !ep.res && ep.mask == ACT_NONE &&
         ep.act == ACT_LRELU)
-        return TVAE_DX6_DISPATCH_E(0, 1, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    if (vg.wo) return TVAE_DX6_DISPATCH(1, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+        return dense_x6_dispatch(0, 1, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+    if (vg.wo) return dense_x6_dispatch(1, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
     // plain hidden layer that stores its output (round 6): whole 512-row tiles, bias + LeakyReLU | none (forward) or the
     // LeakyReLU mask of the saved activation (data gradient), nothing fused behind it: lean store epilogue
     if (X && rows % DX6_ROWS == 0 && ep.C && !ep.res && !cd.w && !cd.bits && !it.xr && !ep.ctile && !ep.accumulate && !ep.gbias &&
         ((ep.mask == ACT_NONE && (ep.act == ACT_LRELU || ep.act == ACT_NONE)) || (ep.mask == ACT_LRELU && ep.aux && ep.act == ACT_NONE && !ep.bias)) &&
         ep.ldc * 8 * 4 < (1L << 31) && ep.ldaux * 8 * 4 < (1L << 31))
-        return TVAE_DX6_DISPATCH_E(0, 3, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    return TVAE_DX6_DISPATCH(0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+        return dense_x6_dispatch(0, 3, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+    return dense_x6_dispatch(0, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
 }
 int tvae_linear_fwd_x6(const void* w3, const float* X, const float* bias, const float* res, float* Y, int M, int N,
                        int K, long ldx, long ldy, int act, float slope, const float* col_w, const float* col_b,

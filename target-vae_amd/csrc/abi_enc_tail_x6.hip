@@ -1,7 +1,7 @@
 // libtvae_hip.so: the encoder tail (conv2 1x1x1 + the stacked head projection) fused per direction on the bf16 matrix
 // pipe with exactly split operands (enc_tail_x6_kernels.hpp).
 #include "abi_dense_x6.hpp"
-#include "enc_tail_x6_kernels.hpp"
+#include "enc_tail_wgrad_kernels.hpp"
 
 using namespace tvae;
 
@@ -122,8 +122,8 @@ int tvae_enc_tail_wgrad_x6(const float* A1, long lda, const float* dheads, long 
                            nh, (const uint4*)bits_h, Wh, ws, N, slope, amax_a1, (const float*)slots);
     } else if (parts == 2) {
         // max |dheads|: one pass over nh x N floats (62 MB at the bench shape)
-        hipLaunchKernelGGL(h3_zero_slots_kernel, dim3(1), dim3(64), 0, S(stream), slots, 1);
-        TVAE_CHECK_LAUNCH();
+        const int rc = h3_zero_slots(slots, 1, 64, S(stream));
+        if (rc) return rc;
         hipLaunchKernelGGL(h3_absmax_rows_kernel, dim3(grid1d(N / 16 + 1, 256, 96), nh), dim3(256), 0, S(stream), dheads, ldd, N,
                            slots);
         TVAE_CHECK_LAUNCH();

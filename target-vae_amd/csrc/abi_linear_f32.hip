@@ -1,8 +1,16 @@
 // libtvae_hip.so, dense layers on the fp32 matrix pipe (gemm_f32_mfma.hpp): the 128-wide encoder 1x1x1
 // layers in every arithmetic, and every dense layer when the caller asks for exact fp32 products.
 #include "abi_common.hpp"
+#include "gemm_f32_kernels.hpp"
 
 using namespace tvae;
+
+int tvae::splitk_finalize(const float* ws, int splits, int M, int N, const Epilogue& ep, hipStream_t stream) {
+    int blocks = cdiv((long)M * N, 64);
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(splitk_finalize_kernel, dim3(blocks), dim3(256), 0, stream, ws, splits, M, N, ep);
+    return (int)hipGetLastError();
+}
 
 // the float4 epilogue needs plain row-major C and 16-B aligned C / residual / aux rows
 static inline int vec_epilogue_ok(const Epilogue& ep) {

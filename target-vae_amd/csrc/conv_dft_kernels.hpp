@@ -20,8 +20,8 @@
 // Single input channel (Cin = 1: MNIST / particle configurations).  Twiddles: sincospi of exactly reduced angles.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "small_kernels.hpp"
-#include "conv_x6_kernels.hpp"
+#include "small_device.hpp"
+#include "conv_x6_device.hpp"
 
 namespace tvae {
 

@@ -641,6 +641,37 @@ def test_hand_counted_kernels_use_no_scratch_and_no_packed_fp32():
     assert npk == 0, npk
 
 
+def test_every_kernel_is_built_once():
+    """A non-template `static __global__` function is emitted by every translation unit that sees its definition, and a template
+    kernel by every unit that instantiates it: the kernel headers are split so that each kernel reaches exactly ONE unit, and
+    kernels that several units launch go through a launcher in the unit that owns them (csrc/abi_common.hpp).  Gate on the BUILT
+    libraries: every kernel name of the notes metadata occurs in exactly one of the embedded code objects.  Names and counts
+    only."""
+    import re
+    import subprocess
+    import tempfile
+    from tvae import _cluster_lib, _lib
+    readelf = '/opt/rocm/lib/llvm/bin/llvm-readelf'
+    if not (os.path.exists(readelf) and os.path.exists(_lib.LIB_PATH) and os.path.exists(_cluster_lib.LIB_PATH)):
+        import pytest
+        pytest.skip('needs the ROCm llvm tools and the built libraries')
+    allowed = set()          # names that may be built more than once: none
+    for path, least in ((_lib.LIB_PATH, 200), (_cluster_lib.LIB_PATH, 10)):
+        data = open(path, 'rb').read()
+        offs = [m.start() for m in re.finditer(b'\x7fELF\x02\x01\x01\x40', data)]
+        count = {}
+        for o, end in zip(offs, offs[1:] + [len(data)]):
+            with tempfile.NamedTemporaryFile(suffix='.co') as f:
+                f.write(data[o:end])
+                f.flush()
+                notes = subprocess.run([readelf, '--notes', f.name], capture_output=True, text=True).stdout
+            for n in set(re.findall(r'\.symbol:\s+(\S+)\.kd\b', notes)):      # (.name is also what arguments have)
+                count[n] = count.get(n, 0) + 1
+        assert len(count) >= least, (path, len(count))      # (the walk found the kernels at all)
+        dup = {n: c for n, c in count.items() if c != 1 and n not in allowed}
+        assert not dup, (path, dup)
+
+
 # ---- frequency-domain lifting convolution: which kernel instance every step takes (tvae_conv1_dft_route) -----------------
 # Capacities of the instances, written from their header comments (csrc/conv_dft_kernels.hpp, conv_dft_h3_kernels.hpp,
 # abi_dense_x6.hpp, dense_x6_kernels.hpp) and NOT from the plan that routes to them.  Frame: L (tvae_conv1_dft_frame),
