@@ -1,5 +1,5 @@
-/* C ABI of libtvae_cluster.so: batched Lloyd k-means, Ward linkage and exact t-SNE on the GPU (gfx950), the hot paths
- * of clustering_*.py.
+/* C ABI of libtvae_cluster.so: batched Lloyd k-means, Ward linkage, exact t-SNE and aligned class averages on the GPU
+ * (gfx950), the hot paths of clustering_*.py and class_averages.py.
  *
  * Same conventions as tvae_hip.h: raw device pointers and sizes, the stream as void*, `int` return = hipError_t.  The
  * entry points never allocate, free or synchronise and keep no process-wide state; the workspace is the caller's,
@@ -27,7 +27,7 @@ typedef void* tvae_stream_t;
 
 #define TVAE_KMEANS_MAX_RESTARTS 65535
 
-/* Still 1: the Ward and t-SNE entry points below were ADDED, no existing prototype or meaning changed. */
+/* Still 1: the Ward, t-SNE and alignment entry points below were ADDED, no existing prototype or meaning changed. */
 int tvae_cluster_abi_version(void);          /* == 1 */
 
 /* floats of workspace for one assign / update pair: per restart G x (k*d sums, k counts, 1 changed count, 1 sum of
@@ -136,6 +136,49 @@ int tvae_tsne_step(const int* rowptr, const int* col, const float* val, long nnz
  * ws holds tvae_tsne_groups(N) fp64 words. */
 int tvae_tsne_kl(const int* rowptr, const int* col, const float* val, long nnz, const float* Yt, long ldy,
                  const double* Z, double* kl, double* ws, long ws_doubles, int N, tvae_stream_t stream);
+
+/* ---- Aligned images and aligned 2-D class averages of a clustered stack ------------------------------------------------
+ *
+ * Y[N][C][n][n] (square images, all channels of an image share one pose), theta[N] and dx[N][2] as the encoder predicts
+ * them, t_scale the factor between dx and coordinate units (1 where the translation was inferred by attention, 0.1 for
+ * the unimodal encoder, the reference's dx_scale).  The model's convention: coordinates linspace(-1, 1, n) along columns
+ * and linspace(1, -1, n) along rows, a pixel at x shows canonical content at u = (x - t dx) R(theta).  The aligned image
+ * A_i at the canonical grid point u = (u0, u1) therefore reads image i at
+ *     x = (u0 c + u1 s + t dx0,  -u0 s + u1 c + t dx1),  c = cos theta_i, s = sin theta_i (accurate cosf / sinf),
+ *     col = (x0 + 1) (n - 1) / 2,  row = (1 - x1) (n - 1) / 2,
+ * bilinear over the taps floor and floor + 1 per axis.  A tap outside [0, n - 1] is 0 (zero border: the sample is a
+ * continuous function of the position); a position that is not inside (-1, n) on both axes gives exactly 0, which
+ * covers NaN, +-inf and huge poses (the range is tested before any float -> int conversion).
+ *
+ * Class averages: order[N] holds image indices grouped by class, seg[K + 1] the class boundaries in `order` (both device
+ * pointers; class k = order[seg[k] .. seg[k + 1])), avg[k] = (sum of A_i over the members) / (number of members).
+ * Entries of `order` outside [0, N) are skipped, never dereferenced, and do not count; a class without members gives
+ * zeros.  seg is never read on the host; on the device it is replaced by min(max(0, seg[0], ..., seg[k]), N), which
+ * leaves a monotone seg within [0, N] as it is and makes any other one monotone: nothing is followed out of bounds.
+ * The aligned stack is never written: a class is cut into chunks of tvae_class_average_chunk consecutive members, counted
+ * from the class's own first member; the fp32 sum of a chunk in ascending position goes to the workspace and a second
+ * launch adds the chunks of a class in ascending order and divides.
+ * No float atomics: every output is a pure function of the inputs, bitwise reproducible.  The split of a class into chunks
+ * depends on (seg, N, K, C, n) only, and avg[k] only on class k's ordered member list and those members' images and
+ * poses: not on the other classes, not on K.
+ *
+ * Supported: 1 <= N <= 2^24, 1 <= C <= 1024, 2 <= n <= 1024, 1 <= K <= 65535, fewer than 2^31 workgroups of 256 pixels
+ * (N C ceil(n n / 256), and (N / chunk + K) C ceil(n n / 256) for the averages); anything else returns
+ * hipErrorInvalidValue (1) and writes nothing. */
+
+/* floats of workspace of tvae_class_average: the cleaned seg and one member count per chunk slot (int32 words) and the
+ * partial sums of N / chunk + K slots.  0 for unsupported arguments. */
+long tvae_class_average_ws_floats(int N, int K, int C, int n);
+/* members per chunk (a constant of the build, 32).  0 for unsupported arguments. */
+int tvae_class_average_chunk(int N, int K, int C, int n);
+
+/* out[N][C][n][n] = A_i; out must not be Y. */
+int tvae_align_stack(const float* Y, const float* theta, const float* dx, float* out, int N, int C, int n,
+                     float t_scale, tvae_stream_t stream);
+
+/* avg[K][C][n][n]; ws holds tvae_class_average_ws_floats(N, K, C, n) floats. */
+int tvae_class_average(const float* Y, const float* theta, const float* dx, const int* order, const int* seg, float* avg,
+                       float* ws, long ws_floats, int N, int C, int n, int K, float t_scale, tvae_stream_t stream);
 
 #ifdef __cplusplus
 }

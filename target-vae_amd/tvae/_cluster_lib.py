@@ -35,6 +35,9 @@ SIGNATURES = {
     # exaggeration, momentum, learning_rate
     'tvae_tsne_step': 'ppplpppppppplifff',
     'tvae_tsne_kl': 'ppplplpppli',            # rowptr, col, val, nnz, Yt, ldy, Z, kl, ws (fp64 all three), ws_doubles, N
+    'tvae_align_stack': 'ppppiiif',           # Y, theta, dx, out, N, C, n, t_scale
+    # Y, theta, dx, order (int32), seg (int32), avg, ws, ws_floats, N, C, n, K, t_scale
+    'tvae_class_average': 'pppppppliiiif',
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
@@ -45,6 +48,8 @@ QUERIES = {
     'tvae_ward_merge_ws_ints': ('ii', 'l'),
     'tvae_tsne_groups': ('i', 'i'),
     'tvae_tsne_repulsion_ws_floats': ('i', 'l'),
+    'tvae_class_average_ws_floats': ('iiii', 'l'),
+    'tvae_class_average_chunk': ('iiii', 'i'),
 }
 
 _cl = None

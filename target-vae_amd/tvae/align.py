@@ -1,0 +1,192 @@
+"""Aligned images and aligned 2-D class averages of a clustered stack on the GPU: the step after clustering_*.py, the
+picture at the top of the reference's README.  Every image is resampled into the canonical frame with the rotation and
+translation the encoder predicted for it, and the resampled images are averaged per cluster.
+
+The pose convention is the model's (train_*.py: eval_minibatch; coordinates tvae.tables.image_coords): a pixel at
+coordinate x shows canonical content at u = (x - t dx) R(theta), so the aligned image at the grid point u reads its
+image at x = u R(theta)^T + t dx, bilinearly, with a zero border.  t is 1 where the translation was inferred by attention
+and 0.1 for --t-inf unimodal (the reference's dx_scale, which get_latent does not apply to the dx it returns):
+`translation_scale`.  include/tvae_cluster.h states the definition in full.
+
+The kernels are tvae_align_stack and tvae_class_average of libtvae_cluster.so.  The class averages are fused: the aligned
+stack is never written, the stack is read once, there are no float atomics and the result is bitwise reproducible;
+avg[k] depends on class k's members alone, not on the other classes or on the number of classes.  There is no CPU
+fallback for the kernels; `segments` is torch code that does not care where its tensors live.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import _cluster_lib as CL
+from ._lib import TvaeHipError
+
+MAX_IMAGES = 1 << 24
+MAX_CLUSTERS = 65535
+
+
+def translation_scale(t_inf: str) -> float:
+    """Factor between the dx a clustering run saves and coordinate units."""
+    if t_inf == 'attention':
+        return 1.0
+    if t_inf == 'unimodal':
+        return 0.1
+    raise ValueError(f"t_inf must be 'attention' or 'unimodal', got {t_inf!r}")
+
+
+def segments(labels, n_clusters):
+    """labels [N] (integers, any device) -> (order int32 [N], seg int32 [K + 1], counts int32 [K]): the image indices
+    grouped by class, ascending index within a class (a stable sort on the labels' device); class k is
+    order[seg[k]:seg[k + 1]].  Labels outside [0, K) go to no class: their indices sit behind seg[K]."""
+    lab = torch.as_tensor(labels)
+    if lab.dim() != 1 or lab.dtype.is_floating_point or lab.dtype == torch.bool:
+        raise TvaeHipError('segments: labels must be a one-dimensional integer array')
+    K = int(n_clusters)
+    if K < 1:
+        raise TvaeHipError(f'segments: n_clusters = {K} must be positive')
+    lab = lab.to(torch.int64)
+    key = torch.where((lab >= 0) & (lab < K), lab, torch.full_like(lab, K))
+    order = torch.sort(key, stable=True).indices
+    counts = torch.bincount(key, minlength=K + 1)[:K]
+    seg = torch.zeros(K + 1, dtype=torch.int64, device=lab.device)
+    seg[1:] = torch.cumsum(counts, 0)
+    return order.to(torch.int32), seg.to(torch.int32), counts.to(torch.int32)
+
+
+def _check_stack(images, theta, dx, what):
+    for nm, t in (('images', images), ('theta', theta), ('dx', dx)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise TvaeHipError(f'{what}: {nm} must be a contiguous CUDA fp32 tensor (no CPU fallback)')
+    if images.dim() != 4 or images.shape[-1] != images.shape[-2]:
+        raise TvaeHipError(f'{what}: images must be [N][C][n][n] (square), got {tuple(images.shape)}')
+    N, C, n, _ = images.shape
+    if not (1 <= N <= MAX_IMAGES and 1 <= C <= 1024 and 2 <= n <= 1024):
+        raise TvaeHipError(f'{what}: N={N}, C={C}, n={n} outside the supported range '
+                           '(1 <= N <= 2^24, 1 <= C <= 1024, 2 <= n <= 1024)')
+    if theta.numel() != N or theta.dim() > 2 or tuple(dx.shape) != (N, 2):
+        raise TvaeHipError(f'{what}: theta must hold N = {N} angles and dx must be [N][2], got {tuple(theta.shape)} '
+                           f'and {tuple(dx.shape)}')
+    if theta.device != images.device or dx.device != images.device:
+        raise TvaeHipError(f'{what}: images, theta and dx must live on one device')
+    return N, C, n
+
+
+def align_stack(images, theta, dx, t_scale=1.0):
+    """images [N][C][n][n], theta [N] or [N][1], dx [N][2] (CUDA fp32) -> the aligned images, same shape."""
+    N, C, n = _check_stack(images, theta, dx, 'align_stack')
+    out = torch.empty_like(images)
+    with torch.cuda.device(images.device):
+        CL.call('tvae_align_stack', images, theta.reshape(N), dx, out, N, C, n, float(t_scale))
+    return out
+
+
+def chunk_members(N, K, C, n) -> int:
+    """Members of a class per partial sum of tvae_class_average (0 for unsupported arguments)."""
+    return CL.query('tvae_class_average_chunk', N, K, C, n)
+
+
+def class_averages(images, theta, dx, labels, n_clusters=None, t_scale=1.0):
+    """-> (avg fp32 [K][C][n][n], counts int32 [K]) on the device of `images`: avg[k] is the mean of the aligned images
+    with label k (zeros for an empty class).  labels: [N] integers on any device or a numpy array; a label outside
+    [0, K) belongs to no class.  n_clusters None: the largest label + 1."""
+    N, C, n = _check_stack(images, theta, dx, 'class_averages')
+    lab = torch.as_tensor(labels)
+    if lab.dim() != 1 or lab.numel() != N:
+        raise TvaeHipError(f'class_averages: labels must hold N = {N} entries, got {tuple(lab.shape)}')
+    lab = lab.to(images.device)
+    K = int(n_clusters) if n_clusters is not None else int(lab.max()) + 1
+    if not 1 <= K <= MAX_CLUSTERS:
+        raise TvaeHipError(f'class_averages: n_clusters = {K} outside [1, {MAX_CLUSTERS}]')
+    order, seg, counts = segments(lab, K)
+    wsf = CL.query('tvae_class_average_ws_floats', N, K, C, n)
+    if wsf <= 0:
+        raise TvaeHipError(f'class_averages: N={N}, K={K}, C={C}, n={n} is more than one launch covers')
+    avg = torch.empty(K, C, n, n, dtype=torch.float32, device=images.device)
+    ws = torch.empty(wsf, dtype=torch.float32, device=images.device)
+    with torch.cuda.device(images.device):
+        CL.call('tvae_class_average', images, theta.reshape(N), dx, order, seg, avg, ws, wsf, N, C, n, K, float(t_scale))
+    return avg, counts
+
+
+def save_outputs(out_dir, avg, counts, particles=False):
+    """class_averages.npy ([K][C][n][n]) and class_counts.npy; class_averages.mrcs ([K * C][n][n]) for particles; the
+    montage class_averages.jpg when matplotlib is present (stderr says so when it is not)."""
+    from . import figures
+    avg, counts = np.asarray(avg, dtype=np.float32), np.asarray(counts)
+    np.save(os.path.join(out_dir, 'class_averages.npy'), avg)
+    np.save(os.path.join(out_dir, 'class_counts.npy'), counts)
+    if particles:
+        from src import mrc
+        with open(os.path.join(out_dir, 'class_averages.mrcs'), 'wb') as f:
+            mrc.write(f, avg.reshape(-1, avg.shape[-2], avg.shape[-1]))
+    try:
+        figures._plt()
+    except ImportError as e:
+        print('# matplotlib is not available ({}): class_averages.jpg is skipped'.format(e), file=sys.stderr)
+        return
+    figures.save_class_averages(out_dir, avg, counts)
+
+
+# ---- class_averages.py: the averages from the files a clustering run wrote ------------------------------------------------
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser('Aligned 2-D class averages of a clustered stack')
+    p.add_argument('--stack', required=True, help='the images (.npy, .mrc or .mrcs): [N][n][n] or [N][C][n][n]')
+    p.add_argument('--rotations', required=True, help='rotations.npy of the clustering run')
+    p.add_argument('--translations', required=True, help='translations.npy of the clustering run')
+    p.add_argument('--clusters', required=True, help='clusters.npy of the clustering run')
+    p.add_argument('--t-inf', default='attention', choices=['unimodal', 'attention'],
+                   help='translation inference of the run: chooses the scale of the translations (1 or 0.1)')
+    p.add_argument('--crop', default=0, type=int, help='central crop, as the clustering run applied it')
+    p.add_argument('--n-clusters', default=None, type=int, help='default: the largest label + 1')
+    p.add_argument('--out-dir', default='.', help='where class_averages.npy, class_counts.npy and the figure go')
+    p.add_argument('--write-aligned', action='store_true', help='also write the aligned images, aligned.npy')
+    p.add_argument('-d', '--device', type=int, default=0)
+    return p
+
+
+def load_stack(path, crop=0):
+    """-> float32 [N][C][n][m] on the host."""
+    if path.endswith('mrc') or path.endswith('mrcs'):
+        from src import mrc
+        a = np.asarray(mrc.open_stack(path)[0], dtype=np.float32)
+    else:
+        a = np.asarray(np.load(path), dtype=np.float32)
+    if a.ndim == 3:
+        a = a[:, None]
+    if a.ndim != 4:
+        raise SystemExit(f'--stack must hold [N][n][n] or [N][C][n][n], got {a.shape}')
+    if crop > 0:
+        si, sj = (a.shape[-2] - crop) // 2, (a.shape[-1] - crop) // 2
+        a = a[..., si:si + crop, sj:sj + crop]
+    return np.ascontiguousarray(a)
+
+
+def run(argv=None):
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available() or args.device == -1:
+        raise SystemExit('the MI355X build has no CPU compute path')
+    torch.cuda.set_device(args.device)
+    device = torch.device('cuda', args.device)
+    stack = load_stack(args.stack, args.crop)
+    particles = args.stack.endswith('mrc') or args.stack.endswith('mrcs')
+    images = torch.from_numpy(stack).to(device)
+    theta = torch.from_numpy(np.asarray(np.load(args.rotations), dtype=np.float32).reshape(-1)).to(device)
+    dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
+    clusters = np.asarray(np.load(args.clusters)).reshape(-1)
+    t = translation_scale(args.t_inf)
+    try:
+        avg, counts = class_averages(images, theta, dx, clusters, args.n_clusters, t)
+        aligned = align_stack(images, theta, dx, t) if args.write_aligned else None
+    except TvaeHipError as e:
+        raise SystemExit(str(e)) from e
+    os.makedirs(args.out_dir, exist_ok=True)
+    save_outputs(args.out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles)
+    if aligned is not None:
+        np.save(os.path.join(args.out_dir, 'aligned.npy'), aligned.cpu().numpy())
+    print('# class averages of {} images in {} classes: {}'.format(images.shape[0], avg.shape[0], args.out_dir),
+          file=sys.stderr)
+    return avg, counts

@@ -14,6 +14,11 @@ names -- confusion_matrix.jpg (mnist, dsprites), z_vals.jpg (galaxy with --z-dim
 the reference drops the path separator there), the three predicted_*_vals.jpg histograms (particles).  Without
 matplotlib tsne.npy is still written and stderr says that the figures were skipped.  With the switch unset a run is
 what it was before the figures existed, the line on stderr that says so included.
+
+TVAE_CLASS_AVERAGES=1 adds the step after the reference scripts: every image resampled into the canonical frame with its
+predicted rotation and translation and averaged per cluster on the GPU (tvae.align) -- class_averages.npy
+([K][C][n][n]), class_counts.npy, class_averages.mrcs for particles and the montage class_averages.jpg when matplotlib is
+present.  class_averages.py computes the same from the saved .npy files alone.  Unset, nothing changes.
 """
 from __future__ import annotations
 
@@ -164,6 +169,19 @@ def _figures(kind, args, out_dir, z_values, rot_pred, tr_pred, clusters, y_label
         figures.save_histograms(out_dir, rot_pred.cpu().numpy(), tr_pred.cpu().numpy())
 
 
+def _class_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters):
+    """TVAE_CLASS_AVERAGES=1: the aligned class averages of the run (tvae.align), from the preprocessed images the encoder
+    saw and the run's own rotations, translations and clusters."""
+    from . import align
+    print('# saving aligned class averages ... ', file=sys.stderr)
+    if images.shape[-1] != images.shape[-2]:
+        raise SystemExit('TVAE_CLASS_AVERAGES=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
+    y = images.to(device).float().contiguous()
+    avg, counts = align.class_averages(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(),
+                                       np.asarray(clusters), args.n_clusters, align.translation_scale(args.t_inf))
+    align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles=kind == 'particles')
+
+
 def run(kind: str, argv=None):
     args = build_parser(kind).parse_args(argv)
     from src import models  # noqa: F401     (whole-module checkpoints unpickle as src.models.*)
@@ -224,6 +242,8 @@ def run(kind: str, argv=None):
         _figures(kind, args, out_dir, z_values, rot_pred, tr_pred, clusters, y_labels, mapping)
     else:
         print('# the t-SNE, confusion-matrix and histogram figures of the reference are not built', file=sys.stderr)
+    if os.environ.get('TVAE_CLASS_AVERAGES', '') == '1':
+        _class_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
 
     np.save(os.path.join(out_dir, 'latents.npy'), z_values.cpu().numpy())
     np.save(os.path.join(out_dir, 'rotations.npy'), rot_pred.cpu().numpy())

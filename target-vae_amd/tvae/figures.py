@@ -113,3 +113,29 @@ def save_histograms(out_dir, rot_pred, tr_pred):
         plt.savefig(paths[-1])
         plt.close(fig)
     return paths
+
+
+def save_class_averages(out_dir, averages, counts):
+    """Montage of the aligned class averages [K][C][n][n]: one grey panel per class (three channels as RGB scaled to the
+    panel's own range, any other number averaged over the channels), titled with the class and its number of members."""
+    plt = _plt()
+    avg, counts = np.asarray(averages, dtype=np.float64), np.asarray(counts).reshape(-1)
+    K = avg.shape[0]
+    cols = min(K, 10)
+    rows = (K + cols - 1) // cols
+    fig, axes = plt.subplots(rows, cols, figsize=(2 * cols, 2.3 * rows), squeeze=False)
+    for k, ax in enumerate(axes.ravel()):
+        ax.axis('off')
+        if k >= K:
+            continue
+        a = avg[k]
+        if a.shape[0] == 3:
+            lo, hi = a.min(), a.max()
+            ax.imshow(np.moveaxis((a - lo) / (hi - lo) if hi > lo else np.zeros_like(a), 0, -1))
+        else:
+            ax.imshow(a.mean(0), cmap='gray')
+        ax.set_title('{}: {}'.format(k, int(counts[k])), fontsize=9)
+    path = os.path.join(out_dir, 'class_averages.jpg')
+    plt.savefig(path, bbox_inches='tight')
+    plt.close(fig)
+    return path
