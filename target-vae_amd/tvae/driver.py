@@ -84,7 +84,7 @@ def build_parser(kind: str) -> argparse.ArgumentParser:
                    help='train on N synthetic images of the dataset shape instead of loading files')
     # Round 6: ON BY DEFAULT wherever it applies (the attention branch without CTF filters / mask: every BASELINE configuration).
     # The minibatch shape of a run is fixed, the replay is bitwise the eager result
-    # (tests/test_driver_gpu.py::test_graphed_step_bitwise_equals_eager) and the ~70 launches of a step are most of its cost at
+    # on every capturable route (tests/test_graph_gpu.py) and the ~70 launches of a step are most of its cost at
     # small per-GPU batches (12 images: 1.68 -> 1.43 ms).  --graph insists (error where it cannot apply), --no-graph runs eagerly.
     p.add_argument('--graph', action='store_true',
                    help='insist on replaying a captured hipGraph of forward + backward for full-size minibatches '
@@ -210,6 +210,13 @@ def _load_ctf(args, n_train, n_test, n, shard=None):
     return torch.from_numpy(ftr).float().unsqueeze(1), torch.from_numpy(fte).float().unsqueeze(1)
 
 
+def graph_supported(t_inf: str, r_inf: str, has_ctf: bool, mask_radius) -> bool:
+    """Whether the training step of a run can be captured into a hipGraph (tvae/graph.py): the TARGET-VAE branch (attention
+    over translations, attention over rotations with or without offsets) without per-image CTF filters and without a
+    circular mask.  `mask_radius` is None for the datasets that have no mask at all, 0 for particles without one."""
+    return (t_inf == 'attention' and r_inf != 'unimodal') and not has_ctf and not (mask_radius or 0) > 0
+
+
 def run(kind: str, argv=None):
     args = build_parser(kind).parse_args(argv)
     from src import models                     # drop-in classes (checkpoints pickle as src.models.*)
@@ -315,7 +322,7 @@ def run(kind: str, argv=None):
                          '(train_particles.py:303-307,330-333) and is not built')
     step_dim = args.encoder_padding if kind == 'particles' else image_dim   # reference positional argument
     graphed = None
-    graph_ok = (t_inf == 'attention' and r_inf != 'unimodal') and not isinstance(train_src, tuple) and not (mask_radius or 0) > 0
+    graph_ok = graph_supported(t_inf, r_inf, isinstance(train_src, tuple), mask_radius)
     if args.graph and args.no_graph:
         raise SystemExit('--graph and --no-graph exclude each other')
     if args.graph and not graph_ok:

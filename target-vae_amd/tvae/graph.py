@@ -1,13 +1,20 @@
-"""hipGraph replay of the forward + backward of the training step (opt-in: `--graph` of the drivers, `bench.py --graph`).
+"""hipGraph replay of the forward + backward of the training step.
+
+The four drivers capture it BY DEFAULT wherever tvae.driver.graph_supported() says the step can be captured: the attention
+branch (`--t-inf attention`, `--r-inf attention` or `attention+offsets`) without CTF filters and without a mask radius.
+`--graph` insists (an error where it cannot apply), `--no-graph` or TVAE_GRAPH=0 runs every step eagerly; `bench.py` takes the
+graph with `--graph` only.
 
 The 28x28 workloads launch ~70 kernels per 4 ms step, so the host's launch cost shows; capturing forward + backward once and
 replaying it removes it.  What stays outside the graph: the minibatch copy into a static buffer, the three noise draws
 (torch RNG kernels, the reference's order: train_mnist.py:206,230 / src/models.py:387), the gradient all-reduce and the
 fused Adam launch -- so learning-rate changes, data parallelism and the optimizer state behave exactly as in eager mode.
 
-Replay is BIT FOR BIT equal to eager execution (tests/test_driver_gpu.py::test_graphed_step_bitwise_equals_eager, also
-with a host synchronize or a `deepcopy(model).cpu()` between replays: the two triggers under which round 2 saw corrupted
-replays no longer reproduce with this library -- profiles/tools/graph_replay_probe.py, profiles/README.md round 3).
+Replay is BIT FOR BIT equal to eager execution on every route a driver can capture (tests/test_graph_gpu.py: one case per
+route of tvae/ops.py, with eager work that outgrows the scratch buffers between replays and with two graphs open at once;
+tests/test_driver_gpu.py::test_graphed_step_bitwise_equals_eager: also with a host synchronize or a `deepcopy(model).cpu()`
+between replays, the two triggers under which round 2 saw corrupted replays -- they no longer reproduce with this library:
+profiles/tools/graph_replay_probe.py, profiles/README.md round 3).
 A minibatch of another size than the captured one (the ragged tail of an epoch) runs eagerly.
 """
 from __future__ import annotations

@@ -149,7 +149,8 @@ def train_epoch(iterator, x_coord, generator_model, encoder_model, optim, t_inf,
     """Reference train_mnist.py:300-346: loss = -elbo; backward; step; batch-weighted running means.
     With `mask_radius` not None it is the particles variant (train_particles.py:350-410): minibatches are (y,) or
     (y, ctf) and `image_dim` carries the encoder padding like the reference's positional argument.
-    `graphed` (tvae.graph.GraphedStep, opt-in): minibatches of its captured size replay a hipGraph of forward + backward."""
+    `graphed` (a tvae.graph.GraphedStep; the drivers pass one by default wherever tvae.driver.graph_supported() holds):
+    minibatches of its captured size replay a hipGraph of forward + backward, any other size (the ragged tail) runs eagerly."""
     generator_model.train()
     encoder_model.train()
     c = 0

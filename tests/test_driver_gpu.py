@@ -146,7 +146,7 @@ def test_eval_model_matches_oracle():
 
 
 def test_graphed_step_bitwise_equals_eager():
-    """tvae.graph.GraphedStep (opt-in `--graph`): replaying the captured forward + backward gives BIT FOR BIT the eager
+    """tvae.graph.GraphedStep (the drivers' default step): replaying the captured forward + backward gives BIT FOR BIT the eager
     gradients and ELBO terms over several optimizer steps -- also with the two triggers under which round 2 saw corrupted
     replays (a host synchronize between a replay and the next launch; deepcopy(model).cpu() between replays)."""
     import copy
@@ -207,14 +207,26 @@ def test_graphed_step_bitwise_equals_eager():
     assert r0 == r1 and torch.equal(opt.flat_p, p1)
 
 
-def test_cli_graph_flag_same_log_as_eager(tmp_path):
-    """`train_mnist.py` with the hipGraph step (the default since round 6, and with --graph insisting on it) prints the same
-    TSV lines as the eager run (--no-graph) under the same seed."""
+# driver -> (its arguments, the runs to compare): every driver's DEFAULT run (captured) against --no-graph; train_mnist also
+# with --graph insisting.  train_particles without --mask-radius (a mask runs eagerly: driver.graph_supported).
+GRAPH_CLI = {
+    'train_mnist': (CASES['train_mnist'][0], (['--no-graph'], [], ['--graph'])),
+    'train_galaxy': (CASES['train_galaxy'][0], (['--no-graph'], [])),
+    'train_dsprites': (CASES['train_dsprites'][0], (['--no-graph'], [])),
+    'train_particles': (['--crop', '20', '-z', '2', '--fourier-expansion'], (['--no-graph'], [])),
+}
+
+
+@pytest.mark.parametrize('script', sorted(GRAPH_CLI))
+def test_cli_graph_flag_same_log_as_eager(script, tmp_path):
+    """Every driver with the hipGraph step (the default since round 6; train_mnist also with --graph insisting on it) prints
+    the same TSV lines as its eager run (--no-graph) under the same seed."""
+    args, runs = GRAPH_CLI[script]
     outs = []
-    for extra in (['--no-graph'], [], ['--graph']):
-        cmd = [sys.executable, os.path.join(PKG, 'train_mnist.py')] + SMALL + CASES['train_mnist'][0] + extra + \
+    for extra in runs:
+        cmd = [sys.executable, os.path.join(PKG, script + '.py')] + SMALL + args + extra + \
             ['--seed', '7', '--log-root', str(tmp_path / ('logs' + ''.join(extra)))]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
         assert r.returncode == 0, r.stderr[-3000:]
         outs.append([ln for ln in r.stdout.splitlines() if '\t' in ln])
-    assert outs[0] == outs[1] == outs[2] and len(outs[0]) == 5
+    assert all(o == outs[0] for o in outs[1:]) and len(outs[0]) == 5, outs

@@ -11,14 +11,12 @@ import torch
 
 from conftest import GOLDEN, assert_encoder_grads, assert_grad_close, load_golden, rel_err, seeded_models, tdict
 from oracle import tvae_oracle as O
+from step_cases import (OOB_CONFIGS, bits_equal as _bits_equal, build_encoder, build_generator, build_step_models,
+                        cin3_direct_encoder, dev, fresh, golden_step, heads103_encoder)
 
 pytestmark = pytest.mark.gpu
 OUT_TOL = 1e-4
 GRAD_TOL = 1e-3
-
-
-def dev():
-    return torch.device('cuda:0')
 
 
 @pytest.fixture(params=['f32', 'x6', 'h3'], autouse=True)
@@ -29,25 +27,6 @@ def gemm_mode(request):
     from tvae import _lib
     with _lib.arithmetic(request.param):
         yield request.param
-
-
-def build_encoder(fx, prefix):
-    import src.models as M
-    cfg = [int(v) for v in fx['cfg']]
-    n, cin, zd, C, k, p, R, refine, normal = cfg[:9]
-    enc = M.InferenceNetwork_AttentionTranslation_AttentionRotation(
-        n, cin, zd, kernels_num=C, kernels_size=k, padding=p, groupconv=R, rot_refinement=bool(refine),
-        theta_prior=float(fx['theta_prior']), normal_prior_over_r=bool(normal))
-    enc.load_state_dict({k_: v for k_, v in tdict(fx, prefix).items()})
-    return enc.to(dev())
-
-
-def build_generator(fx, prefix, zd, hid, n_out, L, resid, fourier, sigma):
-    import src.models as M
-    gen = M.SpatialGenerator(zd, hid, n_out=n_out, num_layers=L, resid=bool(resid), fourier_expansion=bool(fourier),
-                             sigma=sigma)
-    gen.load_state_dict({k_: v for k_, v in tdict(fx, prefix).items()})
-    return gen.to(dev())
 
 
 @pytest.mark.parametrize('path', sorted(glob.glob(os.path.join(GOLDEN, 'bank_*.npz'))))
@@ -184,13 +163,6 @@ STEP_LIK = {'step_mnist28_P8_init': 'bce', 'step_mnist28_P8_peaked': 'bce',
             'step_particles64_P8': 'gauss', 'step_particles32_fitnoise': 'gauss_var', 'step_galaxy_small': 'bce'}
 
 
-def build_step_models(fx):
-    n, cin, zd, C, k, p, R, refine, normal, hid, L, n_out, fourier, resid = [int(v) for v in fx['cfg']]
-    enc = build_encoder(fx, 'e.')
-    gen = build_generator(fx, 'd.', zd, hid, n_out, L, resid, fourier, float(fx['sigma']))
-    return enc, gen, n
-
-
 @pytest.mark.parametrize('name', sorted(STEP_LIK))
 def test_step_golden(name):
     """eval_minibatch (reference train_*.py) -> (elbo, log_p, kl) and every parameter gradient."""
@@ -275,25 +247,6 @@ def test_step_hot_widths_golden(name, gemm_mode):
         assert_grad_close(t.grad, fx['gd.' + k_], tol=max(GRAD_TOL, 2 * float(fx['kd.' + k_])), name='gen.' + k_)
 
 
-# (n, z_dim, R, B, C, hidden, k, padding, Fourier decoder) of the two memory-safety tests below
-OOB_CONFIGS = {'small': (20, 2, 8, 8, 8, 32, 20, 4, False),
-               'small_fourier': (20, 2, 8, 8, 8, 32, 20, 4, True),
-               'S28': (28, 2, 8, 16, 128, 512, 28, 14, False),
-               'S28F': (28, 2, 16, 8, 128, 512, 28, 14, True),
-               'S64': (64, 2, 8, 4, 128, 512, 64, 16, False),
-               # B * Ho a multiple of 32 (as at the bench's B = 256): no ragged last tile
-               'S64x': (64, 2, 8, 32, 128, 512, 64, 16, False),
-               'M50x': (50, 2, 8, 32, 128, 512, 28, 8, False),
-               # the reference's MNIST geometries (k = 28, padding 8): the 44- and 66-wide ring
-               # transforms; M28r: a batch whose last 32-column tile is ragged
-               'M28': (28, 2, 8, 32, 128, 512, 28, 8, False),
-               'M28r': (28, 2, 8, 5, 128, 512, 28, 8, False),
-               'M50': (50, 2, 8, 4, 128, 512, 28, 8, False),
-               # round 5: a large frame (L = 112, Ho = 97 = 3 x 32 + 1): the WIDE generic transforms
-               # along w (workgroup per tile, extra output column on the vector ALU), ragged batch
-               'G96': (96, 2, 8, 3, 16, 64, 32, 16, False)}
-
-
 @pytest.mark.parametrize('cfg', ['small', 'small_fourier', 'S28', 'S28F', 'S64', 'S64x', 'M28', 'M28r', 'M50', 'M50x', 'G96'])
 def test_step_does_not_read_out_of_bounds(cfg):
     """Out-of-bounds READ detector.  Every float tensor the step allocates (torch.empty / torch.zeros, workspaces
@@ -357,27 +310,11 @@ def test_step_does_not_read_out_of_bounds(cfg):
             assert torch.equal(g0[k_], g1[k_]), (g, k_)
 
 
-def _bits_equal(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and \
-        torch.equal(a.contiguous().reshape(-1).view(torch.uint8), b.contiguous().reshape(-1).view(torch.uint8))
-
-
 def _oob_case(case):
     """run() of one configuration of test_step_does_not_write_out_of_bounds: a closure that performs the whole computation from
     the same inputs on every call and returns {name: tensor} of everything it produced."""
     import src.models as M
     from tvae import latent, ops, optim, step, tables
-
-    def fresh(n, zd, R, B, C, hid, k, pad, four, cin=1):
-        torch.manual_seed(0)
-        gen = M.SpatialGenerator(zd, hid, num_layers=2, fourier_expansion=four, sigma=2.0 / (n - 1)).to(dev())
-        enc = M.InferenceNetwork_AttentionTranslation_AttentionRotation(
-            n, cin, zd, kernels_num=C, kernels_size=k, padding=pad, groupconv=R, rot_refinement=True, theta_prior=np.pi,
-            normal_prior_over_r=False).to(dev())
-        x = torch.from_numpy(tables.image_coords(n)).to(dev())
-        y = torch.randn(B, cin, n, n, device=dev())
-        nz = step.draw_noise(B, R * enc.output_size() ** 2, zd, dev())
-        return gen, enc, x, y, nz
 
     def step_run(gen, enc, terms):
         params = list(gen.named_parameters()) + list(enc.named_parameters())
@@ -415,24 +352,11 @@ def _oob_case(case):
         return step_run(gen, enc, lambda: step.elbo_terms(x, y, gen, enc, 'gauss', nz))
     if case in ('heads103', 'heads103_x32'):
         # z_dim = 50: 103 head rows (the wide encoder tail in h3); second geometry: a column count that is a multiple of 32
-        (n, k, pad, B), R, zd = {'heads103': (20, 20, 4, 3), 'heads103_x32': (21, 20, 3, 2)}[case], 4, 50
-        torch.manual_seed(5)
-        enc = M.InferenceNetwork_AttentionTranslation_AttentionRotation(n, 1, zd, kernels_num=128, kernels_size=k, padding=pad,
-                                                                        groupconv=R, rot_refinement=True, theta_prior=np.pi,
-                                                                        normal_prior_over_r=False).to(dev())
-        with torch.no_grad():
-            for m in (enc.conv_a, enc.conv_r, enc.conv_z):
-                m.weight.mul_(8.0)
-        return encoder_run(enc, torch.rand(B, 1, n, n, device=dev()), zd, R)
+        return encoder_run(*heads103_encoder(case))
     if case == 'cin3_direct':
         # three input channels through the DIRECT convolution kernels (fp32 MFMA in f32, the LDS-resident split kernels
         # otherwise): the frequency-domain route is switched off for this case
-        n, k, pad, B, R, zd = 20, 9, 3, 5, 4, 2
-        torch.manual_seed(6)
-        enc = M.InferenceNetwork_AttentionTranslation_AttentionRotation(n, 3, zd, kernels_num=128, kernels_size=k, padding=pad,
-                                                                        groupconv=R, rot_refinement=True, theta_prior=np.pi,
-                                                                        normal_prior_over_r=False).to(dev())
-        inner = encoder_run(enc, torch.rand(B, 3, n, n, device=dev()), zd, R)
+        inner = encoder_run(*cin3_direct_encoder())
 
         def run():
             old, ops.CONV_DFT = ops.CONV_DFT, False
@@ -451,11 +375,7 @@ def _oob_case(case):
             return {k_: t.detach().clone() for k_, t in (('elbo', e), ('log_p', lp), ('kl', kl), ('zc', zc), ('th', th), ('dx', dx))}
         return run
     if case in ('particles_ctf_mask', 'galaxy_fourier_nout3'):
-        fx = load_golden('step_particles32_ctf_mask' if case == 'particles_ctf_mask' else 'step_galaxy_small')
-        enc, gen, n = build_step_models(fx)
-        x = O.image_coords(n).to(dev())
-        noise = tuple(torch.from_numpy(fx[k_]).to(dev()) for k_ in ('E', 'eps_z', 'eps_theta'))
-        yy = torch.from_numpy(fx['y']).to(dev())
+        fx, enc, gen, x, yy, noise = golden_step('step_particles32_ctf_mask' if case == 'particles_ctf_mask' else 'step_galaxy_small')
         if case == 'particles_ctf_mask':
             ctf = torch.from_numpy(fx['ctf']).to(dev())
             return step_run(gen, enc, lambda: step.eval_minibatch_particles(x, yy, ctf, gen, enc, 'attention', 'attention+offsets', 0,

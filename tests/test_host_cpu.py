@@ -574,6 +574,61 @@ def test_scratch_buffers_outlive_a_captured_graph():
         ops._PINNED.update(saved[1])
 
 
+@pytest.mark.parametrize('t_inf,r_inf,has_ctf,mask_radius,want', [
+    # the TARGET-VAE branch, both spellings of --r-inf; mask_radius: None (datasets without a mask), 0 (particles, none asked)
+    ('attention', 'attention+offsets', False, None, True),
+    ('attention', 'attention', False, None, True),
+    ('attention', 'attention+offsets', False, 0, True),
+    ('attention', 'attention', False, 0, True),
+    # a circular mask or per-image CTF filters: the step runs eagerly
+    ('attention', 'attention+offsets', False, 7, False),
+    ('attention', 'attention', False, 7, False),
+    ('attention', 'attention+offsets', True, None, False),
+    ('attention', 'attention+offsets', True, 0, False),
+    ('attention', 'attention', True, 7, False),
+    # the secondary inference branches are never captured
+    ('attention', 'unimodal', False, None, False),
+    ('attention', 'unimodal', False, 0, False),
+    ('unimodal', 'unimodal', False, None, False),
+    ('unimodal', 'attention', False, None, False),
+    ('unimodal', 'attention+offsets', False, 0, False),
+    ('unimodal', 'unimodal', True, 7, False),
+])
+def test_graph_supported_table(t_inf, r_inf, has_ctf, mask_radius, want):
+    """tvae.driver.graph_supported: which runs the drivers capture into a hipGraph by default."""
+    from tvae import driver
+    got = driver.graph_supported(t_inf, r_inf, has_ctf, mask_radius)
+    assert got is want
+
+
+def test_graph_case_table_and_exclusions_are_current():
+    """CPU twin of tests/test_graph_gpu.py::test_every_capturable_route_was_replayed: every excluded route still exists in
+    tvae/ops.py and carries a reason, the route scan finds the names ops.py is known to record (both names of a conditional
+    expression included), and the case table only names configurations, fixtures and builders that exist."""
+    import step_cases as S
+    routes = S.noted_routes()
+    assert {'conv1.dft_ring', 'conv1.x6', 'conv1.f32', 'enc.tail_fwd_wide', 'enc.tail_fwd_x6', 'dec.hidden_h3_mem',
+            'dec.hidden_h3_meas', 'dec.no_h_inference', 'dec.no_h', 'dec.fused_out', 'dec.hidden_x6', 'dec.ld_pad',
+            'trans_attn.plain', 'trans_attn.rot_pool'} <= routes
+    assert all(re.fullmatch(r'[a-z0-9_]+\.[a-z0-9_]+', r) for r in routes), sorted(routes)
+    for name, reason in S.GRAPH_EXCLUDED_ROUTES.items():
+        assert name in routes, f'{name} is excluded but tvae/ops.py no longer records it'
+        assert isinstance(reason, str) and len(reason.split()) >= 4, name
+    assert {'enc.inference', 'dec.no_h_inference', 'trans_attn.plain', 'mlp_encoder.kernels'} <= set(S.GRAPH_EXCLUDED_ROUTES)
+    for case, c in S.GRAPH_CASES.items():
+        assert len([k_ for k_ in ('cfg', 'golden', 'encoder') if k_ in c]) == 1, case
+        assert c['lik'] in ('bce', 'bce3', 'gauss', 'gauss_var'), case
+        if 'cfg' in c:
+            assert c['cfg'] in S.OOB_CONFIGS, case
+        elif 'golden' in c:
+            assert os.path.exists(os.path.join(ROOT, 'tests', 'golden', c['golden'] + '.npz')), case
+        else:
+            assert c['encoder'] in set(S.HEADS103_GEOM) | {'cin3_direct'}, case
+    assert set(S.GRAPH_ARITHMETIC_CASES) <= set(S.GRAPH_CASES)
+    from tvae import _lib
+    assert set(S.GRAPH_ARITHMETIC_MODES) | {'h3'} == set(_lib.GEMM_MODES)
+
+
 def test_flat_adam_second_backward_raises():
     """with the two-bucket reducer active exactly one backward per step() is supported -- a second one reaching the
     early bucket after it was posted raises; after disable_early_bucket() (captured-graph path) the hooks are inert."""
