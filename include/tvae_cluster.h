@@ -1,5 +1,6 @@
-/* C ABI of libtvae_cluster.so: batched Lloyd k-means, Ward linkage, exact t-SNE and aligned class averages on the GPU
- * (gfx950), the hot paths of clustering_*.py and class_averages.py.
+/* C ABI of libtvae_cluster.so: batched Lloyd k-means, Ward linkage, exact t-SNE, aligned class averages and their half
+ * sets, variance maps and ring correlation on the GPU (gfx950), the hot paths of clustering_*.py, class_averages.py and
+ * class_resolution.py.
  *
  * Same conventions as tvae_hip.h: raw device pointers and sizes, the stream as void*, `int` return = hipError_t.  The
  * entry points never allocate, free or synchronise and keep no process-wide state; the workspace is the caller's,
@@ -27,7 +28,8 @@ typedef void* tvae_stream_t;
 
 #define TVAE_KMEANS_MAX_RESTARTS 65535
 
-/* Still 1: the Ward, t-SNE and alignment entry points below were ADDED, no existing prototype or meaning changed. */
+/* Still 1: the Ward, t-SNE, alignment and class-statistics entry points below were ADDED, no existing prototype or
+ * meaning changed. */
 int tvae_cluster_abi_version(void);          /* == 1 */
 
 /* floats of workspace for one assign / update pair: per restart G x (k*d sums, k counts, 1 changed count, 1 sum of
@@ -179,6 +181,73 @@ int tvae_align_stack(const float* Y, const float* theta, const float* dx, float*
 /* avg[K][C][n][n]; ws holds tvae_class_average_ws_floats(N, K, C, n) floats. */
 int tvae_class_average(const float* Y, const float* theta, const float* dx, const int* order, const int* seg, float* avg,
                        float* ws, long ws_floats, int N, int C, int n, int K, float t_scale, tvae_stream_t stream);
+
+/* ---- Quality of the class averages: half sets, variance maps and the Fourier ring correlation ---------------------------
+ *
+ * tvae_class_halves is tvae_class_average with three accumulators per pixel, in the same single pass over the stack: the
+ * pose convention, the sampling, the zero border and the out-of-frame rule are those of the section above, `order`
+ * entries outside [0, N) are skipped, seg is cleaned on the device in the same way, and the chunks and slots are the same
+ * (tvae_class_average_chunk members counted from the class's own first position).
+ *
+ * Halves: position q of a member counts from the class's first position in `order`; a skipped entry keeps its position.
+ * Half 0 takes the even q, half 1 the odd q (a chunk starts at an even position, so the parity within the chunk is the
+ * half).  Per pixel and chunk three fp32 sums in ascending position, S0 over the even members, S1 over the odd ones and
+ * Q = sum A^2 over all of them (each sample is taken once), and the two member counts n0, n1.  A second launch adds the
+ * chunks of a class in ascending order in fp64 and writes, each rounded to fp32 once,
+ *     half[h] = S_h / n_h (zeros where n_h = 0),   avg = (S0 + S1) / (n0 + n1) (zeros for an empty class),
+ *     var = max(0, (Q - (S0 + S1)^2 / m) / (m - 1)) with m = n0 + n1, and 0 for m < 2,
+ * and counts[k] = (n0, n1).
+ * avg agrees with tvae_class_average to rounding, NOT bit for bit: the order of addition differs (two interleaved fp32
+ * sums per chunk and fp64 above them, against one fp32 sum throughout).
+ * The variance is the sum-of-squares form: its error is relative to Q / m, not to the variance itself.  That is fine for
+ * normalised particles (mean near 0, spread near 1) and poor for images whose mean dwarfs their spread.
+ * No float atomics: every output is a pure function of the inputs, bitwise reproducible, and every output of class k
+ * depends on class k's ordered member list and those members' images and poses only: not on the other classes, not on K.
+ *
+ * Supported: the range of tvae_class_average with the slot count tripled where it bounds the grid,
+ * 3 (N / chunk + K) C ceil(n n / 256) < 2^31; anything else returns hipErrorInvalidValue (1) and writes nothing.
+ *
+ * tvae_class_frc: the Fourier ring correlation of P pairs of planes a[p], b[p] (n x n); planes are independent, a NaN in
+ * a plane stays in that plane's results.
+ * Mask: with d the distance of pixel (i, j) from ((n - 1) / 2, (n - 1) / 2), m = 1 for d <= mask_radius,
+ * m = (1 + cos(pi (d - mask_radius) / mask_edge)) / 2 for mask_radius < d < mask_radius + mask_edge and 0 beyond;
+ * mask_radius <= 0 means no mask, mask_edge = 0 a hard edge; a non-finite radius or edge and a negative edge are
+ * rejected.
+ * Transform: F(ky, kx) = sum_ij a[i][j] m(i, j) exp(-2 pi i (ky i + kx j) / n), ky and kx the signed frequencies in the
+ * order of numpy's fftfreq; a direct DFT in two stages (rows to the half spectrum kx = 0 .. n / 2, then columns) with fp32
+ * products and sums and a table of the n twiddles whose argument is reduced exactly, (i k) mod n in integers, each entry
+ * within an ulp.
+ * Rings: the ring of (ky, kx) is the integer r with r - 1/2 <= sqrt(ky^2 + kx^2) < r + 1/2, decided in exact integer
+ * arithmetic as (2r - 1)^2 <= 4 (ky^2 + kx^2) < (2r + 1)^2 for r >= 1 and 4 (ky^2 + kx^2) < 1 for r = 0 (round half up,
+ * no float comparison).  Rings 0 .. n / 2 (integer division) are kept, the corners beyond are dropped.
+ *     sums[p][r] = (sum Re(Fa conj Fb), sum |Fa|^2, sum |Fb|^2) over the ring of the FULL plane,
+ * accumulated in fp64 in a fixed order (ascending ky index, then ascending kx, over the half spectrum with its Hermitian
+ * weights; the three products of a coefficient are formed in fp64 and rounded to fp32 once), no atomics;
+ *     frc[p][r] = sums0 / sqrt(sums1 sums2) in fp64, rounded to fp32; exactly 0 where either power is 0.
+ *
+ * Supported: 2 <= n <= 1024, 1 <= P <= TVAE_FRC_MAX_PLANES (65535: the planes are the y dimension of the launch grids), ws
+ * 8-byte aligned; anything else returns hipErrorInvalidValue (1) and writes nothing, and the queries return 0. */
+
+#define TVAE_FRC_MAX_PLANES 65535
+
+/* floats of workspace of tvae_class_halves: the cleaned seg and two member counts per chunk slot (int32 words, padded to
+ * a multiple of 4) and three partial sums per pixel of N / chunk + K slots.  0 for unsupported arguments. */
+long tvae_class_halves_ws_floats(int N, int K, int C, int n);
+
+/* avg[K][C][n][n], half[2][K][C][n][n], var[K][C][n][n], counts[K][2] (int32) */
+int tvae_class_halves(const float* Y, const float* theta, const float* dx, const int* order, const int* seg, float* avg,
+                      float* half, float* var, int* counts, float* ws, long ws_floats, int N, int C, int n, int K,
+                      float t_scale, tvae_stream_t stream);
+
+/* number of rings, n / 2 + 1 (integer division).  0 for unsupported n. */
+int tvae_frc_rings(int n);
+/* floats of workspace of tvae_class_frc: per plane the half spectra of the rows of a and b (4 n R) and the three products
+ * of every coefficient (3 n R), R = tvae_frc_rings(n).  0 for unsupported arguments. */
+long tvae_class_frc_ws_floats(int P, int n);
+
+/* a[P][n][n], b[P][n][n] -> frc[P][R] (fp32), sums[P][R][3] (fp64), R = tvae_frc_rings(n) */
+int tvae_class_frc(const float* a, const float* b, float* frc, double* sums, float* ws, long ws_floats, int P, int n,
+                   float mask_radius, float mask_edge, tvae_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 """ctypes binding of libtvae_cluster.so (C ABI declared in include/tvae_cluster.h): the batched k-means, Ward
-linkage and t-SNE kernels.
+linkage, t-SNE, alignment and class-statistics kernels.
 
 A library of its own beside libtvae_hip.so -- the ABI of the training kernels (tvae._lib.SIGNATURES, version 7) is not
 touched by the clustering half.  Same rules: no CPU fallback, tensors are checked by tvae._lib._ptr (GPU, contiguous,
@@ -38,6 +38,9 @@ SIGNATURES = {
     'tvae_align_stack': 'ppppiiif',           # Y, theta, dx, out, N, C, n, t_scale
     # Y, theta, dx, order (int32), seg (int32), avg, ws, ws_floats, N, C, n, K, t_scale
     'tvae_class_average': 'pppppppliiiif',
+    # Y, theta, dx, order (int32), seg (int32), avg, half, var, counts (int32), ws, ws_floats, N, C, n, K, t_scale
+    'tvae_class_halves': 'pppppppppp' 'l' 'iiiif',
+    'tvae_class_frc': 'pppppliiff',           # a, b, frc, sums (fp64), ws, ws_floats, P, n, mask_radius, mask_edge
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
@@ -50,6 +53,9 @@ QUERIES = {
     'tvae_tsne_repulsion_ws_floats': ('i', 'l'),
     'tvae_class_average_ws_floats': ('iiii', 'l'),
     'tvae_class_average_chunk': ('iiii', 'i'),
+    'tvae_class_halves_ws_floats': ('iiii', 'l'),
+    'tvae_frc_rings': ('i', 'i'),
+    'tvae_class_frc_ws_floats': ('ii', 'l'),
 }
 
 _cl = None

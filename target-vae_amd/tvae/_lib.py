@@ -290,6 +290,8 @@ _F64_OK |= {('tvae_ward_merge', p) for p in (0, 4, 6, 11, 13)}
 # ... and Z, the |grad|^2 partials, the KL divergence and its workspace of the t-SNE entry points
 _F64_OK |= {('tvae_tsne_repulsion', 3), ('tvae_tsne_step', 6), ('tvae_tsne_step', 11)}
 _F64_OK |= {('tvae_tsne_kl', p) for p in (6, 7, 8)}
+# ... and the ring sums of tvae_class_frc
+_F64_OK |= {('tvae_class_frc', 3)}
 
 
 def _ptr(t, name, pos):

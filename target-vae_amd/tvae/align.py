@@ -8,8 +8,11 @@ image at x = u R(theta)^T + t dx, bilinearly, with a zero border.  t is 1 where 
 and 0.1 for --t-inf unimodal (the reference's dx_scale, which get_latent does not apply to the dx it returns):
 `translation_scale`.  include/tvae_cluster.h states the definition in full.
 
-The kernels are tvae_align_stack and tvae_class_average of libtvae_cluster.so.  The class averages are fused: the aligned
-stack is never written, the stack is read once, there are no float atomics and the result is bitwise reproducible;
+`class_halves` and `frc` measure the quality of the averages: the two half-set averages and the variance map of every
+class in the same single pass, and the Fourier ring correlation of the halves (tvae.resolution turns it into a number).
+
+The kernels are tvae_align_stack, tvae_class_average, tvae_class_halves and tvae_class_frc of libtvae_cluster.so.  The
+class averages are fused: the aligned stack is never written, the stack is read once, there are no float atomics and the result is bitwise reproducible;
 avg[k] depends on class k's members alone, not on the other classes or on the number of classes.  There is no CPU
 fallback for the kernels; `segments` is torch code that does not care where its tensors live.
 """
@@ -110,6 +113,81 @@ def class_averages(images, theta, dx, labels, n_clusters=None, t_scale=1.0):
     with torch.cuda.device(images.device):
         CL.call('tvae_class_average', images, theta.reshape(N), dx, order, seg, avg, ws, wsf, N, C, n, K, float(t_scale))
     return avg, counts
+
+
+def _check_labels(images, theta, dx, labels, n_clusters, what):
+    N, C, n = _check_stack(images, theta, dx, what)
+    lab = torch.as_tensor(labels)
+    if lab.dim() != 1 or lab.numel() != N:
+        raise TvaeHipError(f'{what}: labels must hold N = {N} entries, got {tuple(lab.shape)}')
+    lab = lab.to(images.device)
+    K = int(n_clusters) if n_clusters is not None else int(lab.max()) + 1
+    if not 1 <= K <= MAX_CLUSTERS:
+        raise TvaeHipError(f'{what}: n_clusters = {K} outside [1, {MAX_CLUSTERS}]')
+    return N, C, n, K, lab
+
+
+def class_halves(images, theta, dx, labels, n_clusters=None, t_scale=1.0):
+    """-> (avg fp32 [K][C][n][n], halves fp32 [2][K][C][n][n], var fp32 [K][C][n][n], counts int32 [K][2]) on the device of
+    `images`, in ONE pass over the stack (tvae_class_halves): the members of a class in ascending image index go
+    alternately to half 0 and half 1, halves[h][k] is the mean of the aligned images of half h, avg[k] that of the whole
+    class and var[k] its per-pixel sample variance (sum-of-squares form, 0 for fewer than two members).  Arguments and
+    checks as class_averages.  avg agrees with class_averages to rounding, not bit for bit.  Both halves share one encoder
+    and one set of poses: a ring correlation of them is not a gold-standard one and reads optimistic."""
+    N, C, n, K, lab = _check_labels(images, theta, dx, labels, n_clusters, 'class_halves')
+    order, seg, _ = segments(lab, K)
+    wsf = CL.query('tvae_class_halves_ws_floats', N, K, C, n)
+    if wsf <= 0:
+        raise TvaeHipError(f'class_halves: N={N}, K={K}, C={C}, n={n} is more than one launch covers')
+    dev = images.device
+    avg = torch.empty(K, C, n, n, dtype=torch.float32, device=dev)
+    halves = torch.empty(2, K, C, n, n, dtype=torch.float32, device=dev)
+    var = torch.empty(K, C, n, n, dtype=torch.float32, device=dev)
+    counts = torch.empty(K, 2, dtype=torch.int32, device=dev)
+    ws = torch.empty(wsf, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        CL.call('tvae_class_halves', images, theta.reshape(N), dx, order, seg, avg, halves, var, counts, ws, wsf, N, C, n, K,
+                float(t_scale))
+    return avg, halves, var, counts
+
+
+FRC_WS_FLOATS = 1 << 26           # workspace of one tvae_class_frc call: 256 MB
+
+
+def frc(a, b, mask_radius=None, mask_edge=0.0):
+    """a, b [...][n][n] (CUDA fp32, equal shapes) -> (frc fp32 [...][R], sums fp64 [...][R][3]), R = n // 2 + 1: the Fourier
+    ring correlation of every pair of planes under the soft circular mask (mask_radius None or <= 0: no mask) and the ring
+    sums (Re(Fa conj Fb), |Fa|^2, |Fb|^2) it is the ratio of.  include/tvae_cluster.h states the definition."""
+    for nm, t in (('a', a), ('b', b)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise TvaeHipError(f'frc: {nm} must be a contiguous CUDA fp32 tensor (no CPU fallback)')
+    if a.shape != b.shape or a.device != b.device or a.dim() < 2 or a.shape[-1] != a.shape[-2]:
+        raise TvaeHipError(f'frc: a and b must be [...][n][n] of one shape on one device, got {tuple(a.shape)} and '
+                           f'{tuple(b.shape)}')
+    n = a.shape[-1]
+    R = CL.query('tvae_frc_rings', n)
+    P = a.numel() // (n * n) if n else 0
+    if R <= 0 or P < 1:
+        raise TvaeHipError(f'frc: n={n} with {P} planes outside the supported range (2 <= n <= 1024, at least one plane)')
+    radius = 0.0 if mask_radius is None else float(mask_radius)
+    edge = float(mask_edge)
+    if not (np.isfinite(radius) and np.isfinite(edge) and edge >= 0):
+        raise TvaeHipError(f'frc: mask_radius = {mask_radius} and mask_edge = {mask_edge} must be finite, the edge not negative')
+    lead = tuple(a.shape[:-2])
+    a2, b2 = a.reshape(P, n, n), b.reshape(P, n, n)
+    out = torch.empty(P, R, dtype=torch.float32, device=a.device)
+    sums = torch.empty(P, R, 3, dtype=torch.float64, device=a.device)
+    # Planes are independent and a plane's workgroups, addition order and twiddles depend on n alone, so a call on a slice
+    # of the planes cannot change a bit of any plane's result: the slices only bound the workspace.
+    per = CL.query('tvae_class_frc_ws_floats', 1, n)
+    step = max(1, min(P, FRC_WS_FLOATS // per, 65535))
+    wsf = CL.query('tvae_class_frc_ws_floats', step, n)
+    ws = torch.empty(wsf, dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        for p0 in range(0, P, step):
+            p1 = min(p0 + step, P)
+            CL.call('tvae_class_frc', a2[p0:p1], b2[p0:p1], out[p0:p1], sums[p0:p1], ws, wsf, p1 - p0, n, radius, edge)
+    return out.reshape(lead + (R,)), sums.reshape(lead + (R, 3))
 
 
 def save_outputs(out_dir, avg, counts, particles=False):

@@ -19,6 +19,13 @@ TVAE_CLASS_AVERAGES=1 adds the step after the reference scripts: every image res
 predicted rotation and translation and averaged per cluster on the GPU (tvae.align) -- class_averages.npy
 ([K][C][n][n]), class_counts.npy, class_averages.mrcs for particles and the montage class_averages.jpg when matplotlib is
 present.  class_averages.py computes the same from the saved .npy files alone.  Unset, nothing changes.
+
+TVAE_CLASS_FRC=1 measures those averages (tvae.resolution): the two half-set averages and the variance map of every class
+in one pass over the images, the Fourier ring correlation of the halves and a resolution per class -- class_halves.npy,
+class_variance.npy, class_frc.npy, class_counts.npy ([K][2], the members of each half; it replaces the [K] file of
+TVAE_CLASS_AVERAGES=1 when both are set), class_resolution.txt and, with matplotlib, class_frc.jpg and class_variance.jpg.
+Both halves share one encoder and one set of poses: not a gold-standard FRC, it reads optimistic.  class_resolution.py
+computes the same from the saved .npy files alone.  Unset, nothing changes.
 """
 from __future__ import annotations
 
@@ -182,6 +189,19 @@ def _class_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clus
     align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles=kind == 'particles')
 
 
+def _class_frc(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters):
+    """TVAE_CLASS_FRC=1: half-set averages, variance maps, ring correlation and resolution of the run's classes
+    (tvae.resolution), from the same images, poses and clusters as the class averages."""
+    from . import align, resolution
+    print('# saving class half sets, variance maps and FRC ({}) ... '.format(resolution.NOTE), file=sys.stderr)
+    if images.shape[-1] != images.shape[-2]:
+        raise SystemExit('TVAE_CLASS_FRC=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
+    y = images.to(device).float().contiguous()
+    res = resolution.class_resolution(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(),
+                                      np.asarray(clusters), args.n_clusters, align.translation_scale(args.t_inf))
+    resolution.save_outputs(out_dir, res)
+
+
 def run(kind: str, argv=None):
     args = build_parser(kind).parse_args(argv)
     from src import models  # noqa: F401     (whole-module checkpoints unpickle as src.models.*)
@@ -244,6 +264,8 @@ def run(kind: str, argv=None):
         print('# the t-SNE, confusion-matrix and histogram figures of the reference are not built', file=sys.stderr)
     if os.environ.get('TVAE_CLASS_AVERAGES', '') == '1':
         _class_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+    if os.environ.get('TVAE_CLASS_FRC', '') == '1':
+        _class_frc(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
 
     np.save(os.path.join(out_dir, 'latents.npy'), z_values.cpu().numpy())
     np.save(os.path.join(out_dir, 'rotations.npy'), rot_pred.cpu().numpy())

@@ -139,3 +139,51 @@ def save_class_averages(out_dir, averages, counts):
     plt.savefig(path, bbox_inches='tight')
     plt.close(fig)
     return path
+
+
+def save_class_frc(out_dir, curves, thresholds=(0.143, 0.5), n=None, apix=None):
+    """The ring-correlation curve of every class [K][R] against the spatial frequency (1 / pixel, or 1 / Angstrom with
+    `apix`; the ring index without `n`), with a dashed line at every threshold."""
+    plt = _plt()
+    c = np.asarray(curves, dtype=np.float64)
+    K, R = c.shape
+    x = np.arange(R, dtype=np.float64)
+    label = 'ring'
+    if n is not None:
+        x, label = x / (n * (apix if apix is not None else 1.0)), '1 / Angstrom' if apix is not None else '1 / pixel'
+    fig = plt.figure(figsize=(10, 6))
+    cmap = plt.cm.rainbow
+    for k in range(K):
+        plt.plot(x, c[k], color=cmap(k / max(K - 1, 1)), linewidth=1, label=str(k) if K <= 20 else None)
+    for t in thresholds:
+        plt.axhline(t, color='k', linestyle='--', linewidth=0.8)
+    plt.xlabel('spatial frequency ({})'.format(label))
+    plt.ylabel('FRC of the two half-set averages')
+    plt.ylim(-0.2, 1.05)
+    if K <= 20:
+        plt.legend(title='class', fontsize=8)
+    path = os.path.join(out_dir, 'class_frc.jpg')
+    plt.savefig(path, bbox_inches='tight')
+    plt.close(fig)
+    return path
+
+
+def save_class_variance(out_dir, variance, counts):
+    """Montage of the per-pixel variance maps [K][C][n][n] (averaged over the channels), one panel per class on its own
+    scale, titled with the class and its number of members."""
+    plt = _plt()
+    var, counts = np.asarray(variance, dtype=np.float64), np.asarray(counts).reshape(-1)
+    K = var.shape[0]
+    cols = min(K, 10)
+    rows = (K + cols - 1) // cols
+    fig, axes = plt.subplots(rows, cols, figsize=(2 * cols, 2.3 * rows), squeeze=False)
+    for k, ax in enumerate(axes.ravel()):
+        ax.axis('off')
+        if k >= K:
+            continue
+        ax.imshow(var[k].mean(0), cmap='magma')
+        ax.set_title('{}: {}'.format(k, int(counts[k])), fontsize=9)
+    path = os.path.join(out_dir, 'class_variance.jpg')
+    plt.savefig(path, bbox_inches='tight')
+    plt.close(fig)
+    return path
