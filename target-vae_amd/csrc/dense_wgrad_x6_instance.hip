@@ -7,6 +7,28 @@
 using namespace tvae;
 
 // variant = VIRT | XVA << 1 | LRF << 2   (LRF: 0 off, 1 two-valued from H, 2 two-valued from sign bits)
+// Variant 11 (sign bits against gy x the recomputed first-layer operand) runs in 32-column steps (STEP = 32, a ring of its own
+// size) when the reduction slices and the images are multiples of 32 columns; -DTVAE_WG_STEP16 keeps the 16-column instance
+// everywhere (the A/B partner: profiles/tools/build_variant.sh dense_wgrad_x6_p2 -DTVAE_WG_STEP16 old.so).
+#ifdef TVAE_WG_STEP16
+constexpr bool WG_STEP32 = false;
+#else
+constexpr bool WG_STEP32 = true;
+#endif
+#define TVAE_WG_BITS_XVA(NP_)                                                                                         \
+    do {                                                                                                              \
+        if constexpr (WG_STEP32) {                                                                                    \
+            if (nchunk % 32 == 0 && N % 32 == 0 && va.Np >= 32 && va.Np % 32 == 0) {                                  \
+                hipError_t e_ = allow_big_lds(dense_wgrad_x6_dma_kernel<true, true, 2, NP_, false, 32>, WG32_RING_BYTES); \
+                if (e_ != hipSuccess) return (int)e_;                                                                 \
+                hipLaunchKernelGGL((dense_wgrad_x6_dma_kernel<true, true, 2, NP_, false, 32>), dim3(tm.grid()),       \
+                                   dim3(DX6_THREADS), WG32_RING_BYTES, st, dY, ldd, X, ldx, ws, M, Kf, N, nchunk, tm, bt, \
+                                   dy_stride, vg, va, atile, hs);                                                     \
+                return (int)hipGetLastError();                                                                        \
+            }                                                                                                         \
+        }                                                                                                             \
+        TVAE_WG_ONE(true, true, 2, NP_);                                                                              \
+    } while (0)
 #define TVAE_WG_ONE(V_, X_, L_, NP_)                                                                                  \
     do {                                                                                                              \
         hipError_t e_ = allow_big_lds(dense_wgrad_x6_dma_kernel<V_, X_, L_, NP_>, WG_RING_BYTES);                     \
@@ -26,7 +48,7 @@ using namespace tvae;
             case 5: TVAE_WG_ONE(true, false, 1, NP_);                                                                 \
             case 7: TVAE_WG_ONE(true, true, 1, NP_);                                                                  \
             case 9: TVAE_WG_ONE(true, false, 2, NP_);                                                                 \
-            case 11: TVAE_WG_ONE(true, true, 2, NP_);                                                                 \
+            case 11: TVAE_WG_BITS_XVA(NP_);                                                                           \
             default: return (int)hipErrorInvalidValue;                                                                \
         }                                                                                                             \
     }                                                                                                                 \

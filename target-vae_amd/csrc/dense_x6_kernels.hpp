@@ -1130,6 +1130,21 @@ constexpr ATile ATILE_PLAIN = {30, 0x3fffffff, 0};
 // ------------------------------------------------------------------------------------------
 constexpr int WG_SLOT_BYTES = 4096 + 1024 + 256;      // A | X (or coordinates 256 + latent term 256) | gy
 constexpr int WG_RING_BYTES = 8 * 3 * WG_SLOT_BYTES;
+// STEP = 32 (sign bits against gy x the recomputed first-layer operand only: VIRT, XVA, LRF == 2): a step is 32 columns, ONE
+// stored bit word per row.  At 16 columns that instance fetched every word twice (once per half), re-fetched the latent term
+// (constant over an image) behind an integer division, and paid a barrier, ten m0 writes and a 24-register copy per 32
+// columns for 2 x 16 MFMAs.  Here a slot is five 256-byte DMAs -- bit words of fragment rows i = 0, 1 | 64 coordinate dwords
+// (lane = dword) | this thread's latent term | 32 gy -- i.e. NDMA = 5 per 32 columns instead of 10, all still unconditional
+// and clamped (see above: nothing but DMAs under the hand-counted vmcnt).  The landed word serves both 16-column sub-steps
+// (cell of sub-step u, octet khalf: bits 16 u + 8 khalf ..+ 7); the B stage holds four octets per part
+// ([stage][part][octet < 4][128 k rows]); a thread builds its four columns of half 0, then of half 1, and the MFMAs run
+// sub-step 0 (j, i, p), then sub-step 1: s[k] and every accumulator see the 16-column kernel's exact sequence -- the slabs
+// are bit-identical.  Np % 32 == 0 (host) keeps a step inside one image, so the image index advances by compare-and-
+// increment.  One barrier per 32 columns; the two A-cell sets ping-pong through a loop unrolled by two (no copy).  The ring
+// is sized from this slot (30 KB, not 126 KB); the registers (208-216) still keep it at one workgroup per CU.
+// Measured (profiles/README.md, "Sign-bit weight gradient in 32-column steps"): 1 365 -> 1 117 us per launch at S64.
+constexpr int WG32_SLOT_BYTES = 5 * 256;
+constexpr int WG32_RING_BYTES = 8 * 3 * WG32_SLOT_BYTES;
 
 // LRF (implicit LeakyReLU gradient only): the two-valued form of VirtGrad.  act' = slope + (1 - slope) [H > 0], so
 //   dW[m][k] = wo[m] * ( slope * s[k] + (1 - slope) * sum_n [H[m][n] > 0] * (gy[n] X[k][n]) ),   s[k] = sum_n gy[n] X[k][n]:
@@ -1138,20 +1153,27 @@ constexpr int WG_RING_BYTES = 8 * 3 * WG_SLOT_BYTES;
 // per product block (the single A part against the three X parts) instead of six.  s[k] is accumulated by the threads
 // that build the X cells (each owns one feature row k of the tile) and joins the partial slab in the epilogue.
 // LRF: 0 = off, 1 = two-valued form with [H > 0] taken from the saved activation (dY = H), 2 = from the sign bits a forward
-// launch stored (VirtGrad.bits: one word per row and 32 columns, two dword DMAs per wave and step instead of four 1 KB ones)
+// launch stored (VirtGrad.bits: one word per row and 32 columns, two dword DMAs per wave and step instead of four 1 KB ones;
+// a 16-column step uses half of the word it fetched, STEP = 32 below all of it)
 // ABF (round 4; NP == 1, plain operands only): the A operand is STORED as bf16 (S' of the one-part mode, written by
 // dft_dy_ring_kernel<.., S16>): 8 consecutive n of a row ARE a one-part cell, so the two 1 KB DMAs of a step (instruction g:
 // rows 32 g .. 32 g + 31, lane -> (row lane & 31, 16-byte piece lane >> 5)) land lane-linear in exactly the order in which
 // the fragments read them back -- no split, no vector-ALU work at all on this operand, half the bytes.
-template <bool VIRT, bool XVA, int LRF, int NP, bool ABF = false>
+template <bool VIRT, bool XVA, int LRF, int NP, bool ABF = false, int STEP = 16>
 static __global__ __launch_bounds__(DX6_THREADS, 2)
 void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const float* __restrict__ X, long ldx, float* ws,
                                int M, int Kf, int N, int nchunk, TileMap tm, DenseBatch bt, long dy_stride, VirtGrad vg,
                                VirtAct va, ATile atile, H3Scale hs) {
     static_assert(!ABF || (NP == 1 && !VIRT && !XVA && LRF == 0), "bf16-stored A: one-part mode, plain operands");
+    static_assert(STEP == 16 || (STEP == 32 && VIRT && XVA && LRF == 2), "32-column steps: sign bits x recomputed operand");
+    constexpr bool S32 = STEP == 32;
     constexpr int NDMA = (ABF ? 2 : (LRF == 2 ? 2 : 4)) + (XVA ? 2 : 1) + (VIRT ? 1 : 0);   // DMA instructions per wave and step
-    __shared__ __attribute__((aligned(16))) uint4 Bs[2 * 3 * 2 * 128];    // [stage][part][octet half][k row]
-    extern __shared__ __attribute__((aligned(16))) unsigned char wg_ring[];   // [wave][slot < 3][WG_SLOT_BYTES]
+    // slot of a step: its size, where the X operand (or the coordinates, 256 bytes further the latent term) and gy start
+    constexpr int SLOT = S32 ? WG32_SLOT_BYTES : WG_SLOT_BYTES, XOFF = S32 ? 512 : 4096, GOFF = S32 ? 1024 : 4096 + 1024;
+    // B stage [stage][part][octet][k row]: two octets per 16-column step (three parts reserved), four per 32-column step
+    constexpr int BPART = S32 ? 512 : 256, BSTAGE = S32 ? NP * 512 : 768;
+    __shared__ __attribute__((aligned(16))) uint4 Bs[2 * BSTAGE];
+    extern __shared__ __attribute__((aligned(16))) unsigned char wg_ring[];   // [wave][slot < 3][SLOT]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int tile_m, tile_k, split;
@@ -1167,7 +1189,7 @@ void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const flo
     const int m0 = tile_m * DX6_ROWS, k0 = tile_k * 128;
     const int nbeg = split * nchunk;
     const int nend = min(N, nbeg + nchunk);
-    const int nk = (nend - nbeg) >> 4;
+    const int nk = (nend - nbeg) >> (S32 ? 5 : 4);
     const int khalf = lane >> 5;
     if (nk <= 0) {                                      // empty reduction slice: zero partial
 #pragma unroll
@@ -1221,10 +1243,11 @@ void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const flo
     const int kx = min(k0 + kr, Kf - 1);
     const float b_ok = (k0 + kr) < Kf ? 1.f : 0.f;
     // X: this thread's own 16 bytes (4 consecutive n of its row); XVA: dword lane & 31 of the step's 32 coordinates
-    const float* x_src = XVA ? va.xr + 2 * (long)nbeg + (lane & 31) : X + (long)kx * ldx + nbeg + 4 * q4;
+    // (32-column steps: dword lane of the step's 64)
+    const float* x_src = XVA ? va.xr + 2 * (long)nbeg + (S32 ? lane : lane & 31) : X + (long)kx * ldx + nbeg + 4 * q4;
     const float* lb_src = XVA ? (va.lb ? va.lb + kx : va.bc + kx) : nullptr;   // no latent term: a valid dummy, scaled by 0
     const float lb_on = (XVA && va.lb) ? 1.f : 0.f;
-    const float* g_src = VIRT ? vg.gy + nbeg + (lane & 15) : nullptr;
+    const float* g_src = VIRT ? vg.gy + nbeg + (lane & (STEP - 1)) : nullptr;
     const float va_w0 = XVA ? va.wc[2 * kx] : 0.f, va_w1 = XVA ? va.wc[2 * kx + 1] : 0.f, va_bc = XVA ? va.bc[kx] : 0.f;
     float sx = 1.f;
     if (NP == 2) {
@@ -1233,12 +1256,14 @@ void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const flo
         else sx = h3_scale(hs.amax_x[0]);
     }
     const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)wg_ring +
-                              (unsigned)(wave * 3 * WG_SLOT_BYTES);
-    const unsigned char* ring = wg_ring + wave * 3 * WG_SLOT_BYTES;
+                              (unsigned)(wave * 3 * SLOT);
+    const unsigned char* ring = wg_ring + wave * 3 * SLOT;
+    // 32-column steps: the image of the step being fetched, by compare-and-increment (Np % 32 == 0: a step lies in ONE image)
+    int img = S32 ? nbeg / va.Np : 0, img_end = S32 ? (img + 1) * va.Np : 0;
     auto dma_step = [&](int slot, int t) {
-        const int na = nbeg + 16 * t;                    // wave-uniform; a 16-wide step never straddles a column tile
+        const int na = nbeg + STEP * t;                  // wave-uniform; a 16-wide step never straddles a column tile
         const long off = (long)(na >> atile.sh) * atile.ts + (na & atile.mask);
-        const unsigned sl = ring_lds + (unsigned)(slot * WG_SLOT_BYTES);
+        const unsigned sl = ring_lds + (unsigned)(slot * SLOT);
         if (ABF) {
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
@@ -1262,11 +1287,15 @@ void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const flo
             }
         }
         if (XVA) {
-            const float* sx = x_src + 32 * t;
-            const unsigned dx = sl + 4096u;
+            const float* sx = x_src + 2 * STEP * t;
+            const unsigned dx = sl + (unsigned)XOFF;
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" :: "s"(dx), "v"(sx) : "memory", "m0");
-            const float* slb = lb_src + (long)(lb_on != 0.f ? na / va.Np : 0) * Kf;
-            const unsigned dl = sl + 4096u + 256u;
+            if (S32 && na >= img_end) {                  // (the steps come in order; a clamped repeat stays where it is)
+                ++img;
+                img_end += va.Np;
+            }
+            const float* slb = lb_src + (long)(lb_on != 0.f ? (S32 ? img : na / va.Np) : 0) * Kf;
+            const unsigned dl = sl + (unsigned)XOFF + 256u;
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" :: "s"(dl), "v"(slb) : "memory", "m0");
         } else {
             const float* sx = x_src + 16 * t;
@@ -1274,8 +1303,8 @@ void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const flo
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" :: "s"(dx), "v"(sx) : "memory", "m0");
         }
         if (VIRT) {
-            const float* sg = g_src + 16 * t;
-            const unsigned dg = sl + 4096u + 1024u;
+            const float* sg = g_src + STEP * t;
+            const unsigned dg = sl + (unsigned)GOFF;
             asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" :: "s"(dg), "v"(sg) : "memory", "m0");
         }
     };
@@ -1287,7 +1316,7 @@ void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const flo
         for (int h = 0; h < 2; ++h)
             a_at[i][h] = (2 * i + ((lane >> 4) & 1)) * 1024 + (lane & 15) * 64 + (((2 * khalf + h) ^ ((lane >> 2) & 3)) * 16);
     auto read_a = [&](int slot, float4 (&r)[2][2], float4 (&gq)[2]) {
-        const unsigned char* sl = ring + slot * WG_SLOT_BYTES;
+        const unsigned char* sl = ring + slot * SLOT;
         if (ABF) {                                       // the cell of fragment i: lane-linear, as the DMA left it
 #pragma unroll
             for (int i = 0; i < 2; ++i) r[i][0] = *reinterpret_cast<const float4*>(sl + i * 1024 + 16 * lane);
@@ -1308,11 +1337,11 @@ void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const flo
         }
     };
     const bool xva_lrelu = XVA && va.act == ACT_LRELU;
-    auto read_x = [&](int slot) -> float4 {
-        const unsigned char* sl = ring + slot * WG_SLOT_BYTES + 4096;
+    auto read_x = [&](int slot, int half = 0) -> float4 {  // half: the 16-column half of a 32-column step
+        const unsigned char* sl = ring + slot * SLOT + XOFF;
         if (XVA) {
-            const float4 c0 = *reinterpret_cast<const float4*>(sl + 32 * q4);
-            const float4 c1 = *reinterpret_cast<const float4*>(sl + 32 * q4 + 16);
+            const float4 c0 = *reinterpret_cast<const float4*>(sl + 128 * half + 32 * q4);
+            const float4 c1 = *reinterpret_cast<const float4*>(sl + 128 * half + 32 * q4 + 16);
             const float lbv = *reinterpret_cast<const float*>(sl + 256 + 4 * lane) * lb_on;
             if (xva_lrelu) {                             // straight-line LeakyReLU (see dense_x6_kernel: no per-value branches in the loop)
                 const float p0 = dec_l0_pre(va_w0, va_w1, va_bc, lbv, c0.x, c0.y), p1 = dec_l0_pre(va_w0, va_w1, va_bc, lbv, c0.z, c0.w);
@@ -1397,17 +1426,22 @@ void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const flo
     // the row's validity and (h3) its power-of-two scale are ONE per-thread factor: the values are born scaled, s[k] is
     // accumulated scaled and unscaled once at the end -- exact, bitwise what scaling at the split gave
     const float bsx = NP == 2 ? b_ok * sx : b_ok;
-    auto store_b = [&](int stage, const float4& x, int slot, bool real_step) {
+    auto store_b = [&](int stage, const float4& x, int slot, bool real_step, int half = 0) {
         unsigned hw[2], mw[2], lw[2];
         float4 gm = make_float4(bsx, bsx, bsx, bsx);
         if (LRF) {                                       // gy of this thread's four columns joins the X values
-            const float4 g4 = *reinterpret_cast<const float4*>(ring + slot * WG_SLOT_BYTES + 4096 + 1024 + 16 * q4);
+            const float4 g4 = *reinterpret_cast<const float4*>(ring + slot * SLOT + GOFF + 64 * half + 16 * q4);
             gm = make_float4(g4.x * bsx, g4.y * bsx, g4.z * bsx, g4.w * bsx);
         }
         const float v[4] = {x.x * gm.x, x.y * gm.y, x.z * gm.z, x.w * gm.w};
         // s[k] of the two-valued form: this thread's share of row kr (the clamped step past the end must not count)
-        if (LRF && real_step) ssum += (v[0] + v[1]) + (v[2] + v[3]);
-        uint2* dst = reinterpret_cast<uint2*>(Bs + stage * 768 + (q4 >> 1) * 128 + kr) + (q4 & 1);
+        if (LRF && real_step) {
+            // (the compiler contracts this sum, and the 16-column instances have always rounded it as written out for the
+            // 32-column ones, whose two halves it would otherwise contract differently from one another)
+            if (S32) ssum += __fmaf_rn(x.x, gm.x, v[1]) + __fmaf_rn(x.z, gm.z, v[3]);
+            else ssum += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+        uint2* dst = reinterpret_cast<uint2*>(Bs + stage * BSTAGE + (2 * half + (q4 >> 1)) * 128 + kr) + (q4 & 1);
         if (NP == 1) {
             dst[0] = make_uint2(bf16_pair(v[0], v[1]), bf16_pair(v[2], v[3]));
             return;
@@ -1416,14 +1450,14 @@ void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const flo
 #pragma unroll
             for (int q = 0; q < 2; ++q) split2h_pair(v[2 * q], v[2 * q + 1], hw[q], lw[q]);
             dst[0] = make_uint2(hw[0], hw[1]);
-            dst[2 * 256] = make_uint2(lw[0], lw[1]);
+            dst[2 * BPART] = make_uint2(lw[0], lw[1]);
             return;
         }
 #pragma unroll
         for (int q = 0; q < 2; ++q) split3_pair(v[2 * q], v[2 * q + 1], hw[q], mw[q], lw[q]);
         dst[0] = make_uint2(hw[0], hw[1]);
-        dst[2 * 256] = make_uint2(mw[0], mw[1]);
-        dst[2 * 512] = make_uint2(lw[0], lw[1]);
+        dst[2 * BPART] = make_uint2(mw[0], mw[1]);
+        dst[4 * BPART] = make_uint2(lw[0], lw[1]);
     };
 
     f32x16 acc[2][4];
@@ -1434,57 +1468,114 @@ void dense_wgrad_x6_dma_kernel(const float* __restrict__ dY, long ldd, const flo
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    Cell16 af[2][3];
     const int tl = nk - 1;
-    {   // prologue: three steps in flight, step 0 split as soon as its slot has landed
-        dma_step(0, 0);
-        dma_step(1, min(1, tl));
-        dma_step(2, min(2, tl));
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NDMA) : "memory");
-        float4 ar[2][2], g0[2];
-        read_a(0, ar, g0);
-        virt_a(ar, g0);
-        split_a(ar, af, 0);
-        store_b(0, read_x(0), 0, true);
-    }
-    __syncthreads();
-    int s_next = 1, s_dma = 0;                           // slot of step t+1, slot the DMAs of step t+3 go to (= t % 3)
-    for (int t = 0; t < nk; ++t) {
-        const int cur = t & 1;
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NDMA) : "memory");      // slot of step t+1 has landed
-        dma_step(s_dma, min(t + 3, tl));                 // unconditional (clamped): uniform vmcnt bookkeeping
-        Cell16 an[2][3];
-        const uint4* bs = Bs + cur * 768 + khalf * 128 + (lane & 31);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            Cell16 bf[3];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) bf[p].u = bs[p * 256 + j * 32];
-            if (LRF) {                                   // exact 0 / 1 operand: ONE A part against the X parts
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int p = 0; p < NP; ++p) mfma_part<NP>(acc[i][j], af[i][0], bf[p]);
-            } else {
-                mfma_np<NP>(acc[0][j], af[0], bf);
-                mfma_np<NP>(acc[1][j], af[1], bf);
-            }
-            if (j == 0) {                                // A cells of step t+1 from the ring
-                float4 ar[2][2], gn[2];
-                read_a(s_next, ar, gn);
-                virt_a(ar, gn);
-                split_a(ar, an, min(t + 1, tl));
-            }
-            if (j == 1) store_b(cur ^ 1, read_x(s_next), s_next, t + 1 < nk);   // B cells of step t+1
+    if constexpr (S32) {
+        // 32-column steps: the cells of BOTH sub-steps of a step from one landed word, two cell sets ping-ponged by a loop
+        // unrolled by two; a thread builds its four columns of half 0, then of half 1 (s[k] sums in the 16-column order)
+        Cell16 afA[2][2][3], afB[2][2][3];               // [sub-step][fragment row group][part (one used)]
+        {   // prologue: three steps in flight, step 0 split as soon as its slot has landed
+            dma_step(0, 0);
+            dma_step(1, min(1, tl));
+            dma_step(2, min(2, tl));
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NDMA) : "memory");
+            float4 ar[2][2], g0[2];
+            read_a(0, ar, g0);
+            split_a(ar, afA[0], 0);                      // (nbeg % 32 == 0: step u of split_a's 16-column count IS sub-step u)
+            split_a(ar, afA[1], 1);
+            store_b(0, read_x(0, 0), 0, true, 0);
+            store_b(0, read_x(0, 1), 0, true, 1);
         }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) af[i][p] = an[i][p];
-        s_next = s_next == 2 ? 0 : s_next + 1;
-        s_dma = s_dma == 2 ? 0 : s_dma + 1;
-        __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
+        int s_next = 1, s_dma = 0;                       // slot of step t+1, slot the DMAs of step t+3 go to (= t % 3)
+        auto step = [&](int t, Cell16 (&afc)[2][2][3], Cell16 (&afn)[2][2][3]) {
+            const int cur = t & 1;
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NDMA) : "memory");  // slot of step t+1 has landed
+            dma_step(s_dma, min(t + 3, tl));             // unconditional (clamped): uniform vmcnt bookkeeping
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const uint4* bs = Bs + cur * BSTAGE + (2 * u + khalf) * 128 + (lane & 31);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    Cell16 bf[3];
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) bf[p].u = bs[p * BPART + j * 32];
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) mfma_part<NP>(acc[i][j], afc[u][i][0], bf[p]);
+                    if (u == 0 && j == 0) {              // A cells of step t+1 from the ring
+                        float4 ar[2][2], gn[2];
+                        read_a(s_next, ar, gn);
+                        split_a(ar, afn[0], 0);
+                        split_a(ar, afn[1], 1);
+                    }
+                    if (j == 1) store_b(cur ^ 1, read_x(s_next, u), s_next, t + 1 < nk, u);   // B cells of step t+1, half u
+                }
+            }
+            s_next = s_next == 2 ? 0 : s_next + 1;
+            s_dma = s_dma == 2 ? 0 : s_dma + 1;
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+        };
+        // (both steps of a trip unconditional, as in dense_x6_kernel)
+        int tt = 0;
+        for (; tt + 1 < nk; tt += 2) {
+            step(tt, afA, afB);
+            step(tt + 1, afB, afA);
+        }
+        if (nk & 1) step(nk - 1, afA, afB);
+    } else {
+        Cell16 af[2][3];
+        {   // prologue: three steps in flight, step 0 split as soon as its slot has landed
+            dma_step(0, 0);
+            dma_step(1, min(1, tl));
+            dma_step(2, min(2, tl));
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NDMA) : "memory");
+            float4 ar[2][2], g0[2];
+            read_a(0, ar, g0);
+            virt_a(ar, g0);
+            split_a(ar, af, 0);
+            store_b(0, read_x(0), 0, true);
+        }
+        __syncthreads();
+        int s_next = 1, s_dma = 0;                           // slot of step t+1, slot the DMAs of step t+3 go to (= t % 3)
+        for (int t = 0; t < nk; ++t) {
+            const int cur = t & 1;
+            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NDMA) : "memory");      // slot of step t+1 has landed
+            dma_step(s_dma, min(t + 3, tl));                 // unconditional (clamped): uniform vmcnt bookkeeping
+            Cell16 an[2][3];
+            const uint4* bs = Bs + cur * 768 + khalf * 128 + (lane & 31);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                Cell16 bf[3];
+#pragma unroll
+                for (int p = 0; p < NP; ++p) bf[p].u = bs[p * 256 + j * 32];
+                if (LRF) {                                   // exact 0 / 1 operand: ONE A part against the X parts
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) mfma_part<NP>(acc[i][j], af[i][0], bf[p]);
+                } else {
+                    mfma_np<NP>(acc[0][j], af[0], bf);
+                    mfma_np<NP>(acc[1][j], af[1], bf);
+                }
+                if (j == 0) {                                // A cells of step t+1 from the ring
+                    float4 ar[2][2], gn[2];
+                    read_a(s_next, ar, gn);
+                    virt_a(ar, gn);
+                    split_a(ar, an, min(t + 1, tl));
+                }
+                if (j == 1) store_b(cur ^ 1, read_x(s_next), s_next, t + 1 < nk);   // B cells of step t+1
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int p = 0; p < 3; ++p) af[i][p] = an[i][p];
+            s_next = s_next == 2 ? 0 : s_next + 1;
+            s_dma = s_dma == 2 ? 0 : s_dma + 1;
+            __builtin_amdgcn_sched_barrier(0);
+            __syncthreads();
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the clamped tail DMAs still target this wave's ring
     float sk[4] = {0.f, 0.f, 0.f, 0.f};                  // slope * s[k] of this lane's four columns
