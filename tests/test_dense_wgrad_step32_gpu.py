@@ -13,6 +13,7 @@ import torch
 
 import guardband
 from conftest import rel_err
+from dense_bits_ref import random_bits
 
 pytestmark = pytest.mark.gpu
 SLOPE = 0.01
@@ -39,14 +40,6 @@ def call(*a):
 def rnd(*shape, seed=0, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(*shape, generator=g) * scale
-
-
-def random_bits(rows, N, seed):
-    """[rows][N / 32] random int32 words and the 0 / 1 matrix they encode (bit n & 31 of word n >> 5 is column n)."""
-    g = torch.Generator().manual_seed(seed)
-    words = torch.randint(-2 ** 31, 2 ** 31, (rows, N // 32), generator=g, dtype=torch.int64)
-    mask = ((words[:, :, None] >> torch.arange(32)) & 1).reshape(rows, N).bool()
-    return words.to(torch.int32), mask
 
 
 def first_layer_fp64(xr, Wc, bc, LB, Np):
