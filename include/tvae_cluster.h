@@ -249,6 +249,54 @@ long tvae_class_frc_ws_floats(int P, int n);
 int tvae_class_frc(const float* a, const float* b, float* frc, double* sums, float* ws, long ws_floats, int P, int n,
                    float mask_radius, float mask_edge, tvae_stream_t stream);
 
+/* ---- Particle preprocessing: Fourier downsample (with the crop as its window) and background-ring normalisation ----------
+ *
+ * Downsample.  A window of M x N pixels of a frame X[B][H][W] is given by (r0, c0, M, N); it goes to m x n, 1 <= m <= M and
+ * 1 <= n <= N.  With F(ky, kx) = sum_ab x[a][b] exp(-2 pi i (ky a / M + kx b / N)) the output spectrum is
+ *     rows:     row p = 0 .. m - 1 takes source row src(p) = p for p < m div 2 and src(p) = M - m + p for every other p: the
+ *               upper block is the LAST ceil(m / 2) source rows, so for odd m the middle row comes from the signed frequency
+ *               -(m + 1) / 2.  This is the reference's slicing rule (src/image.py: F[0 : m // 2] and F[-m // 2 :]), kept exactly;
+ *     columns:  kx = 0 .. n div 2 with weight w = 1 for kx = 0 and for the Nyquist column of an even n, 2 for every other one;
+ * and the result is the real part of the inverse transform on the m x n grid times 1 / (M N) (the reference's (m n) / (M N)
+ * folded into the 1 / (m n) of the inverse).  Equivalently, with
+ *     Ry[i][a] = sum_p exp(2 pi i p i / m) exp(-2 pi i src(p) a / M),    Kx[b][j] = sum_kx w_kx exp(2 pi i kx (j / n - b / N)),
+ *     out = (Re Ry  X  Re Kx  -  Im Ry  X  Im Kx) / (M N).
+ *
+ * tvae_image_resample does not build these tables: it is a GENERIC batched sandwich product
+ *     out[b] = scale (Ar Xwin_b Br - Ai Xwin_b Bi),
+ * the tables the caller's, row-major fp32, Ar and Ai [m][M], Br and Bi [N][n]; Ai = NULL together with Bi = NULL skips the
+ * second term (one of them NULL alone is rejected).  tvae.tables.resample_tables builds the four tables of the downsample in
+ * fp64 and rounds them once.  Arithmetic: fp32 FMA chains on the fp32 matrix pipe in a fixed order (first over the
+ * window's rows, then over its columns in chunks of 64, the Ai / Bi product after the Ar / Br product of a chunk), the
+ * scale applied once at the store.  No atomics: every output is a pure function of the inputs, bitwise reproducible, and
+ * out[b] depends on image b and the tables only, not on B or the other images.  Nothing outside the window is read.
+ * out must not overlap X or a table.
+ *
+ * Normalize.  Images X[B][n][m] (n rows, m columns).  The mask is (n / 2 - i)^2 + (m / 2 - j)^2 >= radius^2 for pixel (i, j):
+ * the centre is (n / 2, m / 2), NOT ((n - 1) / 2, ..) (the reference's); evaluated exactly in fp64.  radius <= 0 means the
+ * default, min(n, m) / 2.  mu = the mean over the masked pixels and sigma = their population (ddof = 0) standard deviation,
+ * both in fp64, sigma in TWO passes (mu first, then sum (x - mu)^2: the sum-of-squares form fails on raw stacks whose mean
+ * dwarfs their spread, the case this exists for).  Each pixel is (x - mu) / sigma formed in fp64 and rounded to fp32 once;
+ * stats[b] = (mu, sigma) in fp64.  IEEE results stand: an empty mask gives NaN throughout, sigma = 0 gives +-inf or NaN.
+ * Partial sums are fp64, combined in a fixed order (per 4096 pixels: per-thread sums in ascending pixel order and a fixed tree;
+ * the groups of an image ascending): bitwise reproducible, image b's results depend on image b only.  out may be X.
+ *
+ * Supported: 1 <= B <= 2^24; 1 <= m <= M <= 1024, 1 <= n <= N <= 1024 and the window inside the frame (resample); 1 <= n, m
+ * <= 1024 (normalize); fewer than 2^31 workgroups (B ceil(m / 64) ceil(n / 64 or 128); B ceil(n m / 4096)); a finite radius; ws
+ * and stats 8-byte aligned.  Anything else returns hipErrorInvalidValue (1) and writes nothing, and the query returns 0. */
+
+/* out[B][m][n] */
+int tvae_image_resample(const float* X, const float* Ar, const float* Ai, const float* Br, const float* Bi, float* out,
+                        int B, int H, int W, int r0, int c0, int M, int N, int m, int n, float scale,
+                        tvae_stream_t stream);
+
+/* floats of workspace of tvae_image_normalize: three fp64 partials per group of 4096 pixels.  0 for unsupported arguments. */
+long tvae_image_normalize_ws_floats(int B, int n, int m);
+
+/* X[B][n][m] -> out[B][n][m] (may be X), stats[B][2] (fp64) */
+int tvae_image_normalize(const float* X, float* out, double* stats, float* ws, long ws_floats, int B, int n, int m,
+                         float radius, tvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,9 @@ SIGNATURES = {
     # Y, theta, dx, order (int32), seg (int32), avg, half, var, counts (int32), ws, ws_floats, N, C, n, K, t_scale
     'tvae_class_halves': 'pppppppppp' 'l' 'iiiif',
     'tvae_class_frc': 'pppppliiff',           # a, b, frc, sums (fp64), ws, ws_floats, P, n, mask_radius, mask_edge
+    # X, Ar, Ai (or None), Br, Bi (or None), out, B, H, W, r0, c0, M, N, m, n, scale
+    'tvae_image_resample': 'pppppp' 'iiiiiiiii' 'f',
+    'tvae_image_normalize': 'ppppliiif',      # X, out, stats (fp64), ws, ws_floats, B, n, m, radius
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
@@ -56,6 +59,7 @@ QUERIES = {
     'tvae_class_halves_ws_floats': ('iiii', 'l'),
     'tvae_frc_rings': ('i', 'i'),
     'tvae_class_frc_ws_floats': ('ii', 'l'),
+    'tvae_image_normalize_ws_floats': ('iii', 'l'),
 }
 
 _cl = None

@@ -292,6 +292,8 @@ _F64_OK |= {('tvae_tsne_repulsion', 3), ('tvae_tsne_step', 6), ('tvae_tsne_step'
 _F64_OK |= {('tvae_tsne_kl', p) for p in (6, 7, 8)}
 # ... and the ring sums of tvae_class_frc
 _F64_OK |= {('tvae_class_frc', 3)}
+# ... and the (mean, standard deviation) pairs of tvae_image_normalize
+_F64_OK |= {('tvae_image_normalize', 2)}
 
 
 def _ptr(t, name, pos):

@@ -125,3 +125,57 @@ def image_coords(n: int, m: int | None = None) -> np.ndarray:
     yg = np.linspace(1, -1, n)
     x0, x1 = np.meshgrid(xg, yg)
     return np.stack([x0.ravel(), x1.ravel()], 1).astype(np.float32)
+
+
+# ---- Fourier downsample (tvae.image; the definition is in include/tvae_cluster.h) ----------------------------------------
+def resample_source_rows(M: int, m: int) -> np.ndarray:
+    """src(p): the source spectrum row of output spectrum row p -- rows 0 .. m // 2 - 1, then the LAST ceil(m / 2) rows
+    (the reference's slicing rule F[0 : m // 2], F[-m // 2 :], kept exactly)."""
+    p = np.arange(m, dtype=np.int64)
+    return np.where(p < m // 2, p, M - m + p)
+
+
+def _unit(num: np.ndarray, den: int):
+    """cos and sin of 2 pi num / den, the argument reduced exactly in integers."""
+    a = (2.0 * math.pi / den) * np.mod(num, den).astype(np.float64)
+    return np.cos(a), np.sin(a)
+
+
+@lru_cache(maxsize=None)
+def resample_tables_f64(M: int, N: int, m: int, n: int):
+    """(Ar [m][M], Ai [m][M], Br [N][n], Bi [N][n]) in fp64: the real and imaginary parts of
+        Ry[i][a] = sum_p exp(2 pi i p i / m) exp(-2 pi i src(p) a / M),   Kx[b][j] = sum_kx w_kx exp(2 pi i kx (j / n - b / N)),
+    w = 1 for kx = 0 and the Nyquist column of an even n, 2 elsewhere.  downsample(x) = (Ar x Br - Ai x Bi) / (M N).
+    Cached per shape; the arrays are read-only."""
+    M, N, m, n = int(M), int(N), int(m), int(n)
+    if not (1 <= m <= M and 1 <= n <= N):
+        raise ValueError(f'resample_tables: need 1 <= m <= M and 1 <= n <= N, got ({M}, {N}) -> ({m}, {n})')
+    i = np.arange(m, dtype=np.int64)[:, None]
+    a = np.arange(M, dtype=np.int64)[None, :]
+    Ar, Ai = np.zeros((m, M)), np.zeros((m, M))
+    for p, s in enumerate(resample_source_rows(M, m).tolist()):
+        c, sn = _unit(p * i * M - s * a * m, m * M)
+        Ar += c
+        Ai += sn
+    b = np.arange(N, dtype=np.int64)[:, None]
+    j = np.arange(n, dtype=np.int64)[None, :]
+    Br, Bi = np.zeros((N, n)), np.zeros((N, n))
+    for kx in range(n // 2 + 1):
+        w = 1.0 if kx == 0 or (n % 2 == 0 and kx == n // 2) else 2.0
+        c, sn = _unit(kx * (j * N - b * n), n * N)
+        Br += w * c
+        Bi += w * sn
+    if m == M:
+        Ai[:] = 0.0                    # src(p) = p: Ry = sum_p exp(2 pi i p (i - a) / M) = M times the identity, exactly real
+    for t in (Ar, Ai, Br, Bi):
+        t.setflags(write=False)
+    return Ar, Ai, Br, Bi
+
+
+@lru_cache(maxsize=None)
+def resample_tables(M: int, N: int, m: int, n: int):
+    """The four tables of resample_tables_f64 rounded ONCE to fp32 (what the kernel is given).  Cached per shape."""
+    out = tuple(np.ascontiguousarray(t, dtype=np.float32) for t in resample_tables_f64(M, N, m, n))
+    for t in out:
+        t.setflags(write=False)
+    return out
