@@ -28,8 +28,8 @@ typedef void* tvae_stream_t;
 
 #define TVAE_KMEANS_MAX_RESTARTS 65535
 
-/* Still 1: the Ward, t-SNE, alignment and class-statistics entry points below were ADDED, no existing prototype or
- * meaning changed. */
+/* Still 1: the Ward, t-SNE, alignment, class-statistics, preprocessing and CTF entry points below were ADDED, no existing
+ * prototype or meaning changed. */
 int tvae_cluster_abi_version(void);          /* == 1 */
 
 /* floats of workspace for one assign / update pair: per restart G x (k*d sums, k counts, 1 changed count, 1 sum of
@@ -296,6 +296,61 @@ long tvae_image_normalize_ws_floats(int B, int n, int m);
 /* X[B][n][m] -> out[B][n][m] (may be X), stats[B][2] (fp64) */
 int tvae_image_normalize(const float* X, float* out, double* stats, float* ws, long ws_floats, int B, int n, int m,
                          float radius, tvae_stream_t stream);
+
+/* ---- CTF: a real transfer function per image, the Fourier filter of a stack with it, and its per-class power ---------------
+ *
+ * Frequencies and shapes.  Square planes n x n, R = n / 2 + 1 (integer division).  ky = 0 .. n - 1 and kx = 0 .. R - 1 in the
+ * order of numpy's fftfreq; ks(ky) is the signed frequency (ky for ky < (n + 1) / 2, ky - n for every other one);
+ * q = (ks(ky)^2 + kx^2) / n^2, formed in fp64 from the exact integer numerator.
+ *
+ * Transfer function from five fp64 coefficients per plane, coef[B][5] = (c0, c1, c2, c3, c4):
+ *     t = c2 q + c3 q^2   (turns, fp64),      H = (c0 sin 2 pi t + c1 cos 2 pi t) exp(-c4 q).
+ * t is reduced to t - rint(t) in fp64 before anything is rounded to fp32; sin, cos and exp are each within 2 ulp of fp32 (as
+ * built: sin and cos in fp64, c0 sin + c1 cos rounded to fp32 once, exp in fp32).  Contract:
+ *     |H_gpu - H_fp64| <= 8 2^-24 (|c0| + |c1|)      (for c4 q >= 0).
+ * mode = 1 replaces H by its sign: H < 0 gives -1, anything else +1.
+ * For a contrast transfer function tvae.ctf.coefficients builds the row from the reference's eight-column table exactly as
+ * src/ctf.py calls compute_2d_ctf: dfu = dfv = defocus 1e4, V = 1000 voltage, lambda = 12.2639 / sqrt(V + 0.97845e-6 V^2),
+ * w = ampcont / 100, a = apix scale, c0 = sign sqrt(1 - w^2), c1 = -sign w, c2 = -0.5 df lambda / a^2,
+ * c3 = 0.25 (cs 1e7) lambda^3 / a^4, c4 = bfactor / (4 a^2); sign = -1 is the model's convention (the filter the reference
+ * trains with is -fftshift(Re ifft2(c))).  Astigmatism (dfdiff, dfang) is IGNORED, as the reference ignores it (it passes
+ * dfu = dfv): H depends on q alone, which is also what lets the filter commute with the in-plane rotation of the alignment.
+ *
+ * Filter.  For a real plane x with X = DFT(x) on the half spectrum,
+ *     out[i][j] = (1 / n^2) sum_ky sum_kx w_kx Re( H(ky, kx) X(ky, kx) exp(2 pi i (ky i + kx j) / n) ),
+ * w_kx = 1 for kx = 0 and for the Nyquist column of an even n, 2 for every other one.  A direct DFT in four stages (rows,
+ * columns, columns back, rows back) on the fp32 matrix pipe, the twiddles from a table of n entries whose argument
+ * (i k) mod n is reduced in integers (each entry within an ulp), fp32 FMA chains in a fixed ascending order, H w applied to
+ * the spectrum in one rounding, 1 / n^2 at the store.  No atomics: bitwise reproducible, and out[b] depends on plane b and its
+ * H only, not on B.  One workgroup owns a plane from load to store.  n <= 128: the spectrum stays in LDS, and with coef
+ * neither it nor H is ever in memory; n > 128: the spectrum goes through the plane's own part of the workspace, the same
+ * launch whatever B is.
+ *
+ * Power.  tvae_ctf_power follows the order / seg rules of tvae_class_average (the section above states them): entries of
+ * `order` outside [0, N) are skipped and not counted, seg is replaced on the device by min(max(0, seg[0], ..., seg[k]), N);
+ * D[k] = the sum over the valid members of class k of H_i^2, H_i the fp32 value above (mode 0), squared and added in fp64 in
+ * ascending position within the class.  No atomics; class k's result is independent of the other classes and of K.
+ *
+ * Supported: 2 <= n <= 1024, 1 <= B, N <= 2^24, 1 <= K <= 65535, fewer than 2^31 workgroups (N ceil(n R / 256) for
+ * tvae_ctf_eval, K ceil(n R / 256) for tvae_ctf_power), mode 0 or 1, coef, D and ws 8-byte aligned.  Anything else returns
+ * hipErrorInvalidValue (1) and writes nothing, and the query returns 0. */
+
+/* H[N][n][R] fp32; mode 0 value, 1 sign */
+int tvae_ctf_eval(const double* coef, float* H, int N, int n, int mode, tvae_stream_t stream);
+
+/* floats of workspace of tvae_fourier_filter: n > 128: two complex buffers of n x (R | 1) per plane, 4 n (R | 1) B; n <= 128:
+ * 2 (one 8-byte word that is never touched: 0 stays the answer for unsupported arguments). */
+long tvae_fourier_filter_ws_floats(int B, int n);
+
+/* X plane b at X + b * x_stride (x_stride = 0: one plane for all, else >= n n); exactly one of coef [B][5] and Hp (plane b at
+ * Hp + b * h_stride, 0 = shared, else >= n R) is non-NULL; out[B][n][n] may be X itself (same base, x_stride = n n),
+ * otherwise must not overlap it (an overlap is rejected). */
+int tvae_fourier_filter(const float* X, long x_stride, const double* coef, const float* Hp, long h_stride, float* out,
+                        float* ws, long ws_floats, int B, int n, int mode, tvae_stream_t stream);
+
+/* D[K][n][R] fp64 = sum over the valid members of class k of H_i^2, counts[K] (int32) their number */
+int tvae_ctf_power(const double* coef, const int* order, const int* seg, double* D, int* counts, int N, int K, int n,
+                   tvae_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,10 @@ SIGNATURES = {
     # X, Ar, Ai (or None), Br, Bi (or None), out, B, H, W, r0, c0, M, N, m, n, scale
     'tvae_image_resample': 'pppppp' 'iiiiiiiii' 'f',
     'tvae_image_normalize': 'ppppliiif',      # X, out, stats (fp64), ws, ws_floats, B, n, m, radius
+    'tvae_ctf_eval': 'ppiii',                 # coef (fp64), H, N, n, mode
+    # X, x_stride, coef (fp64, or None), Hp (or None), h_stride, out, ws, ws_floats, B, n, mode
+    'tvae_fourier_filter': 'plpplppliii',
+    'tvae_ctf_power': 'pppppiii',             # coef (fp64), order, seg, D (fp64), counts (int32), N, K, n
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
@@ -60,6 +64,7 @@ QUERIES = {
     'tvae_frc_rings': ('i', 'i'),
     'tvae_class_frc_ws_floats': ('ii', 'l'),
     'tvae_image_normalize_ws_floats': ('iii', 'l'),
+    'tvae_fourier_filter_ws_floats': ('ii', 'l'),
 }
 
 _cl = None

@@ -294,6 +294,8 @@ _F64_OK |= {('tvae_tsne_kl', p) for p in (6, 7, 8)}
 _F64_OK |= {('tvae_class_frc', 3)}
 # ... and the (mean, standard deviation) pairs of tvae_image_normalize
 _F64_OK |= {('tvae_image_normalize', 2)}
+# ... and the coefficient rows of the CTF entry points and the power sums of tvae_ctf_power
+_F64_OK |= {('tvae_ctf_eval', 0), ('tvae_fourier_filter', 2), ('tvae_ctf_power', 0), ('tvae_ctf_power', 3)}
 
 
 def _ptr(t, name, pos):

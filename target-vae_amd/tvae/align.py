@@ -190,27 +190,50 @@ def frc(a, b, mask_radius=None, mask_edge=0.0):
     return out.reshape(lead + (R,)), sums.reshape(lead + (R, 3))
 
 
-def save_outputs(out_dir, avg, counts, particles=False):
+def save_outputs(out_dir, avg, counts, particles=False, stem='class_averages'):
     """class_averages.npy ([K][C][n][n]) and class_counts.npy; class_averages.mrcs ([K * C][n][n]) for particles; the
-    montage class_averages.jpg when matplotlib is present (stderr says so when it is not)."""
+    montage class_averages.jpg when matplotlib is present (stderr says so when it is not).  Another `stem` (the
+    CTF-corrected averages, class_averages_ctf) names the three files and leaves class_counts.npy alone."""
     from . import figures
     avg, counts = np.asarray(avg, dtype=np.float32), np.asarray(counts)
-    np.save(os.path.join(out_dir, 'class_averages.npy'), avg)
-    np.save(os.path.join(out_dir, 'class_counts.npy'), counts)
+    np.save(os.path.join(out_dir, stem + '.npy'), avg)
+    if stem == 'class_averages':
+        np.save(os.path.join(out_dir, 'class_counts.npy'), counts)
     if particles:
         from src import mrc
-        with open(os.path.join(out_dir, 'class_averages.mrcs'), 'wb') as f:
+        with open(os.path.join(out_dir, stem + '.mrcs'), 'wb') as f:
             mrc.write(f, avg.reshape(-1, avg.shape[-2], avg.shape[-1]))
     try:
         figures._plt()
     except ImportError as e:
-        print('# matplotlib is not available ({}): class_averages.jpg is skipped'.format(e), file=sys.stderr)
+        print('# matplotlib is not available ({}): {}.jpg is skipped'.format(e, stem), file=sys.stderr)
         return
-    figures.save_class_averages(out_dir, avg, counts)
+    figures.save_class_averages(out_dir, avg, counts, stem + '.jpg')
 
 
 # ---- class_averages.py: the averages from the files a clustering run wrote ------------------------------------------------
-def build_parser() -> argparse.ArgumentParser:
+def add_ctf_flags(p, corrections, wiener=True):
+    """--ctf, --ctf-correct and --scale (and --wiener-tau): the CTF correction of class_averages.py and class_resolution.py."""
+    p.add_argument('--ctf', default=None, help='CTF parameters, one row per image (the eight-column table of training): '
+                                               'also write the CTF-corrected results')
+    p.add_argument('--ctf-correct', default=corrections[0], choices=list(corrections), help='phase flipping or Wiener weights')
+    if wiener:
+        p.add_argument('--wiener-tau', default=0.1, type=float, help='regularisation of the Wiener weights, 1 / SNR')
+    p.add_argument('--scale', default=1, type=float, help='downsampling factor of the stack against the pixel size in --ctf')
+
+
+def load_ctf_coefficients(path, n_images, scale=1):
+    """The rows of --ctf as tvae.ctf.coefficients (fp64 [N][5]); one row per image is required."""
+    from src import ctf as C
+    from . import ctf
+    table = C.parse_ctf(path)
+    if len(table) != n_images:
+        raise SystemExit(f'--ctf holds {len(table)} rows for {n_images} images: one row per image is required')
+    return ctf.coefficients(table, scale=scale)
+
+
+def build_parser(ctf=False) -> argparse.ArgumentParser:
+    """ctf=True adds the CTF flags (what class_averages.py parses); the default is the parser without them."""
     p = argparse.ArgumentParser('Aligned 2-D class averages of a clustered stack')
     p.add_argument('--stack', required=True, help='the images (.npy, .mrc or .mrcs): [N][n][n] or [N][C][n][n]')
     p.add_argument('--rotations', required=True, help='rotations.npy of the clustering run')
@@ -223,6 +246,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--out-dir', default='.', help='where class_averages.npy, class_counts.npy and the figure go')
     p.add_argument('--write-aligned', action='store_true', help='also write the aligned images, aligned.npy')
     p.add_argument('-d', '--device', type=int, default=0)
+    if ctf:
+        add_ctf_flags(p, ('wiener', 'flip'))
     return p
 
 
@@ -244,7 +269,7 @@ def load_stack(path, crop=0):
 
 
 def run(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser(ctf=True).parse_args(argv)
     if not torch.cuda.is_available() or args.device == -1:
         raise SystemExit('the MI355X build has no CPU compute path')
     torch.cuda.set_device(args.device)
@@ -259,10 +284,19 @@ def run(argv=None):
     try:
         avg, counts = class_averages(images, theta, dx, clusters, args.n_clusters, t)
         aligned = align_stack(images, theta, dx, t) if args.write_aligned else None
+        corrected = None
+        if args.ctf:
+            from . import ctf
+            coef = load_ctf_coefficients(args.ctf, images.shape[0], args.scale)
+            corrected = ctf.class_averages_ctf(images, theta, dx, clusters, coef, args.n_clusters, t, args.ctf_correct,
+                                               args.wiener_tau)
     except TvaeHipError as e:
         raise SystemExit(str(e)) from e
     os.makedirs(args.out_dir, exist_ok=True)
     save_outputs(args.out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles)
+    if corrected is not None:
+        save_outputs(args.out_dir, corrected[0].cpu().numpy(), corrected[1].cpu().numpy(), particles, 'class_averages_ctf')
+        np.save(os.path.join(args.out_dir, 'class_ctf_power.npy'), corrected[2].cpu().numpy())
     if aligned is not None:
         np.save(os.path.join(args.out_dir, 'aligned.npy'), aligned.cpu().numpy())
     print('# class averages of {} images in {} classes: {}'.format(images.shape[0], avg.shape[0], args.out_dir),

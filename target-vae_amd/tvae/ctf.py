@@ -1,0 +1,216 @@
+"""CTF correction on the GPU: the contrast transfer function of every particle from five fp64 coefficients, the per-image
+Fourier filter of a stack (multiply by H, or by its sign: phase flipping), the reference's real-space filter bank, and
+CTF-corrected (phase-flipped or Wiener-weighted) aligned class averages.
+
+Training models a particle as y = h_i * y_mu with a per-image CTF kernel h_i, so the particles of one class, which sit
+at different defoci, partly cancel in a plain average beyond the first CTF zero.  `class_averages_ctf` undoes that:
+  flip     every particle is multiplied by sign(H_i) in Fourier space before it is aligned and averaged;
+  wiener   avg_k = IDFT( (1 / m_k) sum_i H_i X_i  /  ((1 / m_k) sum_i H_i^2 + tau) ), tau = 1 / SNR.
+H is isotropic (astigmatism is ignored, as the reference ignores it), so the filter commutes with the in-plane rotation
+of the alignment and may be applied before it (up to the bilinear resampling).
+
+include/tvae_cluster.h (last section) states the definitions; the kernels are tvae_ctf_eval, tvae_fourier_filter and
+tvae_ctf_power of libtvae_cluster.so.  No FFT library: a direct DFT on the fp32 matrix pipe for any n, odd and prime
+sizes included, bitwise reproducible and independent of the batch.  There is no CPU fallback; `coefficients` is host
+arithmetic in fp64.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _cluster_lib as CL
+from ._lib import TvaeHipError
+
+COLUMNS = ('defocus', 'cs', 'voltage', 'apix', 'bfactor', 'ampcont', 'dfdiff', 'dfang')
+MODES = {'multiply': 0, 'flip': 1, 0: 0, 1: 1}
+WS_FLOATS = 1 << 26               # bound of the workspace of one tvae_fourier_filter call: 256 MB
+MAX_PLANES = 1 << 24
+
+
+def _column(params, name):
+    if isinstance(params, np.ndarray):
+        if params.ndim != 2 or params.shape[1] != len(COLUMNS):
+            raise ValueError(f'coefficients: an array must be [N][8] ({" ".join(COLUMNS)}), got {params.shape}')
+        return np.asarray(params[:, COLUMNS.index(name)], dtype=np.float64)
+    return np.asarray(params[name], dtype=np.float64).reshape(-1)
+
+
+def coefficients(params, scale=1, sign=-1):
+    """The reference's eight-column table (a DataFrame of src.ctf.parse_ctf, a mapping of columns or an [N][8] array) ->
+    coef fp64 [N][5] = (c0, c1, c2, c3, c4) with H = (c0 sin 2 pi t + c1 cos 2 pi t) exp(-c4 q), t = c2 q + c3 q^2 and
+    q = |k|^2 / n^2: exactly src.ctf.compute_2d_ctf as src.ctf.ctf_filter calls it, times `sign`.  sign = -1 is the model's
+    convention (the filter the reference trains with is -fftshift(Re ifft2(c))).  dfdiff and dfang are ignored."""
+    if sign not in (-1, 1):
+        raise ValueError(f'coefficients: sign must be -1 or 1, got {sign!r}')
+    df = _column(params, 'defocus') * 10000.0
+    volt = _column(params, 'voltage') * 1000.0
+    cs = _column(params, 'cs') * 10 ** 7
+    lam = 12.2639 / np.sqrt(volt + 0.97845e-6 * volt ** 2)
+    w = _column(params, 'ampcont') / 100
+    a = _column(params, 'apix') * scale
+    out = np.empty((df.shape[0], 5), dtype=np.float64)
+    out[:, 0] = sign * np.sqrt(1 - w ** 2)
+    out[:, 1] = -sign * w
+    out[:, 2] = -0.5 * df * lam / a ** 2
+    out[:, 3] = 0.25 * cs * lam ** 3 / a ** 4
+    out[:, 4] = _column(params, 'bfactor') / (4 * a ** 2)
+    return out
+
+
+def _mode(mode):
+    try:
+        return MODES[mode]
+    except (KeyError, TypeError):
+        raise TvaeHipError(f"mode must be 'multiply' (0) or 'flip' (1), got {mode!r}") from None
+
+
+def _coef_tensor(coef, device, what):
+    t = torch.as_tensor(np.asarray(coef, dtype=np.float64) if not torch.is_tensor(coef) else coef)
+    if t.dim() != 2 or t.shape[1] != 5 or t.shape[0] < 1:
+        raise TvaeHipError(f'{what}: coef must be [N][5], got {tuple(t.shape)}')
+    return t.to(device=device, dtype=torch.float64).contiguous()
+
+
+def _device(device):
+    if not torch.cuda.is_available():
+        raise TvaeHipError('tvae.ctf needs a GPU (no CPU fallback)')
+    return torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def transfer(coef, n, mode='multiply', device=None):
+    """coef [N][5] -> H fp32 [N][n][n // 2 + 1] on the GPU: the transfer function (or, mode 'flip', its sign) at the
+    frequencies of numpy's rfft2 layout."""
+    dev = _device(device)
+    c = _coef_tensor(coef, dev, 'transfer')
+    N, n = c.shape[0], int(n)
+    if not (2 <= n <= 1024 and N <= MAX_PLANES):
+        raise TvaeHipError(f'transfer: N={N}, n={n} outside the supported range (N <= 2^24, 2 <= n <= 1024)')
+    H = torch.empty(N, n, n // 2 + 1, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        CL.call('tvae_ctf_eval', c, H, N, n, _mode(mode))
+    return H
+
+
+def _filter(x, x_stride, coef, planes, h_stride, out, n, mode, chunk=None):
+    """tvae_fourier_filter over the B planes of `out` in slices that bound the workspace (a plane's result does not depend
+    on the slice it is in)."""
+    B = out.numel() // (n * n)
+    per = CL.query('tvae_fourier_filter_ws_floats', 1, n)
+    if per <= 0 or B < 1:
+        raise TvaeHipError(f'fourier filter: n={n} with {B} planes outside the supported range (2 <= n <= 1024)')
+    step = max(1, min(B, MAX_PLANES, WS_FLOATS // per if chunk is None else int(chunk)))
+    wsf = CL.query('tvae_fourier_filter_ws_floats', step, n)
+    ws = torch.empty(wsf // 2, dtype=torch.float64, device=out.device).view(torch.float32)
+    xf, of = x.reshape(-1), out.reshape(-1)
+    with torch.cuda.device(out.device):
+        for b0 in range(0, B, step):
+            b1 = min(b0 + step, B)
+            xs = xf[b0 * x_stride:b1 * x_stride] if x_stride else xf
+            cs = coef[b0:b1] if coef is not None else None
+            hs = None
+            if planes is not None:
+                hs = planes.reshape(-1)[b0 * h_stride:b1 * h_stride] if h_stride else planes.reshape(-1)
+            CL.call('tvae_fourier_filter', xs, x_stride, cs, hs, h_stride, of[b0 * n * n:b1 * n * n], ws, wsf, b1 - b0, n,
+                    mode)
+    return out
+
+
+def filter_stack(images, coef=None, planes=None, mode='multiply', inplace=False, chunk=None):
+    """images [N][n][n] or [N][C][n][n] (contiguous CUDA fp32) -> Re IDFT(H_i DFT(image_i)), same shape.  Exactly one of
+    coef ([N][5] fp64, host or device: H is formed in registers, never stored) and planes ([N][n][R] or one shared [n][R],
+    CUDA fp32, R = n // 2 + 1).  The channels of an image share its row.  mode 'flip' multiplies by sign(H) instead.
+    inplace overwrites `images`.  chunk: planes per launch (default: what keeps the workspace within 256 MB)."""
+    if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.float32 and images.is_contiguous()):
+        raise TvaeHipError('filter_stack: images must be a contiguous CUDA fp32 tensor (no CPU fallback)')
+    if images.dim() not in (3, 4) or images.shape[-1] != images.shape[-2]:
+        raise TvaeHipError(f'filter_stack: images must be [N][n][n] or [N][C][n][n] (square), got {tuple(images.shape)}')
+    if (coef is None) == (planes is None):
+        raise TvaeHipError('filter_stack: exactly one of coef and planes')
+    N, n = images.shape[0], images.shape[-1]
+    C = images.shape[1] if images.dim() == 4 else 1
+    R = n // 2 + 1
+    m = _mode(mode)
+    c = p = None
+    h_stride = 0
+    if coef is not None:
+        c = _coef_tensor(coef, images.device, 'filter_stack')
+        if c.shape[0] != N:
+            raise TvaeHipError(f'filter_stack: coef must hold N = {N} rows, got {c.shape[0]}')
+        if C > 1:
+            c = c.repeat_interleave(C, 0).contiguous()
+    else:
+        p = planes
+        if not (torch.is_tensor(p) and p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+                and p.device == images.device):
+            raise TvaeHipError('filter_stack: planes must be a contiguous CUDA fp32 tensor on the device of images')
+        if tuple(p.shape) == (N, n, R):
+            h_stride = n * R
+            if C > 1:
+                p = p.repeat_interleave(C, 0).contiguous()
+        elif tuple(p.shape) != (n, R):
+            raise TvaeHipError(f'filter_stack: planes must be [{N}][{n}][{R}] or [{n}][{R}], got {tuple(p.shape)}')
+    out = images if inplace else torch.empty_like(images)
+    return _filter(images, n * n, c, p, h_stride, out, n, m, chunk)
+
+
+def filter_bank(params, n, scale=1, device=None, chunk=None):
+    """src.ctf.ctf_filter(params, n, n, scale) on the device: fp32 [N][n][n], the real-space kernels the model convolves
+    with, -fftshift(Re ifft2(c)) for odd and even n -- the filter (sign = -1) of ONE shared plane, a delta at
+    (n // 2, n // 2)."""
+    dev = _device(device)
+    n = int(n)
+    rows = coefficients(params, scale, -1)
+    if rows.shape[0] == 0:
+        return torch.zeros(0, n, n, dtype=torch.float32, device=dev)
+    c = _coef_tensor(rows, dev, 'filter_bank')
+    delta = torch.zeros(n, n, dtype=torch.float32, device=dev)
+    delta[n // 2, n // 2] = 1.0
+    out = torch.empty(c.shape[0], n, n, dtype=torch.float32, device=dev)
+    return _filter(delta, 0, c, None, 0, out, n, 0, chunk)
+
+
+def power(coef, labels, n, n_clusters=None, device=None):
+    """-> (D fp64 [K][n][R], counts int32 [K]): D[k] = sum of H_i^2 over the images with label k (tvae_ctf_power)."""
+    from . import align
+    dev = _device(device)
+    c = _coef_tensor(coef, dev, 'power')
+    N, n = c.shape[0], int(n)
+    lab = torch.as_tensor(labels)
+    if lab.dim() != 1 or lab.numel() != N:
+        raise TvaeHipError(f'power: labels must hold N = {N} entries, got {tuple(lab.shape)}')
+    lab = lab.to(dev)
+    K = int(n_clusters) if n_clusters is not None else int(lab.max()) + 1
+    if not (1 <= K <= align.MAX_CLUSTERS and 2 <= n <= 1024 and N <= MAX_PLANES):
+        raise TvaeHipError(f'power: N={N}, K={K}, n={n} outside the supported range')
+    order, seg, _ = align.segments(lab, K)
+    D = torch.empty(K, n, n // 2 + 1, dtype=torch.float64, device=dev)
+    counts = torch.empty(K, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        CL.call('tvae_ctf_power', c, order, seg, D, counts, N, K, n)
+    return D, counts
+
+
+def class_averages_ctf(images, theta, dx, labels, coef, n_clusters=None, t_scale=1.0, correct='wiener', tau=0.1):
+    """CTF-corrected aligned class averages -> (avg fp32 [K][C][n][n], counts int32 [K], D fp64 [K][n][R]).
+    images [N][C][n][n], theta, dx, labels, n_clusters, t_scale as tvae.align.class_averages; coef [N][5].
+      'flip'    align.class_averages of the phase-flipped stack;
+      'wiener'  x' = H_i x_i;  N_k = the aligned mean of x' over the m_k members;  G_k = 1 / (D_k / max(m_k, 1) + tau) formed in
+                fp64 and rounded once;  avg_k = the filter of N_k with the plane G_k.  tau is 1 / SNR.
+    An empty class gives zeros.  D[k] = sum of H_i^2 over the class (both corrections return it)."""
+    from . import align
+    if correct not in ('wiener', 'flip'):
+        raise TvaeHipError(f"class_averages_ctf: correct must be 'wiener' or 'flip', got {correct!r}")
+    N, C, n, K, lab = align._check_labels(images, theta, dx, labels, n_clusters, 'class_averages_ctf')
+    c = _coef_tensor(coef, images.device, 'class_averages_ctf')
+    if c.shape[0] != N:
+        raise TvaeHipError(f'class_averages_ctf: coef must hold N = {N} rows, got {c.shape[0]}')
+    if not float(tau) > 0:
+        raise TvaeHipError(f'class_averages_ctf: tau = {tau} must be positive')
+    D, m = power(c, lab, n, K, images.device)
+    if correct == 'flip':
+        avg, counts = align.class_averages(filter_stack(images, coef=c, mode='flip'), theta, dx, lab, K, t_scale)
+        return avg, counts, D
+    mean, counts = align.class_averages(filter_stack(images, coef=c, mode='multiply'), theta, dx, lab, K, t_scale)
+    G = (1.0 / (D / m.clamp(min=1).to(torch.float64)[:, None, None] + float(tau))).to(torch.float32).contiguous()
+    return filter_stack(mean, planes=G), counts, D

@@ -206,6 +206,11 @@ def _load_ctf(args, n_train, n_test, n, shard=None):
     if shard is not None:
         (a0, a1), (b0, b1) = dp.shard_bounds(n_train, *shard), dp.shard_bounds(n_test, *shard)
         ptr, pte = ptr.iloc[a0:a1].reset_index(drop=True), pte.iloc[b0:b1].reset_index(drop=True)
+    if os.environ.get('TVAE_CTF_GPU') == '1':
+        # the same filter bank from tvae_fourier_filter (tvae.ctf.filter_bank), to fp32 rounding of the host's
+        from . import ctf
+        return (ctf.filter_bank(ptr, kn, scale=args.scale).cpu().unsqueeze(1),
+                ctf.filter_bank(pte, kn, scale=args.scale).cpu().unsqueeze(1))
     ftr, fte = C.ctf_filter(ptr, kn, kn, scale=args.scale), C.ctf_filter(pte, kn, kn, scale=args.scale)
     return torch.from_numpy(ftr).float().unsqueeze(1), torch.from_numpy(fte).float().unsqueeze(1)
 

@@ -115,7 +115,7 @@ def save_histograms(out_dir, rot_pred, tr_pred):
     return paths
 
 
-def save_class_averages(out_dir, averages, counts):
+def save_class_averages(out_dir, averages, counts, name='class_averages.jpg'):
     """Montage of the aligned class averages [K][C][n][n]: one grey panel per class (three channels as RGB scaled to the
     panel's own range, any other number averaged over the channels), titled with the class and its number of members."""
     plt = _plt()
@@ -135,7 +135,7 @@ def save_class_averages(out_dir, averages, counts):
         else:
             ax.imshow(a.mean(0), cmap='gray')
         ax.set_title('{}: {}'.format(k, int(counts[k])), fontsize=9)
-    path = os.path.join(out_dir, 'class_averages.jpg')
+    path = os.path.join(out_dir, name)
     plt.savefig(path, bbox_inches='tight')
     plt.close(fig)
     return path

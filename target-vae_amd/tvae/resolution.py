@@ -114,7 +114,9 @@ def save_outputs(out_dir, res, threshold=0.143, apix=None):
 
 
 # ---- class_resolution.py: the same from the files a clustering run wrote --------------------------------------------------
-def build_parser() -> argparse.ArgumentParser:
+def build_parser(ctf=False) -> argparse.ArgumentParser:
+    """ctf=True adds --ctf, --ctf-correct flip and --scale (what class_resolution.py parses); the default is the parser without
+    them."""
     p = argparse.ArgumentParser('Half-set averages, variance maps and FRC resolution of the aligned 2-D class averages')
     p.add_argument('--stack', required=True, help='the images (.npy, .mrc or .mrcs): [N][n][n] or [N][C][n][n]')
     p.add_argument('--rotations', required=True, help='rotations.npy of the clustering run')
@@ -130,11 +132,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--mask-radius', default=None, type=float, help='soft mask radius in pixels; default (n - 1) / 2 - 4')
     p.add_argument('--mask-edge', default=MASK_EDGE, type=float, help='width of the raised-cosine edge in pixels')
     p.add_argument('-d', '--device', type=int, default=0)
+    if ctf:
+        align.add_ctf_flags(p, ('flip',), wiener=False)
     return p
 
 
 def run(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser(ctf=True).parse_args(argv)
     if not torch.cuda.is_available() or args.device == -1:
         raise SystemExit('the MI355X build has no CPU compute path')
     torch.cuda.set_device(args.device)
@@ -144,6 +148,11 @@ def run(argv=None):
     dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
     clusters = np.asarray(np.load(args.clusters)).reshape(-1)
     try:
+        if args.ctf:
+            # phase-flipped in place, in the chunks of tvae.ctf.filter_stack, before the one pass over the stack
+            from . import ctf
+            coef = align.load_ctf_coefficients(args.ctf, images.shape[0], args.scale)
+            ctf.filter_stack(images, coef=coef, mode='flip', inplace=True)
         res = class_resolution(images, theta, dx, clusters, args.n_clusters, align.translation_scale(args.t_inf),
                                args.mask_radius, args.mask_edge)
     except TvaeHipError as e:
