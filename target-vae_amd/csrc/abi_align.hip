@@ -9,33 +9,27 @@
 
 using namespace tvae_cluster;
 
-#define ALIGN_CHECK_LAUNCH()                     \
-    do {                                         \
-        hipError_t e__ = hipGetLastError();      \
-        if (e__ != hipSuccess) return (int)e__;  \
-    } while (0)
-
 static bool align_shape_ok(long N, long C, long n) {
-    if (N < 1 || N > ALIGN_N_MAX || C < 1 || C > ALIGN_C_MAX || n < 2 || n > ALIGN_SIDE_MAX) return false;
-    return N * C * align_tiles((int)n) <= 0x7fffffffL;        // workgroups of tvae_align_stack
+    if (N < 1 || N > PLANES_MAX || C < 1 || C > ALIGN_C_MAX || n < 2 || n > SIDE_MAX) return false;
+    return N * C * align_tiles((int)n) <= GRID_MAX;        // workgroups of tvae_align_stack
 }
 
 static bool avg_shape_ok(long N, long K, long C, long n) {
-    if (!align_shape_ok(N, C, n) || K < 1 || K > ALIGN_K_MAX) return false;
-    return avg_slots((int)N, (int)K) * C * align_tiles((int)n) <= 0x7fffffffL;
+    if (!align_shape_ok(N, C, n) || K < 1 || K > CLASSES_MAX) return false;
+    return avg_slots((int)N, (int)K) * C * align_tiles((int)n) <= GRID_MAX;
 }
 
 // tvae_class_halves: three partial sums per slot and pixel; the slot count tripled where it bounds the grid
 static bool halves_shape_ok(long N, long K, long C, long n) {
     if (!avg_shape_ok(N, K, C, n)) return false;
-    return 3 * avg_slots((int)N, (int)K) * C * align_tiles((int)n) <= 0x7fffffffL;
+    return 3 * avg_slots((int)N, (int)K) * C * align_tiles((int)n) <= GRID_MAX;
 }
 
 // workspace of tvae_class_halves: (K + 1) cleaned boundaries and two member counts per slot (int32), padded to a multiple
 // of 4 words, then the partial sums [slots][C][3][n][n]
 static long halves_ws_ints(int N, int K) { return ((long)K + 1 + 2 * avg_slots(N, K) + 3) / 4 * 4; }
 
-static bool frc_shape_ok(long P, long n) { return P >= 1 && P <= FRC_P_MAX && n >= 2 && n <= FRC_SIDE_MAX; }
+static bool frc_shape_ok(long P, long n) { return P >= 1 && P <= FRC_P_MAX && n >= 2 && n <= SIDE_MAX; }
 
 // workspace: (K + 1) cleaned boundaries and one member count per slot (int32), padded to a multiple of 4 words, then the
 // partial sums [slots][C][n][n]
@@ -55,8 +49,8 @@ int tvae_align_stack(const float* Y, const float* theta, const float* dx, float*
     if (!align_shape_ok(N, C, n) || !Y || !theta || !dx || !out || out == Y) return (int)hipErrorInvalidValue;
     const int tiles = align_tiles(n);
     const unsigned grid = (unsigned)((long)N * C * tiles);
-    align_stack_kernel<<<grid, ALIGN_TILE, 0, (hipStream_t)stream>>>(Y, theta, dx, out, C, n, tiles, t_scale);
-    ALIGN_CHECK_LAUNCH();
+    align_stack_kernel<<<grid, ALIGN_TILE, 0, S(stream)>>>(Y, theta, dx, out, C, n, tiles, t_scale);
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 
@@ -70,14 +64,14 @@ int tvae_class_average(const float* Y, const float* theta, const float* dx, cons
     int* cnt = clean + (K + 1);
     float* part = ws + ints;
     const int tiles = align_tiles(n);
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = S(stream);
     avg_seg_kernel<<<1, ALIGN_TILE, 0, s>>>(seg, clean, K, N);
-    ALIGN_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     avg_accum_kernel<<<(unsigned)(slots * C * tiles), ALIGN_TILE, 0, s>>>(Y, theta, dx, order, clean, part, cnt, N, C, n,
                                                                          K, tiles, t_scale);
-    ALIGN_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     avg_reduce_kernel<<<(unsigned)((long)K * C * tiles), ALIGN_TILE, 0, s>>>(part, cnt, clean, avg, C, n, tiles);
-    ALIGN_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 
@@ -97,39 +91,39 @@ int tvae_class_halves(const float* Y, const float* theta, const float* dx, const
     int* cnt = clean + (K + 1);
     float* part = ws + ints;
     const int tiles = align_tiles(n);
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = S(stream);
     avg_seg_kernel<<<1, ALIGN_TILE, 0, s>>>(seg, clean, K, N);
-    ALIGN_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     halves_accum_kernel<<<(unsigned)(slots * C * tiles), ALIGN_TILE, 0, s>>>(Y, theta, dx, order, clean, part, cnt, N, C,
                                                                             n, K, tiles, t_scale);
-    ALIGN_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     halves_reduce_kernel<<<(unsigned)((long)K * C * tiles), ALIGN_TILE, 0, s>>>(part, cnt, clean, avg, half, var, counts,
                                                                                K, C, n, tiles);
-    ALIGN_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 
-int tvae_frc_rings(int n) { return frc_shape_ok(1, n) ? frc_half(n) : 0; }
+int tvae_frc_rings(int n) { return frc_shape_ok(1, n) ? half_side(n) : 0; }
 
 long tvae_class_frc_ws_floats(int P, int n) { return frc_shape_ok(P, n) ? P * frc_plane_floats(n) : 0; }
 
 int tvae_class_frc(const float* a, const float* b, float* frc, double* sums, float* ws, long ws_floats, int P, int n,
                    float mask_radius, float mask_edge, tvae_stream_t stream) {
     if (!frc_shape_ok(P, n) || !a || !b || !frc || !sums || !ws) return (int)hipErrorInvalidValue;
-    if (!(mask_radius - mask_radius == 0.f) || !(mask_edge - mask_edge == 0.f) || mask_edge < 0.f)   // NaN, +-inf
+    if (!finite(mask_radius) || !finite(mask_edge) || mask_edge < 0.f)
         return (int)hipErrorInvalidValue;
-    if (ws_floats < P * frc_plane_floats(n) || (reinterpret_cast<size_t>(ws) & 7)) return (int)hipErrorInvalidValue;
-    const int H = frc_half(n);
+    if (ws_floats < P * frc_plane_floats(n) || !aligned8(ws)) return (int)hipErrorInvalidValue;
+    const int H = half_side(n);
     float2* G = reinterpret_cast<float2*>(ws);                // [P][2][n][H] complex
     float* prod = ws + 4L * P * n * H;                        // [P][3][n][H]
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = S(stream);
     frc_rows_kernel<<<dim3((n + FRC_ROWS - 1) / FRC_ROWS, P, 2), FRC_TILE, 0, s>>>(a, b, G, n, mask_radius, mask_edge);
-    ALIGN_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     const long items = (long)((n + FRC_KY - 1) / FRC_KY) * H;
     frc_cols_kernel<<<dim3((unsigned)((items + FRC_TILE - 1) / FRC_TILE), P), FRC_TILE, 0, s>>>(G, prod, n);
-    ALIGN_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     frc_rings_kernel<<<dim3((H + FRC_RING_TILE - 1) / FRC_RING_TILE, P), FRC_RING_TILE, 0, s>>>(prod, frc, sums, n);
-    ALIGN_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 

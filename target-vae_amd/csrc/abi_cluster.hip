@@ -3,15 +3,10 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tvae_cluster.h"
+#include "cluster_common.hpp"
 #include "kmeans_kernels.hpp"
 
 using namespace tvae_cluster;
-
-#define CLUSTER_CHECK_LAUNCH()                   \
-    do {                                         \
-        hipError_t e__ = hipGetLastError();      \
-        if (e__ != hipSuccess) return (int)e__;  \
-    } while (0)
 
 // R <= 65535: the restarts are the y dimension of the launch grids
 static bool shape_ok(long N, long d, long k, long R) {
@@ -38,7 +33,7 @@ int tvae_kmeans_assign(const float* Xt, long ldx, const float* C, const int* don
     const int vec = (ldx % 4 == 0) && ((reinterpret_cast<size_t>(Xt) & 15) == 0);
     const dim3 grid(pl.G, R);
     const size_t lds = (size_t)pl.KC * d * sizeof(float);
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = S(stream);
     if (d <= 4)
         kmeans_assign_kernel<4><<<grid, TILE, lds, s>>>(Xt, ldx, C, done, labels, mind2, ws, N, d, k, pl, vec);
     else if (d <= 16)
@@ -47,9 +42,9 @@ int tvae_kmeans_assign(const float* Xt, long ldx, const float* C, const int* don
         kmeans_assign_kernel<32><<<grid, TILE, lds, s>>>(Xt, ldx, C, done, labels, mind2, ws, N, d, k, pl, vec);
     else
         kmeans_assign_kernel<0><<<grid, TILE, lds, s>>>(Xt, ldx, C, done, labels, mind2, ws, N, d, k, pl, vec);
-    CLUSTER_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     kmeans_changed_sum_kernel<<<(R + 63) / 64, 64, 0, s>>>(ws, done, changed, d, k, R, pl);
-    CLUSTER_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 
@@ -58,16 +53,16 @@ int tvae_kmeans_update(const float* ws, long ws_floats, const int* done, float* 
     if (!shape_ok(N, d, k, R) || !ws || !done || !C || !inertia || !shift) return (int)hipErrorInvalidValue;
     const Plan pl = make_plan(N, d, k);
     if (ws_floats < pl.per_restart * R) return (int)hipErrorInvalidValue;
-    kmeans_update_kernel<<<R, TILE, 0, (hipStream_t)stream>>>(ws, done, C, inertia, shift, d, k, pl);
-    CLUSTER_CHECK_LAUNCH();
+    kmeans_update_kernel<<<R, TILE, 0, S(stream)>>>(ws, done, C, inertia, shift, d, k, pl);
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 
 int tvae_kmeans_mindist(const float* Xt, long ldx, const float* cnew, float* D, int N, int d, int R,
                         tvae_stream_t stream) {
     if (!shape_ok(N, d, 1, R) || ldx < N || !Xt || !cnew || !D) return (int)hipErrorInvalidValue;
-    kmeans_mindist_kernel<<<dim3((unsigned)(((long)N + TILE - 1) / TILE), R), TILE, 0, (hipStream_t)stream>>>(Xt, ldx, cnew, D, N, d);
-    CLUSTER_CHECK_LAUNCH();
+    kmeans_mindist_kernel<<<dim3((unsigned)(((long)N + TILE - 1) / TILE), R), TILE, 0, S(stream)>>>(Xt, ldx, cnew, D, N, d);
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 

@@ -3,19 +3,14 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tvae_cluster.h"
+#include "cluster_common.hpp"
 #include "tsne_kernels.hpp"
 
 using namespace tvae_cluster;
 
-#define TSNE_CHECK_LAUNCH()                      \
-    do {                                         \
-        hipError_t e__ = hipGetLastError();      \
-        if (e__ != hipSuccess) return (int)e__;  \
-    } while (0)
-
 static bool tsne_n_ok(long N) { return N >= 2 && N <= TSNE_N_MAX; }
 static bool tsne_csr_ok(const int* rowptr, const int* col, const float* val, long nnz) {
-    return rowptr && col && val && nnz >= 1 && nnz <= 0x7fffffffL;
+    return rowptr && col && val && nnz >= 1 && nnz <= 0x7fffffffL;      // (the kernels take nnz as an int)
 }
 
 extern "C" {
@@ -35,7 +30,7 @@ int tvae_knn(const float* Xt, long ldx, int* idx, float* d2, int N, int d, int K
     const int vec = (ldx % 4 == 0) && ((reinterpret_cast<size_t>(Xt) & 15) == 0);
     const int grid = (N + rows - 1) / rows;
     const size_t lds = ((size_t)d * KC + 2 * (size_t)K * rows) * sizeof(float);
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = S(stream);
     if (d <= 4)
         knn_kernel<4><<<grid, KNN_WAVE, lds, s>>>(Xt, ldx, idx, d2, N, d, K, rows, KC, vec);
     else if (d <= 16)
@@ -44,26 +39,26 @@ int tvae_knn(const float* Xt, long ldx, int* idx, float* d2, int N, int d, int K
         knn_kernel<32><<<grid, KNN_WAVE, lds, s>>>(Xt, ldx, idx, d2, N, d, K, rows, KC, vec);
     else
         knn_kernel<0><<<grid, KNN_WAVE, lds, s>>>(Xt, ldx, idx, d2, N, d, K, rows, KC, vec);
-    TSNE_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 
 int tvae_tsne_repulsion(const float* Yt, long ldy, float* rep, double* Z, float* ws, long ws_floats, int N,
                         tvae_stream_t stream) {
-    if (!tsne_n_ok(N) || ldy < N || !Yt || !rep || !Z || !ws || (reinterpret_cast<size_t>(ws) & 7) != 0)
+    if (!tsne_n_ok(N) || ldy < N || !Yt || !rep || !Z || !ws || !aligned8(ws))
         return (int)hipErrorInvalidValue;
     const TsnePlan pl = tsne_plan(N);
     if (ws_floats < 2L * pl.RT + 3L * pl.S * N) return (int)hipErrorInvalidValue;
     double* zpart = reinterpret_cast<double*>(ws);
     float* part = ws + 2L * pl.RT;
     const int vec = (ldy % 4 == 0) && ((reinterpret_cast<size_t>(Yt) & 15) == 0);
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = S(stream);
     tsne_repulsion_kernel<<<dim3(pl.RT, pl.S), TSNE_TILE, 0, s>>>(Yt, ldy, part, N, pl, vec);
-    TSNE_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     tsne_rows_kernel<<<pl.RT, TSNE_TILE, 0, s>>>(part, rep, ldy, zpart, N, pl.S);
-    TSNE_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     tsne_sum_kernel<<<1, TSNE_TILE, 0, s>>>(zpart, pl.RT, Z);
-    TSNE_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 
@@ -74,10 +69,10 @@ int tvae_tsne_step(const int* rowptr, const int* col, const float* val, long nnz
         !Yt_out || !gnorm2 || Yt_out == Yt)
         return (int)hipErrorInvalidValue;
     const int RT = tsne_plan(N).RT;
-    tsne_step_kernel<<<RT, TSNE_TILE, 0, (hipStream_t)stream>>>(rowptr, col, val, (int)nnz, Yt, rep, Z, gains, update,
+    tsne_step_kernel<<<RT, TSNE_TILE, 0, S(stream)>>>(rowptr, col, val, (int)nnz, Yt, rep, Z, gains, update,
                                                                  Yt_out, grad, gnorm2, ldy, N, exaggeration, momentum,
                                                                  learning_rate);
-    TSNE_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 
@@ -87,11 +82,11 @@ int tvae_tsne_kl(const int* rowptr, const int* col, const float* val, long nnz, 
         return (int)hipErrorInvalidValue;
     const int RT = tsne_plan(N).RT;
     if (ws_doubles < RT) return (int)hipErrorInvalidValue;
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = S(stream);
     tsne_kl_kernel<<<RT, TSNE_TILE, 0, s>>>(rowptr, col, val, (int)nnz, Yt, ldy, Z, ws, N);
-    TSNE_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     tsne_sum_kernel<<<1, TSNE_TILE, 0, s>>>(ws, RT, kl);
-    TSNE_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 

@@ -3,15 +3,10 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/tvae_cluster.h"
+#include "cluster_common.hpp"
 #include "ward_kernels.hpp"
 
 using namespace tvae_cluster;
-
-#define WARD_CHECK_LAUNCH()                      \
-    do {                                         \
-        hipError_t e__ = hipGetLastError();      \
-        if (e__ != hipSuccess) return (int)e__;  \
-    } while (0)
 
 static bool ward_shape_ok(long M, long d) { return M >= 2 && M <= WARD_M_MAX && d >= 1 && d <= 256; }
 
@@ -33,7 +28,7 @@ int tvae_ward_nn(const float* Ct, long ldc, const float* cnt, int* nn, float* nd
     const int vec = (ldc % 4 == 0) && ((reinterpret_cast<size_t>(Ct) & 15) == 0);
     const dim3 grid(pl.RT, pl.S);
     const size_t lds = (size_t)pl.KC * (d + 1) * sizeof(float);
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = S(stream);
     if (d <= 4)
         ward_nn_kernel<4><<<grid, WARD_TILE, lds, s>>>(Ct, ldc, cnt, pd, pj, M, d, pl, vec);
     else if (d <= 16)
@@ -42,9 +37,9 @@ int tvae_ward_nn(const float* Ct, long ldc, const float* cnt, int* nn, float* nd
         ward_nn_kernel<32><<<grid, WARD_TILE, lds, s>>>(Ct, ldc, cnt, pd, pj, M, d, pl, vec);
     else
         ward_nn_kernel<0><<<grid, WARD_TILE, lds, s>>>(Ct, ldc, cnt, pd, pj, M, d, pl, vec);
-    WARD_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     ward_nn_reduce_kernel<<<pl.RT, WARD_TILE, 0, s>>>(pd, pj, nn, nd, M, pl.S);
-    WARD_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 
@@ -58,13 +53,13 @@ int tvae_ward_merge(const double* C_in, long ld_in, const float* cnt_in, const i
         return (int)hipErrorInvalidValue;
     int* pos = ws;
     int* rank = ws + M;
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = S(stream);
     ward_scan_kernel<<<1, WARD_SCAN, 0, s>>>(nn, pos, rank, m_out, M);
-    WARD_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     const dim3 grid((M + WARD_TILE - 1) / WARD_TILE, d < WARD_FY ? d : WARD_FY);
     ward_apply_kernel<<<grid, WARD_TILE, 0, s>>>(C_in, ld_in, cnt_in, id_in, hmax_in, nn, pos, rank, C_out, Ct_out, ld_out,
                                                  cnt_out, id_out, hmax_out, rec_ids, rec_hs, M, d, N, base, cap);
-    WARD_CHECK_LAUNCH();
+    TVAE_CLUSTER_CHECK_LAUNCH();
     return 0;
 }
 

@@ -27,14 +27,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "cluster_common.hpp"
+
 namespace tvae_cluster {
 
 constexpr int ALIGN_TILE = 256;          // pixels per workgroup = threads per workgroup
 constexpr int AVG_CHUNK = 32;            // members of a class per partial sum
-constexpr int ALIGN_N_MAX = 1 << 24;     // images
-constexpr int ALIGN_K_MAX = 65535;       // classes
 constexpr int ALIGN_C_MAX = 1024;        // channels
-constexpr int ALIGN_SIDE_MAX = 1024;     // n
 
 struct AlignPose {
     float c, s, tx, ty;                  // cos, sin, t * dx0, t * dx1
@@ -114,6 +113,54 @@ __global__ __launch_bounds__(ALIGN_TILE) void avg_seg_kernel(const int* __restri
     }
 }
 
+// The prologue of a workgroup of avg_accum_kernel and halves_accum_kernel (grid = slots * C * tiles, tile fastest, then
+// channel): which pixel tile, channel and slot `block` is, the class that owns the slot and the chunk's members; the members'
+// image indices (-1 = skipped or behind the chunk's end) and poses go to LDS.  load() returns false for a slot that has no
+// chunk, BEFORE any barrier: both such returns depend on `block` and `clean` alone, so they are uniform over the workgroup
+// and the caller returns at once.  Otherwise it ends with the __syncthreads() behind which pose and member may be read.
+struct AvgChunk {
+    int tile, ch, slot, members;
+    __device__ __forceinline__ bool load(unsigned block, const int* clean, const int* order, const float* theta,
+                                         const float* dx, int N, int C, int K, int tiles, float t_scale, AlignPose* pose,
+                                         int* member) {
+        tile = block % tiles;
+        const long rest = block / tiles;
+        ch = (int)(rest % C);
+        slot = (int)(rest / C);
+        // the class whose slots contain `slot`: the largest k with clean[k] / AVG_CHUNK + k <= slot (strictly increasing in k)
+        int lo = 0, hi = K - 1;
+        if (clean[0] / AVG_CHUNK > slot) return false;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (clean[mid] / AVG_CHUNK + mid <= slot) lo = mid; else hi = mid - 1;
+        }
+        const int k = lo;
+        const int sk = clean[k], ek = clean[k + 1];
+        const int first = sk + (slot - (sk / AVG_CHUNK + k)) * AVG_CHUNK;
+        if (first >= ek) return false;                        // a slot that no chunk owns: nobody reads it either
+        members = min(AVG_CHUNK, ek - first);
+        if (threadIdx.x < AVG_CHUNK) {
+            int id = -1;
+            AlignPose q = {0.f, 0.f, 0.f, 0.f};
+            if ((int)threadIdx.x < members) {
+                id = order[first + threadIdx.x];
+                if (id < 0 || id >= N) id = -1;
+            }
+            if (id >= 0) {
+                const float th = theta[id];
+                q.c = cosf(th);
+                q.s = sinf(th);
+                q.tx = t_scale * dx[2 * (long)id];
+                q.ty = t_scale * dx[2 * (long)id + 1];
+            }
+            pose[threadIdx.x] = q;
+            member[threadIdx.x] = id;
+        }
+        __syncthreads();
+        return true;
+    }
+};
+
 // grid = slots * C * tiles (tile fastest, then channel).  part[slots][C][n][n], cnt[slots] (written by tile 0 of channel 0)
 __global__ __launch_bounds__(ALIGN_TILE) void avg_accum_kernel(const float* __restrict__ Y,
                                                                const float* __restrict__ theta,
@@ -123,41 +170,10 @@ __global__ __launch_bounds__(ALIGN_TILE) void avg_accum_kernel(const float* __re
                                                                int* __restrict__ cnt, int N, int C, int n, int K, int tiles,
                                                                float t_scale) {
     __shared__ AlignPose pose[AVG_CHUNK];
-    __shared__ int member[AVG_CHUNK];                         // image index, -1 = skipped
-    const int tile = blockIdx.x % tiles;
-    const long rest = blockIdx.x / tiles;
-    const int ch = (int)(rest % C);
-    const int slot = (int)(rest / C);
-    // the class whose slots contain `slot`: the largest k with clean[k] / AVG_CHUNK + k <= slot (strictly increasing in k)
-    int lo = 0, hi = K - 1;
-    if (clean[0] / AVG_CHUNK > slot) return;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (clean[mid] / AVG_CHUNK + mid <= slot) lo = mid; else hi = mid - 1;
-    }
-    const int k = lo;
-    const int sk = clean[k], ek = clean[k + 1];
-    const int first = sk + (slot - (sk / AVG_CHUNK + k)) * AVG_CHUNK;
-    if (first >= ek) return;                                  // a slot that no chunk owns: nobody reads it either
-    const int members = min(AVG_CHUNK, ek - first);
-    if (threadIdx.x < AVG_CHUNK) {
-        int id = -1;
-        AlignPose q = {0.f, 0.f, 0.f, 0.f};
-        if ((int)threadIdx.x < members) {
-            id = order[first + threadIdx.x];
-            if (id < 0 || id >= N) id = -1;
-        }
-        if (id >= 0) {
-            const float th = theta[id];
-            q.c = cosf(th);
-            q.s = sinf(th);
-            q.tx = t_scale * dx[2 * (long)id];
-            q.ty = t_scale * dx[2 * (long)id + 1];
-        }
-        pose[threadIdx.x] = q;
-        member[threadIdx.x] = id;
-    }
-    __syncthreads();
+    __shared__ int member[AVG_CHUNK];
+    AvgChunk w;
+    if (!w.load(blockIdx.x, clean, order, theta, dx, N, C, K, tiles, t_scale, pose, member)) return;
+    const int tile = w.tile, ch = w.ch, slot = w.slot, members = w.members;
     if (tile == 0 && ch == 0 && threadIdx.x == 0) {
         int v = 0;
         for (int m = 0; m < members; ++m) v += member[m] >= 0;

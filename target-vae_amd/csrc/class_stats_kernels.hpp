@@ -20,8 +20,7 @@
 // frc_rings_kernel      a thread = one ring of one plane.  For a given ky the kx of a ring form one interval, found in exact
 //                       integer arithmetic; the thread walks ky in ascending index and kx in ascending order and adds in fp64
 //                       with the Hermitian weights of the half spectrum.  A fixed order, no atomics.
-// The twiddles cos and sin of 2 pi t / n are built once per workgroup with sincospi in fp64 on the exact argument 2 t / n
-// and rounded to fp32 once (half an ulp; exact 0 and +-1 on the axes).
+// The twiddles cos and sin of 2 pi t / n are built once per workgroup (dft_twiddles of cluster_common.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,17 +28,14 @@
 
 namespace tvae_cluster {
 
-constexpr int FRC_SIDE_MAX = 1024;       // n
 constexpr int FRC_P_MAX = 65535;         // planes: the y dimension of the launch grids
 constexpr int FRC_ROWS = 8;              // rows of a plane per workgroup of stage 1
 constexpr int FRC_KY = 4;                // ky per thread of stage 2
 constexpr int FRC_TILE = 256;            // threads per workgroup of stages 1 and 2
 constexpr int FRC_RING_TILE = 64;        // threads (rings) per workgroup of the ring sums
 
-// kx = 0 .. n / 2; also the number of rings
-__host__ __device__ static inline int frc_half(int n) { return n / 2 + 1; }
 // floats of workspace per plane: the half spectra of the rows of a and b (complex) and the three products per coefficient
-static inline long frc_plane_floats(int n) { return 7L * n * frc_half(n); }
+static inline long frc_plane_floats(int n) { return 7L * n * half_side(n); }
 
 // grid = slots * C * tiles (tile fastest, then channel).  part[slots][C][3][n][n] (S0, S1, Q), cnt[slots][2] (written by
 // tile 0 of channel 0)
@@ -51,41 +47,10 @@ __global__ __launch_bounds__(ALIGN_TILE) void halves_accum_kernel(const float* _
                                                                   int* __restrict__ cnt, int N, int C, int n, int K,
                                                                   int tiles, float t_scale) {
     __shared__ AlignPose pose[AVG_CHUNK];
-    __shared__ int member[AVG_CHUNK];                         // image index, -1 = skipped or behind the chunk's end
-    const int tile = blockIdx.x % tiles;
-    const long rest = blockIdx.x / tiles;
-    const int ch = (int)(rest % C);
-    const int slot = (int)(rest / C);
-    // the class whose slots contain `slot`: the largest k with clean[k] / AVG_CHUNK + k <= slot (strictly increasing in k)
-    int lo = 0, hi = K - 1;
-    if (clean[0] / AVG_CHUNK > slot) return;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (clean[mid] / AVG_CHUNK + mid <= slot) lo = mid; else hi = mid - 1;
-    }
-    const int k = lo;
-    const int sk = clean[k], ek = clean[k + 1];
-    const int first = sk + (slot - (sk / AVG_CHUNK + k)) * AVG_CHUNK;
-    if (first >= ek) return;                                  // a slot that no chunk owns: nobody reads it either
-    const int members = min(AVG_CHUNK, ek - first);
-    if (threadIdx.x < AVG_CHUNK) {
-        int id = -1;
-        AlignPose q = {0.f, 0.f, 0.f, 0.f};
-        if ((int)threadIdx.x < members) {
-            id = order[first + threadIdx.x];
-            if (id < 0 || id >= N) id = -1;
-        }
-        if (id >= 0) {
-            const float th = theta[id];
-            q.c = cosf(th);
-            q.s = sinf(th);
-            q.tx = t_scale * dx[2 * (long)id];
-            q.ty = t_scale * dx[2 * (long)id + 1];
-        }
-        pose[threadIdx.x] = q;
-        member[threadIdx.x] = id;
-    }
-    __syncthreads();
+    __shared__ int member[AVG_CHUNK];
+    AvgChunk w;
+    if (!w.load(blockIdx.x, clean, order, theta, dx, N, C, K, tiles, t_scale, pose, member)) return;
+    const int tile = w.tile, ch = w.ch, slot = w.slot, members = w.members;
     if (tile == 0 && ch == 0 && threadIdx.x < 2) {
         int v = 0;
         for (int m = threadIdx.x; m < members; m += 2) v += member[m] >= 0;
@@ -162,15 +127,6 @@ __global__ __launch_bounds__(ALIGN_TILE) void halves_reduce_kernel(const float* 
     var[at] = v;
 }
 
-// The n twiddles (cos, sin)(2 pi t / n) of a workgroup
-__device__ __forceinline__ void frc_twiddles(float2* tw, int n) {
-    for (int t = threadIdx.x; t < n; t += blockDim.x) {
-        double s, c;
-        sincospi((double)(2 * t) / (double)n, &s, &c);
-        tw[t] = make_float2((float)c, (float)s);
-    }
-}
-
 // m(i, j): 1 within `radius` of the centre ((n - 1) / 2, (n - 1) / 2), a raised cosine over `edge`, 0 beyond; radius <= 0: no
 // mask.  fp64: what the mask adds to the error of a coefficient is far below the sums' own rounding.
 __device__ __forceinline__ float frc_mask(int i, int j, int n, float radius, float edge) {
@@ -187,14 +143,14 @@ __device__ __forceinline__ float frc_mask(int i, int j, int n, float radius, flo
 // G(i, kx) = sum_j x[i][j] m(i, j) exp(-2 pi i kx j / n)
 __global__ __launch_bounds__(FRC_TILE) void frc_rows_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                             float2* __restrict__ G, int n, float radius, float edge) {
-    __shared__ float2 tw[FRC_SIDE_MAX];
-    __shared__ float row[FRC_ROWS * FRC_SIDE_MAX];
-    const int H = frc_half(n);
+    __shared__ float2 tw[SIDE_MAX];
+    __shared__ float row[FRC_ROWS * SIDE_MAX];
+    const int H = half_side(n);
     const int i0 = blockIdx.x * FRC_ROWS;
     const int rows = min(FRC_ROWS, n - i0);
     const size_t plane = blockIdx.y;
     const float* __restrict__ x = (blockIdx.z == 0 ? a : b) + (plane * n + i0) * n;
-    frc_twiddles(tw, n);
+    dft_twiddles(tw, n, blockDim.x);
     for (int e = threadIdx.x; e < rows * n; e += FRC_TILE) {  // the rows are adjacent in memory: one contiguous read
         const int r = e / n, j = e - r * n;
         row[r * n + j] = x[e] * frc_mask(i0 + r, j, n, radius, edge);
@@ -211,8 +167,7 @@ __global__ __launch_bounds__(FRC_TILE) void frc_rows_kernel(const float* __restr
             const float v = xr[j];
             re = fmaf(v, w.x, re);
             im = fmaf(-v, w.y, im);
-            t += kx;
-            t -= t >= n ? n : 0;
+            tw_advance(t, kx, n);
         }
         dst[e] = make_float2(re, im);                         // e = r * H + kx: the rows of G are adjacent as well
     }
@@ -221,11 +176,11 @@ __global__ __launch_bounds__(FRC_TILE) void frc_rows_kernel(const float* __restr
 // grid = (ceil(ceil(n / FRC_KY) * H / FRC_TILE), P).  prod[P][3][n][H]: Re(Fa conj Fb), |Fa|^2, |Fb|^2 at (ky, kx) with
 // F(ky, kx) = sum_i G(i, kx) exp(-2 pi i ky i / n); the products in fp64 from the fp32 coefficients, rounded to fp32 once
 __global__ __launch_bounds__(FRC_TILE) void frc_cols_kernel(const float2* __restrict__ G, float* __restrict__ prod, int n) {
-    __shared__ float2 tw[FRC_SIDE_MAX];
-    const int H = frc_half(n);
+    __shared__ float2 tw[SIDE_MAX];
+    const int H = half_side(n);
     const int groups = (n + FRC_KY - 1) / FRC_KY;
     const size_t plane = blockIdx.y;
-    frc_twiddles(tw, n);
+    dft_twiddles(tw, n, blockDim.x);
     __syncthreads();
     const int e = blockIdx.x * FRC_TILE + threadIdx.x;
     if (e >= groups * H) return;
@@ -249,8 +204,7 @@ __global__ __launch_bounds__(FRC_TILE) void frc_cols_kernel(const float2* __rest
             aim[u] = fmaf(va.y, w.x, fmaf(-va.x, w.y, aim[u]));
             bre[u] = fmaf(vb.x, w.x, fmaf(vb.y, w.y, bre[u]));
             bim[u] = fmaf(vb.y, w.x, fmaf(-vb.x, w.y, bim[u]));
-            t[u] += ky[u];
-            t[u] -= t[u] >= n ? n : 0;
+            tw_advance(t[u], ky[u], n);
         }
     }
     float* __restrict__ dst = prod + plane * 3 * n * H + kx;
@@ -281,7 +235,7 @@ __device__ __forceinline__ int frc_first_kx(int t) {
 // odd n does not exist) counts twice, once for its mirror image (-ky, -kx), whose three products are the same.
 __global__ __launch_bounds__(FRC_RING_TILE) void frc_rings_kernel(const float* __restrict__ prod, float* __restrict__ frc,
                                                                   double* __restrict__ sums, int n) {
-    const int H = frc_half(n);
+    const int H = half_side(n);
     const int r = blockIdx.x * FRC_RING_TILE + threadIdx.x;
     if (r >= H) return;
     const size_t plane = blockIdx.y;

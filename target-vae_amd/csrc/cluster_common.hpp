@@ -1,0 +1,75 @@
+// What the kernel families of libtvae_cluster.so share: the launch check, the host-side argument tests, the shape limits,
+// the DFT twiddle table and the fragment conventions of the fp32 MFMA.  Host and device code, and NO __global__ function:
+// a non-template kernel is emitted by every unit that sees its definition (abi_common.hpp), so a header that any unit of the
+// library may include -- this one -- must not define one.  That is the difference from align_kernels.hpp and the other
+// *_kernels.hpp, each of which exactly one unit may see.  It does not include abi_common.hpp either: that header carries the
+// training ABI and gemm_f32_mfma.hpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/tvae_cluster.h"
+
+#define TVAE_CLUSTER_CHECK_LAUNCH()              \
+    do {                                         \
+        hipError_t e__ = hipGetLastError();      \
+        if (e__ != hipSuccess) return (int)e__;  \
+    } while (0)
+
+namespace tvae_cluster {
+
+// ---- host ------------------------------------------------------------------------------------------------------------------
+constexpr long GRID_MAX = 0x7fffffffL;   // workgroups along x of one launch
+
+static inline hipStream_t S(tvae_stream_t s) { return (hipStream_t)s; }
+static inline bool aligned8(const void* p) { return (reinterpret_cast<size_t>(p) & 7) == 0; }
+static inline bool finite(float x) { return x - x == 0.f; }            // false for NaN and +-inf
+// (allow_big_lds of abi_common.hpp)
+template <class KernelT>
+static hipError_t allow_big_lds(KernelT kernel, size_t bytes) {
+    if (bytes <= 48 * 1024) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)bytes);
+}
+
+// ---- limits: one set for every family; a family header names a limit of its own only where it means something else -----------
+constexpr int SIDE_MAX = 1024;           // n: side of an image or plane
+constexpr int PLANES_MAX = 1 << 24;      // images or planes of a stack
+constexpr int CLASSES_MAX = 65535;       // classes
+
+// ---- direct DFT --------------------------------------------------------------------------------------------------------------
+// kx = 0 .. n / 2 of a half spectrum; also the number of rings
+__host__ __device__ static inline int half_side(int n) { return n / 2 + 1; }
+
+// The n twiddles (cos, sin)(2 pi t / n) of a workgroup: sincospi in fp64 on the exact argument 2 t / n, rounded to fp32 once
+// (half an ulp; exact 0 and +-1 on the axes).  `stride` = the threads of the workgroup, a constant or blockDim.x.
+__device__ __forceinline__ void dft_twiddles(float2* tw, int n, unsigned stride) {
+    for (int t = threadIdx.x; t < n; t += stride) {
+        double s, c;
+        sincospi((double)(2 * t) / (double)n, &s, &c);
+        tw[t] = make_float2((float)c, (float)s);
+    }
+}
+
+// t = (a k) mod n from one k to the next, in integers: t and step in [0, n), no argument is ever reduced in floating point
+__device__ __forceinline__ void tw_advance(int& t, int step, int n) {
+    t += step;
+    t -= t >= n ? n : 0;
+}
+
+// ---- v_mfma_f32_32x32x2_f32: an exact fp32 FMA chain per output, ascending k -----------------------------------------------------
+// Lane l supplies A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31].  D is sixteen registers per lane: column
+// j = l & 31, row i = mfma_row(reg, l >> 5) = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5) (gemm_f32_mfma.hpp).
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ void zero(f32x16& a) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) a[r] = 0.f;
+}
+
+// row of accumulator register r within a tile whose first row is row0 (row0 is added FIRST, as the kernels always wrote the
+// sum: another order of the integer additions is another instruction schedule)
+__device__ __forceinline__ int mfma_row(int r, int khalf, int row0 = 0) {
+    return row0 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+}
+
+}  // namespace tvae_cluster

@@ -9,9 +9,7 @@
 //                       Every kernel here calls this one function: an image's H is the same bits wherever it is formed.
 // ctf_eval_kernel       a thread = one (ky, kx) of one row.
 // ctf_filter_kernel     ONE 256-thread workgroup (four waves) owns ONE plane from load to store; a direct DFT in four stages
-//                       on v_mfma_f32_32x32x2_f32 (an exact fp32 FMA chain per output, ascending k; lane l supplies
-//                       A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31]; D: column j = l & 31, row
-//                       i = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5), as in image_kernels.hpp):
+//                       on v_mfma_f32_32x32x2_f32 (the fragment layout: cluster_common.hpp):
 //                         1 rows          G(i, kx)  = sum_j  x(i, j) e^{-2 pi i kx j / n}              2 MFMAs per k step
 //                         2 columns       F(ky, kx) = sum_i  e^{-2 pi i ky i / n} G(i, kx)             4
 //                           multiply      F *= H(ky, kx) w_kx, H formed in registers (or read from the caller's plane)
@@ -19,8 +17,8 @@
 //                         4 rows back     out(i, j) = n^-2 sum_kx Re(P(i, kx) e^{+2 pi i kx j / n})    2
 //                       A wave walks 32 x 32 output tiles (tile = wave, wave + 4, ...), the whole reduction of a tile in its
 //                       registers.  The twiddle operand of every stage is NOT staged: a lane reads it from the table of the n
-//                       values (cos, sin)(2 pi t / n) at t = (a k) mod n, kept in integers (t += 2 a mod n per step), so no
-//                       argument is ever reduced in floating point.  The data operand comes from one of two buffers of
+//                       values (cos, sin)(2 pi t / n) at t = (a k) mod n, kept in integers (tw_advance by 2 a mod n per step), so
+//                       no argument is ever reduced in floating point.  The data operand comes from one of two buffers of
 //                       2 n ld floats (re plane, im plane; row stride ld = (n / 2 + 1) | 1, odd: the A-fragment reads of 32
 //                       consecutive rows at a fixed k and the B-fragment reads of 32 consecutive columns are conflict-free):
 //                       buffer 0 holds x (row stride n | 1), then F; buffer 1 holds G, then P.  Rows, columns and k outside
@@ -37,18 +35,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "cluster_common.hpp"
+
 namespace tvae_cluster {
 
-typedef float ctf_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int CTF_SIDE_MAX = 1024;
-constexpr int CTF_B_MAX = 1 << 24;
-constexpr int CTF_K_MAX = 65535;
 constexpr int CTF_THREADS = 256;
 constexpr int CTF_ONDIE_MAX = 128;       // the largest n whose two buffers sit in LDS
 
-__host__ __device__ static inline int ctf_half(int n) { return n / 2 + 1; }
-__host__ __device__ static inline int ctf_ld(int n) { return ctf_half(n) | 1; }
+__host__ __device__ static inline int ctf_ld(int n) { return half_side(n) | 1; }
 // floats of one buffer (re and im plane); x at row stride n | 1 fits: n | 1 <= 2 ld
 __host__ __device__ static inline long ctf_buf_floats(int n) { return 2L * n * ctf_ld(n); }
 static inline size_t ctf_lds_bytes(int n) {
@@ -72,26 +66,12 @@ __device__ __forceinline__ float ctf_value(const double* __restrict__ cf, int ky
 // grid = N * tiles (tile fastest), tiles = ceil(n R / 256).  H[N][n][R]
 __global__ __launch_bounds__(CTF_THREADS) void ctf_eval_kernel(const double* __restrict__ coef, float* __restrict__ H, int n,
                                                                int tiles, int mode) {
-    const int R = ctf_half(n);
+    const int R = half_side(n);
     const unsigned row = blockIdx.x / tiles, tile = blockIdx.x - row * tiles;
     const int e = (int)tile * CTF_THREADS + threadIdx.x;
     if (e >= n * R) return;
     const int ky = e / R, kx = e - ky * R;
     H[(size_t)row * n * R + e] = ctf_value(coef + 5 * (size_t)row, ky, kx, n, mode);
-}
-
-// The n twiddles (cos, sin)(2 pi t / n): sincospi in fp64 on the exact argument 2 t / n, rounded once
-__device__ __forceinline__ void ctf_twiddles(float2* tw, int n) {
-    for (int t = threadIdx.x; t < n; t += CTF_THREADS) {
-        double s, c;
-        sincospi((double)(2 * t) / (double)n, &s, &c);
-        tw[t] = make_float2((float)c, (float)s);
-    }
-}
-
-__device__ __forceinline__ void ctf_zero(ctf_f32x16& a) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.f;
 }
 
 // stages 2 and 3: (Or + i Oi)(a, col) = sum_k (c + i SGN s)((a k) mod n) (Ir + i Ii)(k, col); a, k = 0 .. n - 1, col = 0 .. R - 1
@@ -109,9 +89,9 @@ __device__ __forceinline__ void ctf_columns(const float2* tw, const float* in, f
         const bool aok = a < n, cok = col < R;
         const int step = aok ? (2 * a) % n : 0;
         int t = aok ? (a * khalf) % n : 0;
-        ctf_f32x16 accr, acci;
-        ctf_zero(accr);
-        ctf_zero(acci);
+        f32x16 accr, acci;
+        zero(accr);
+        zero(acci);
         for (int k0 = 0; k0 < n; k0 += 2) {
             const int k = k0 + khalf;
             const bool ok = cok && k < n;
@@ -126,12 +106,11 @@ __device__ __forceinline__ void ctf_columns(const float2* tw, const float* in, f
             accr = __builtin_amdgcn_mfma_f32_32x32x2f32(-wsn, bi, accr, 0, 0, 0);
             acci = __builtin_amdgcn_mfma_f32_32x32x2f32(wc, bi, acci, 0, 0, 0);
             acci = __builtin_amdgcn_mfma_f32_32x32x2f32(wsn, br, acci, 0, 0, 0);
-            t += step;
-            t -= t >= n ? n : 0;
+            tw_advance(t, step, n);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = ta * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+            const int row = mfma_row(r, khalf, ta * 32);
             if (row < n && cok) {
                 orr[(size_t)row * ld + col] = accr[r];
                 oi[(size_t)row * ld + col] = acci[r];
@@ -148,7 +127,7 @@ __global__ __launch_bounds__(CTF_THREADS) void ctf_filter_kernel(const float* X,
                                                                  float* ws, int n, int mode) {
     extern __shared__ __attribute__((aligned(16))) float ctf_sm[];
     float2* const tw = reinterpret_cast<float2*>(ctf_sm);
-    const int R = ctf_half(n), ld = ctf_ld(n), ldx = n | 1;
+    const int R = half_side(n), ld = ctf_ld(n), ldx = n | 1;
     const long buf = ctf_buf_floats(n);
     const size_t b = blockIdx.x;
     float* const buf0 = ONDIE ? ctf_sm + 2 * n : ws + b * 2 * buf;
@@ -159,7 +138,7 @@ __global__ __launch_bounds__(CTF_THREADS) void ctf_filter_kernel(const float* X,
     const int TI = (n + 31) >> 5, TK = (R + 31) >> 5;
     const size_t pl = (size_t)n * ld;                         // floats of a re or im plane
 
-    ctf_twiddles(tw, n);
+    dft_twiddles(tw, n, CTF_THREADS);
     {
         const float* x = X + b * x_stride;
         for (int e = tid; e < n * n; e += CTF_THREADS) {
@@ -176,9 +155,9 @@ __global__ __launch_bounds__(CTF_THREADS) void ctf_filter_kernel(const float* X,
         const bool iok = i < n, kok = kx < R;
         const int step = kok ? (2 * kx) % n : 0;
         int t = kok ? (kx * khalf) % n : 0;
-        ctf_f32x16 accr, acci;
-        ctf_zero(accr);
-        ctf_zero(acci);
+        f32x16 accr, acci;
+        zero(accr);
+        zero(acci);
         for (int j0 = 0; j0 < n; j0 += 2) {
             const int j = j0 + khalf;
             float a = 0.f;
@@ -186,12 +165,11 @@ __global__ __launch_bounds__(CTF_THREADS) void ctf_filter_kernel(const float* X,
             const float2 w = tw[t];
             accr = __builtin_amdgcn_mfma_f32_32x32x2f32(a, kok ? w.x : 0.f, accr, 0, 0, 0);
             acci = __builtin_amdgcn_mfma_f32_32x32x2f32(a, kok ? -w.y : 0.f, acci, 0, 0, 0);
-            t += step;
-            t -= t >= n ? n : 0;
+            tw_advance(t, step, n);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+            const int row = mfma_row(r, khalf, ti * 32);
             if (row < n && kok) {
                 buf1[(size_t)row * ld + kx] = accr[r];
                 buf1[pl + (size_t)row * ld + kx] = acci[r];
@@ -238,8 +216,8 @@ __global__ __launch_bounds__(CTF_THREADS) void ctf_filter_kernel(const float* X,
         const bool iok = i < n, jok = j < n;
         const int step = jok ? (2 * j) % n : 0;
         int t = jok ? (j * khalf) % n : 0;
-        ctf_f32x16 acc;
-        ctf_zero(acc);
+        f32x16 acc;
+        zero(acc);
         for (int k0 = 0; k0 < R; k0 += 2) {
             const int k = k0 + khalf;
             float ar = 0.f, ai = 0.f;
@@ -250,12 +228,11 @@ __global__ __launch_bounds__(CTF_THREADS) void ctf_filter_kernel(const float* X,
             const float2 w = tw[t];
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, jok ? w.x : 0.f, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(-ai, jok ? w.y : 0.f, acc, 0, 0, 0);
-            t += step;
-            t -= t >= n ? n : 0;
+            tw_advance(t, step, n);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+            const int row = mfma_row(r, khalf, ti * 32);
             if (row < n && jok) o[(size_t)row * n + j] = scale * acc[r];
         }
     }
@@ -267,7 +244,7 @@ __global__ __launch_bounds__(CTF_THREADS) void ctf_power_kernel(const double* __
                                                                 double* __restrict__ D, int* __restrict__ counts, int N,
                                                                 int n, int tiles) {
     __shared__ int red[CTF_THREADS];
-    const int R = ctf_half(n);
+    const int R = half_side(n);
     const int k = blockIdx.x / tiles, tile = blockIdx.x - k * tiles;
     // cleaned boundaries of class k: min(max(0, seg[0], ..., seg[k]), N) and the same with seg[k + 1]
     int m = 0;

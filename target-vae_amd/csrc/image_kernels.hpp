@@ -12,8 +12,7 @@
 //             A-fragment reads of stage 2 walk rows at stride 65: conflict-free as well);
 //   stage 2   acc += U Br[chunk][TN] - V Bi[chunk][TN] in steps of 16 chunk columns, the Br / Bi tiles staged like stage 1's;
 //             wave (w >> 1, w & 1) owns 32 rows x TN / 2 columns of the tile in registers for the whole walk.
-// v_mfma_f32_32x32x2_f32 throughout (an exact fp32 FMA chain per output, ascending k): lane l supplies A[i = l & 31][k = l >> 5]
-// and B[k = l >> 5][j = l & 31]; D: column j = l & 31, row i = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5) (gemm_f32_mfma.hpp).
+// v_mfma_f32_32x32x2_f32 throughout (an exact fp32 FMA chain per output, ascending k; the fragment layout: cluster_common.hpp).
 // Every element outside the window, the tables or the output is a PREDICATED zero: nothing outside a tensor or outside the
 // window is ever loaded.  LDS: 50 KB whatever the shape.  No atomics; an output depends on its image and the tables only.
 //
@@ -23,12 +22,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "cluster_common.hpp"
+
 namespace tvae_cluster {
 
-typedef float img_f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int IMG_SIDE_MAX = 1024;
-constexpr int IMG_B_MAX = 1 << 24;
 constexpr int IMG_THREADS = 256;
 constexpr int IMG_TM = 64;          // output rows of a workgroup
 constexpr int IMG_CK = 64;          // window columns of a chunk
@@ -85,11 +82,9 @@ void image_resample_kernel(const float* __restrict__ X, const float* __restrict_
     const float* __restrict__ xw = X + ((long)img * H + r0) * W + c0;        // the window's (0, 0)
 
     const int wm = wave >> 1, wn = wave & 1;                  // stage 2: rows wm 32 .., columns wn 32 NJ ..
-    img_f32x16 acc[NJ];
+    f32x16 acc[NJ];
 #pragma unroll
-    for (int q = 0; q < NJ; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    for (int q = 0; q < NJ; ++q) zero(acc[q]);
 
     // stage 1 roles
     const int s1_rows = (wave & 1) * 32;
@@ -102,11 +97,9 @@ void image_resample_kernel(const float* __restrict__ X, const float* __restrict_
 
     for (int cc = 0; cc < N; cc += IMG_CK) {
         // ---- stage 1 ------------------------------------------------------------------------------------------------
-        img_f32x16 u[NC1];
+        f32x16 u[NC1];
 #pragma unroll
-        for (int q = 0; q < NC1; ++q)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) u[q][r] = 0.f;
+        for (int q = 0; q < NC1; ++q) zero(u[q]);
         const int nk = (M + IMG_BK - 1) / IMG_BK;
         ta.fetch(Ar, M, 0, M, i0, m, tid);
         if (IMAG) tb.fetch(Ai, M, 0, M, i0, m, tid);
@@ -140,7 +133,7 @@ void image_resample_kernel(const float* __restrict__ X, const float* __restrict_
         for (int q = 0; q < NC1; ++q)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = s1_rows + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+                const int row = mfma_row(r, khalf, s1_rows);
                 uv[s1_part * (IMG_TM * IMG_UV_LD) + row * IMG_UV_LD + s1_col0 + 32 * q + l31] = u[q][r];
             }
         // ---- stage 2 ------------------------------------------------------------------------------------------------
@@ -192,7 +185,7 @@ void image_resample_kernel(const float* __restrict__ X, const float* __restrict_
         const int j = j0 + 64 * q + wn * 32 + l31;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int i = i0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
+            const int i = mfma_row(r, khalf, i0 + wm * 32);
             if (i < m && j < n) o[(long)i * n + j] = scale * acc[q][r];
         }
     }

@@ -67,7 +67,34 @@ QUERIES = {
     'tvae_fourier_filter_ws_floats': ('ii', 'l'),
 }
 
+# the shape limits every image family shares (SIDE_MAX, PLANES_MAX, CLASSES_MAX of csrc/cluster_common.hpp)
+MAX_SIDE = 1024
+MAX_PLANES = 1 << 24
+MAX_CLASSES = 65535
+
 _cl = None
+
+
+def is_f32(t, contiguous=True) -> bool:
+    """A CUDA fp32 tensor, contiguous unless the caller lays it out itself."""
+    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and (t.is_contiguous() or not contiguous)
+
+
+def require_f32(t, what, name):
+    """`what` (the public function) and `name` (its argument) are the caller's words: tests and CLIs match on the message."""
+    if not is_f32(t):
+        raise TvaeHipError(f'{what}: {name} must be a contiguous CUDA fp32 tensor (no CPU fallback)')
+
+
+def workspace(floats, device):
+    """At least `floats` fp32 words that start on an 8-byte boundary: the kernels keep fp64 values in them."""
+    return torch.empty((int(floats) + 1) // 2, dtype=torch.float64, device=device).view(torch.float32)
+
+
+def slice_step(planes, cap, fit) -> int:
+    """Planes per call when a stack goes through a kernel in slices: at most `cap` (what a launch covers) and `fit` (what
+    the workspace bound or the caller allows), at least one."""
+    return max(1, min(int(planes), int(cap), int(fit)))
 
 
 def exported_symbols():

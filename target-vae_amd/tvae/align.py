@@ -28,8 +28,8 @@ import torch
 from . import _cluster_lib as CL
 from ._lib import TvaeHipError
 
-MAX_IMAGES = 1 << 24
-MAX_CLUSTERS = 65535
+MAX_IMAGES = CL.MAX_PLANES
+MAX_CLUSTERS = CL.MAX_CLASSES
 
 
 def translation_scale(t_inf: str) -> float:
@@ -62,12 +62,11 @@ def segments(labels, n_clusters):
 
 def _check_stack(images, theta, dx, what):
     for nm, t in (('images', images), ('theta', theta), ('dx', dx)):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise TvaeHipError(f'{what}: {nm} must be a contiguous CUDA fp32 tensor (no CPU fallback)')
+        CL.require_f32(t, what, nm)
     if images.dim() != 4 or images.shape[-1] != images.shape[-2]:
         raise TvaeHipError(f'{what}: images must be [N][C][n][n] (square), got {tuple(images.shape)}')
     N, C, n, _ = images.shape
-    if not (1 <= N <= MAX_IMAGES and 1 <= C <= 1024 and 2 <= n <= 1024):
+    if not (1 <= N <= MAX_IMAGES and 1 <= C <= 1024 and 2 <= n <= CL.MAX_SIDE):
         raise TvaeHipError(f'{what}: N={N}, C={C}, n={n} outside the supported range '
                            '(1 <= N <= 2^24, 1 <= C <= 1024, 2 <= n <= 1024)')
     if theta.numel() != N or theta.dim() > 2 or tuple(dx.shape) != (N, 2):
@@ -96,14 +95,7 @@ def class_averages(images, theta, dx, labels, n_clusters=None, t_scale=1.0):
     """-> (avg fp32 [K][C][n][n], counts int32 [K]) on the device of `images`: avg[k] is the mean of the aligned images
     with label k (zeros for an empty class).  labels: [N] integers on any device or a numpy array; a label outside
     [0, K) belongs to no class.  n_clusters None: the largest label + 1."""
-    N, C, n = _check_stack(images, theta, dx, 'class_averages')
-    lab = torch.as_tensor(labels)
-    if lab.dim() != 1 or lab.numel() != N:
-        raise TvaeHipError(f'class_averages: labels must hold N = {N} entries, got {tuple(lab.shape)}')
-    lab = lab.to(images.device)
-    K = int(n_clusters) if n_clusters is not None else int(lab.max()) + 1
-    if not 1 <= K <= MAX_CLUSTERS:
-        raise TvaeHipError(f'class_averages: n_clusters = {K} outside [1, {MAX_CLUSTERS}]')
+    N, C, n, K, lab = _check_labels(images, theta, dx, labels, n_clusters, 'class_averages')
     order, seg, counts = segments(lab, K)
     wsf = CL.query('tvae_class_average_ws_floats', N, K, C, n)
     if wsf <= 0:
@@ -159,8 +151,7 @@ def frc(a, b, mask_radius=None, mask_edge=0.0):
     ring correlation of every pair of planes under the soft circular mask (mask_radius None or <= 0: no mask) and the ring
     sums (Re(Fa conj Fb), |Fa|^2, |Fb|^2) it is the ratio of.  include/tvae_cluster.h states the definition."""
     for nm, t in (('a', a), ('b', b)):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise TvaeHipError(f'frc: {nm} must be a contiguous CUDA fp32 tensor (no CPU fallback)')
+        CL.require_f32(t, 'frc', nm)
     if a.shape != b.shape or a.device != b.device or a.dim() < 2 or a.shape[-1] != a.shape[-2]:
         raise TvaeHipError(f'frc: a and b must be [...][n][n] of one shape on one device, got {tuple(a.shape)} and '
                            f'{tuple(b.shape)}')
@@ -180,9 +171,9 @@ def frc(a, b, mask_radius=None, mask_edge=0.0):
     # Planes are independent and a plane's workgroups, addition order and twiddles depend on n alone, so a call on a slice
     # of the planes cannot change a bit of any plane's result: the slices only bound the workspace.
     per = CL.query('tvae_class_frc_ws_floats', 1, n)
-    step = max(1, min(P, FRC_WS_FLOATS // per, 65535))
+    step = CL.slice_step(P, 65535, FRC_WS_FLOATS // per)    # (65535: the planes are the y dimension of the launch grids)
     wsf = CL.query('tvae_class_frc_ws_floats', step, n)
-    ws = torch.empty(wsf, dtype=torch.float32, device=a.device)
+    ws = CL.workspace(wsf, a.device)
     with torch.cuda.device(a.device):
         for p0 in range(0, P, step):
             p1 = min(p0 + step, P)

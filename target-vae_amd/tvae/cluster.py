@@ -39,7 +39,7 @@ def _feature_major(X):
 
 
 def _check_points(X, k):
-    if not (torch.is_tensor(X) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 2):
+    if not (CL.is_f32(X, contiguous=False) and X.dim() == 2):
         raise TvaeHipError('kmeans: X must be a CUDA fp32 [N][d] tensor (no CPU fallback)')
     N, d = X.shape
     if not (1 <= d <= 256 and 1 <= k <= 1024 and k <= N):
@@ -144,7 +144,7 @@ def kmeans(X, n_clusters, n_init=100, max_iter=300, tol=1e-4, seed=None, init=No
 
 
 def _check_ward_points(X):
-    if not (torch.is_tensor(X) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 2):
+    if not (CL.is_f32(X, contiguous=False) and X.dim() == 2):
         raise TvaeHipError('ward_linkage: X must be a CUDA fp32 [N][d] tensor (no CPU fallback)')
     N, d = X.shape
     if not (2 <= N <= WARD_MAX_POINTS and 1 <= d <= 256):

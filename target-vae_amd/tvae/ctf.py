@@ -25,7 +25,7 @@ from ._lib import TvaeHipError
 COLUMNS = ('defocus', 'cs', 'voltage', 'apix', 'bfactor', 'ampcont', 'dfdiff', 'dfang')
 MODES = {'multiply': 0, 'flip': 1, 0: 0, 1: 1}
 WS_FLOATS = 1 << 26               # bound of the workspace of one tvae_fourier_filter call: 256 MB
-MAX_PLANES = 1 << 24
+MAX_PLANES = CL.MAX_PLANES
 
 
 def _column(params, name):
@@ -84,7 +84,7 @@ def transfer(coef, n, mode='multiply', device=None):
     dev = _device(device)
     c = _coef_tensor(coef, dev, 'transfer')
     N, n = c.shape[0], int(n)
-    if not (2 <= n <= 1024 and N <= MAX_PLANES):
+    if not (2 <= n <= CL.MAX_SIDE and N <= MAX_PLANES):
         raise TvaeHipError(f'transfer: N={N}, n={n} outside the supported range (N <= 2^24, 2 <= n <= 1024)')
     H = torch.empty(N, n, n // 2 + 1, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
@@ -99,9 +99,9 @@ def _filter(x, x_stride, coef, planes, h_stride, out, n, mode, chunk=None):
     per = CL.query('tvae_fourier_filter_ws_floats', 1, n)
     if per <= 0 or B < 1:
         raise TvaeHipError(f'fourier filter: n={n} with {B} planes outside the supported range (2 <= n <= 1024)')
-    step = max(1, min(B, MAX_PLANES, WS_FLOATS // per if chunk is None else int(chunk)))
+    step = CL.slice_step(B, MAX_PLANES, WS_FLOATS // per if chunk is None else chunk)
     wsf = CL.query('tvae_fourier_filter_ws_floats', step, n)
-    ws = torch.empty(wsf // 2, dtype=torch.float64, device=out.device).view(torch.float32)
+    ws = CL.workspace(wsf, out.device)
     xf, of = x.reshape(-1), out.reshape(-1)
     with torch.cuda.device(out.device):
         for b0 in range(0, B, step):
@@ -121,8 +121,7 @@ def filter_stack(images, coef=None, planes=None, mode='multiply', inplace=False,
     coef ([N][5] fp64, host or device: H is formed in registers, never stored) and planes ([N][n][R] or one shared [n][R],
     CUDA fp32, R = n // 2 + 1).  The channels of an image share its row.  mode 'flip' multiplies by sign(H) instead.
     inplace overwrites `images`.  chunk: planes per launch (default: what keeps the workspace within 256 MB)."""
-    if not (torch.is_tensor(images) and images.is_cuda and images.dtype == torch.float32 and images.is_contiguous()):
-        raise TvaeHipError('filter_stack: images must be a contiguous CUDA fp32 tensor (no CPU fallback)')
+    CL.require_f32(images, 'filter_stack', 'images')
     if images.dim() not in (3, 4) or images.shape[-1] != images.shape[-2]:
         raise TvaeHipError(f'filter_stack: images must be [N][n][n] or [N][C][n][n] (square), got {tuple(images.shape)}')
     if (coef is None) == (planes is None):
@@ -141,8 +140,7 @@ def filter_stack(images, coef=None, planes=None, mode='multiply', inplace=False,
             c = c.repeat_interleave(C, 0).contiguous()
     else:
         p = planes
-        if not (torch.is_tensor(p) and p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
-                and p.device == images.device):
+        if not (CL.is_f32(p) and p.device == images.device):
             raise TvaeHipError('filter_stack: planes must be a contiguous CUDA fp32 tensor on the device of images')
         if tuple(p.shape) == (N, n, R):
             h_stride = n * R
@@ -181,7 +179,7 @@ def power(coef, labels, n, n_clusters=None, device=None):
         raise TvaeHipError(f'power: labels must hold N = {N} entries, got {tuple(lab.shape)}')
     lab = lab.to(dev)
     K = int(n_clusters) if n_clusters is not None else int(lab.max()) + 1
-    if not (1 <= K <= align.MAX_CLUSTERS and 2 <= n <= 1024 and N <= MAX_PLANES):
+    if not (1 <= K <= CL.MAX_CLASSES and 2 <= n <= CL.MAX_SIDE and N <= MAX_PLANES):
         raise TvaeHipError(f'power: N={N}, K={K}, n={n} outside the supported range')
     order, seg, _ = align.segments(lab, K)
     D = torch.empty(K, n, n // 2 + 1, dtype=torch.float64, device=dev)

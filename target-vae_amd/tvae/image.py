@@ -25,8 +25,8 @@ from . import _cluster_lib as CL
 from . import tables
 from ._lib import TvaeHipError
 
-MAX_IMAGES = 1 << 24
-MAX_SIDE = 1024
+MAX_IMAGES = CL.MAX_PLANES
+MAX_SIDE = CL.MAX_SIDE
 
 _DEVICE_TABLES = {}
 
@@ -118,10 +118,10 @@ def normalize(stack, radius=None, return_stats=False, out=None):
         raise TvaeHipError(f'normalize: B={B}, n={n}, m={m} outside the supported range (1 <= B <= 2^24, sides <= {MAX_SIDE})')
     if out is None:
         out = torch.empty_like(x)
-    elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape):
+    elif not (CL.is_f32(out) and out.shape == x.shape):
         raise TvaeHipError('normalize: out must be a contiguous CUDA fp32 tensor of the input\'s shape')
     stats = torch.empty(B, 2, dtype=torch.float64, device=x.device)
-    ws = torch.empty((wsf + 1) // 2, dtype=torch.float64, device=x.device).view(torch.float32)     # 8-byte aligned
+    ws = CL.workspace(wsf, x.device)
     with torch.cuda.device(x.device):
         CL.call('tvae_image_normalize', x.reshape(B, n, m), out.reshape(B, n, m), stats, ws, wsf, B, n, m, r)
     if return_stats:

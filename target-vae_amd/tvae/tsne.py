@@ -50,7 +50,7 @@ def _feature_major(X):
 
 
 def _check_points(X, what):
-    if not (torch.is_tensor(X) and X.is_cuda and X.dtype == torch.float32 and X.dim() == 2):
+    if not (CL.is_f32(X, contiguous=False) and X.dim() == 2):
         raise TvaeHipError(f'{what}: X must be a CUDA fp32 [N][d] tensor (no CPU fallback)')
     N, d = X.shape
     if not (2 <= N <= MAX_POINTS and 1 <= d <= 256):
@@ -158,7 +158,7 @@ class _State:
         self.ws_floats = CL.query('tvae_tsne_repulsion_ws_floats', N)
         if self.groups <= 0 or self.ws_floats <= 0:
             raise TvaeHipError(f'tsne: N={N} is not supported by libtvae_cluster.so')
-        self.ws = torch.empty((self.ws_floats + 1) // 2, dtype=torch.float64, device=dev).view(torch.float32)
+        self.ws = CL.workspace(self.ws_floats, dev)
         self.gn2 = torch.zeros(self.groups, dtype=torch.float64, device=dev)
         self.klws = torch.zeros(self.groups, dtype=torch.float64, device=dev)
 
