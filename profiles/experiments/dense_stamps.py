@@ -19,7 +19,7 @@ for K in [int(v) for v in os.environ.get('KS', '512,2048').split(',')]:
     out = torch.empty(M, Nt, device=dev)
     w3 = torch.empty(query('tvae_dense_x6_bytes', M, K) // 4, device=dev)
     call('tvae_dense_split3', W, K, w3, w3.numel() * 4, M, K, 0)
-    fn = lambda: call('tvae_linear_fwd_x6', w3, X, bb, None, out, M, Nt, K, Nt, Nt, 1, 0.01, None, None, None, None, None, None, None, 0)
+    fn = lambda: call('tvae_linear_fwd_x6', w3, X, bb, None, out, M, Nt, K, Nt, Nt, 1, 0.01, parts=3)
     for _ in range(3):
         fn()
     torch.cuda.synchronize()

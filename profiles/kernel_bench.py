@@ -84,11 +84,11 @@ w3 = torch.empty(query('tvae_dense_x6_bytes', F_, F_) // 4, device=dev)
 call('tvae_dense_split3', W, F_, w3, w3.numel() * 4, F_, F_, 0, None, None)
 w3t = torch.empty_like(w3)
 call('tvae_dense_split3', W, F_, w3t, w3t.numel() * 4, F_, F_, 1, None, None)
-timeit('x6_dec_fwd', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_fwd_x6', w3, h1, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, None, None, None, None, None, None, None, 0, None, PARTS))
-timeit('x6_dec_dgrad', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, h3, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, None, None, None, None, 0, None, None, None, None, None, 0, None, 0, None, None, None, None, PARTS))
-timeit('x6_dec_dgrad_nomask', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, None, h2, F_, Nt, F_, Nt, Nt, 0, 0.01, None, None, None, None, 0, None, None, None, None, None, 0, None, 0, None, None, None, None, PARTS))
-timeit('x6_dec_fwd_res', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_fwd_x6', w3, h1, bb, h3, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, None, None, None, None, None, None, None, 0, None, PARTS))
-timeit('x6_dec_wgrad', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_wgrad_x6', h1, h3, dW, ws, ws.numel(), F_, Nt, F_, Nt, Nt, 0, None, None, 0, 0.01, None, None, None, None, 0, None, PARTS))
+timeit('x6_dec_fwd', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_fwd_x6', w3, h1, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, parts=PARTS))
+timeit('x6_dec_dgrad', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, h3, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, parts=PARTS))
+timeit('x6_dec_dgrad_nomask', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, None, h2, F_, Nt, F_, Nt, Nt, 0, 0.01, parts=PARTS))
+timeit('x6_dec_fwd_res', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_fwd_x6', w3, h1, bb, h3, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, parts=PARTS))
+timeit('x6_dec_wgrad', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_wgrad_x6', h1, h3, dW, ws, ws.numel(), F_, Nt, F_, Nt, Nt, 0, vg_slope=0.01, parts=PARTS))
 if query('tvae_conv1_dft_supported', B, Cin, n, k, pad, C, R):
     at = torch.zeros(query('tvae_conv1_dft_at_floats', B, Cin, n, k, pad, C, R), device=dev)
     wsd = torch.empty(query('tvae_conv1_dft_ws_floats', B, Cin, n, k, pad, C, R), device=dev)
@@ -103,39 +103,49 @@ if query('tvae_conv1_dft_supported', B, Cin, n, k, pad, C, R):
 if only and 'zero' in only:
     w3z = torch.zeros_like(w3)
     hz = torch.zeros_like(h1)
-    timeit('zero_w_x6_dec_fwd', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_fwd_x6', w3z, h1, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, None, None, None, None, None, None, None, 0, None, PARTS))
-    timeit('zero_wx_x6_dec_fwd', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_fwd_x6', w3z, hz, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, None, None, None, None, None, None, None, 0, None, PARTS))
-    timeit('zero_ref_x6_dec_fwd', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_fwd_x6', w3, h1, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, None, None, None, None, None, None, None, 0, None, PARTS))
+    timeit('zero_w_x6_dec_fwd', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_fwd_x6', w3z, h1, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, parts=PARTS))
+    timeit('zero_wx_x6_dec_fwd', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_fwd_x6', w3z, hz, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, parts=PARTS))
+    timeit('zero_ref_x6_dec_fwd', 2.0 * F_ * F_ * Nt, lambda: call('tvae_linear_fwd_x6', w3, h1, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, parts=PARTS))
 if only and 'tail' in only:
     xr2 = torch.randn(Nt, 2, device=dev); wc2 = torch.randn(F_, 2, device=dev)
     gxr = torch.empty(Nt, 2, device=dev); partf = torch.empty((Nt // 128) * F_ * 3, device=dev)
     wo1 = torch.randn(F_, device=dev); gy1 = torch.randn(Nt, device=dev)
     fl = 2.0 * F_ * F_ * Nt
-    timeit('tail_dgrad_plain', fl, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, h3, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, None, None, None, None, 0, None, None, None, None, None, 0, None, 0, None, None, None, None, PARTS))
-    timeit('tail_dgrad_intail', fl, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, h3, None, F_, Nt, F_, Nt, Nt, 1, 0.01, xr2, wc2, gxr, partf, partf.numel(), None, None, None, None, None, 0, None, 0, None, None, None, None, PARTS))
-    timeit('tail_dgrad_virt', fl, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, h3, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, None, None, None, None, 0, wo1, gy1, None, None, None, 0, None, 0, None, None, None, None, PARTS))
-    timeit('tail_dgrad_both', fl, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, h3, None, F_, Nt, F_, Nt, Nt, 1, 0.01, xr2, wc2, gxr, partf, partf.numel(), wo1, gy1, None, None, None, 0, None, 0, None, None, None, None, PARTS))
-    timeit('tail_wgrad_plain', fl, lambda: call('tvae_linear_wgrad_x6', h1, h3, dW, ws, ws.numel(), F_, Nt, F_, Nt, Nt, 0, None, None, 0, 0.01, None, None, None, None, 0, None, PARTS))
+    timeit('tail_dgrad_plain', fl, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, h3, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, parts=PARTS))
+    timeit('tail_dgrad_intail', fl, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, h3, None, F_, Nt, F_, Nt, Nt, 1, 0.01, in_xr=xr2, in_wc=wc2, in_gxr=gxr,
+                                                 in_part=partf, in_part_floats=partf.numel(), parts=PARTS))
+    timeit('tail_dgrad_virt', fl, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, h3, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, vg_wo=wo1, vg_gy=gy1, parts=PARTS))
+    timeit('tail_dgrad_both', fl, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, h3, None, F_, Nt, F_, Nt, Nt, 1, 0.01, in_xr=xr2, in_wc=wc2, in_gxr=gxr,
+                                               in_part=partf, in_part_floats=partf.numel(), vg_wo=wo1, vg_gy=gy1, parts=PARTS))
+    timeit('tail_wgrad_plain', fl, lambda: call('tvae_linear_wgrad_x6', h1, h3, dW, ws, ws.numel(), F_, Nt, F_, Nt, Nt, 0, vg_slope=0.01, parts=PARTS))
     Np_ = n * n
     bc2 = torch.randn(F_, device=dev); lb2 = torch.randn(B, F_, device=dev)
-    va = (xr2, wc2, bc2, lb2, Np_)
+    va = dict(va_xr=xr2, va_wc=wc2, va_bc=bc2, va_lb=lb2, va_np=Np_)
     # the step's actual launches: forward with the recomputed first layer (+ fused output column), data gradient with the
     # implicit gradient + fused first-layer backward + recomputed mask, weight gradient with both implicit operands
     cy = torch.empty(Nt, device=dev)
-    timeit('tail_fwd_step', fl, lambda: call('tvae_linear_fwd_x6', w3, None, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, wo1, bb[:1].contiguous(), cy, *va, None, PARTS))
+    timeit('tail_fwd_step', fl, lambda: call('tvae_linear_fwd_x6', w3, None, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, col_w=wo1, col_b=bb[:1].contiguous(), col_y=cy,
+                                             **va, parts=PARTS))
     sb = torch.zeros(F_, Nt // 32, dtype=torch.int32, device=dev)
-    timeit('tail_fwd_step+bits', fl, lambda: call('tvae_linear_fwd_x6', w3, None, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, wo1, bb[:1].contiguous(), cy, *va, sb, PARTS))
-    timeit('tail_fwd_step_nostore', fl, lambda: call('tvae_linear_fwd_x6', w3, None, bb, None, None, F_, Nt, F_, Nt, Nt, 1, 0.01, wo1, bb[:1].contiguous(), cy, *va, None, PARTS))
+    timeit('tail_fwd_step+bits', fl, lambda: call('tvae_linear_fwd_x6', w3, None, bb, None, h2, F_, Nt, F_, Nt, Nt, 1, 0.01, col_w=wo1, col_b=bb[:1].contiguous(),
+                                                  col_y=cy, **va, sign_bits=sb, parts=PARTS))
+    timeit('tail_fwd_step_nostore', fl, lambda: call('tvae_linear_fwd_x6', w3, None, bb, None, None, F_, Nt, F_, Nt, Nt, 1, 0.01, col_w=wo1, col_b=bb[:1].contiguous(),
+                                                     col_y=cy, **va, parts=PARTS))
     # the step's data gradient: two-valued implicit gradient (weights scaled by wo before the split, 0 / 1 operand)
     csum2 = torch.empty(F_, device=dev)
     w3s = torch.empty_like(w3)
     call('tvae_dense_split3', W, F_, w3s, w3s.numel() * 4, F_, F_, 1, wo1, csum2)
-    timeit('tail_dgrad_step', fl, lambda: call('tvae_linear_dgrad_x6', w3s, h1, None, None, None, F_, Nt, F_, Nt, Nt, 1, 0.01, xr2, wc2, gxr, partf, partf.numel(), None, gy1, csum2, bc2, lb2, Np_, None, 0, None, None, None, None, PARTS))
-    timeit('tail_dgrad_generic', fl, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, None, None, F_, Nt, F_, Nt, Nt, 1, 0.01, xr2, wc2, gxr, partf, partf.numel(), wo1, gy1, None, bc2, lb2, Np_, None, 0, None, None, None, None, PARTS))
+    timeit('tail_dgrad_step', fl, lambda: call('tvae_linear_dgrad_x6', w3s, h1, None, None, None, F_, Nt, F_, Nt, Nt, 1, 0.01, in_xr=xr2, in_wc=wc2, in_gxr=gxr,
+                                               in_part=partf, in_part_floats=partf.numel(), vg_gy=gy1, vg_csum=csum2, in_bc=bc2, in_lb=lb2, in_np=Np_, parts=PARTS))
+    timeit('tail_dgrad_generic', fl, lambda: call('tvae_linear_dgrad_x6', w3t, h1, None, None, None, F_, Nt, F_, Nt, Nt, 1, 0.01, in_xr=xr2, in_wc=wc2, in_gxr=gxr,
+                                                  in_part=partf, in_part_floats=partf.numel(), vg_wo=wo1, vg_gy=gy1, in_bc=bc2, in_lb=lb2, in_np=Np_, parts=PARTS))
     hbits = torch.zeros(F_, Nt // 32, dtype=torch.int32, device=dev).random_(-2 ** 31, 2 ** 31 - 1)
-    timeit('tail_wgrad_step', fl, lambda: call('tvae_linear_wgrad_x6', None, None, dW, ws, ws.numel(), F_, Nt, F_, Nt, Nt, 0, wo1, gy1, 1, 0.01, *va, hbits, PARTS))
-    timeit('tail_wgrad_from_H', fl, lambda: call('tvae_linear_wgrad_x6', h1, None, dW, ws, ws.numel(), F_, Nt, F_, Nt, Nt, 0, wo1, gy1, 1, 0.01, *va, None, PARTS))
-    timeit('tail_wgrad_virt', fl, lambda: call('tvae_linear_wgrad_x6', h1, h3, dW, ws, ws.numel(), F_, Nt, F_, Nt, Nt, 0, wo1, gy1, 1, 0.01, None, None, None, None, 0, None, PARTS))
+    timeit('tail_wgrad_step', fl, lambda: call('tvae_linear_wgrad_x6', None, None, dW, ws, ws.numel(), F_, Nt, F_, Nt, Nt, 0, vg_wo=wo1, vg_gy=gy1, vg_act=1,
+                                               vg_slope=0.01, **va, vg_bits=hbits, parts=PARTS))
+    timeit('tail_wgrad_from_H', fl, lambda: call('tvae_linear_wgrad_x6', h1, None, dW, ws, ws.numel(), F_, Nt, F_, Nt, Nt, 0, vg_wo=wo1, vg_gy=gy1, vg_act=1,
+                                                 vg_slope=0.01, **va, parts=PARTS))
+    timeit('tail_wgrad_virt', fl, lambda: call('tvae_linear_wgrad_x6', h1, h3, dW, ws, ws.numel(), F_, Nt, F_, Nt, Nt, 0, vg_wo=wo1, vg_gy=gy1, vg_act=1, vg_slope=0.01,
+                                               parts=PARTS))
 if only and 'enc' in only:
     # encoder tail (conv2 1x1x1 + head projection), current separate launches vs the fused split-pipe kernels
     nh = 7

@@ -26,10 +26,10 @@ for K in (128, 256, 384, 512):
     for nparts, split in ((3, 'tvae_dense_split3'), (2, 'tvae_dense_split2h')):
         w3 = torch.empty(query('tvae_dense_x6_bytes', M, K) // 4, device=dev)
         call(split, W, K, w3, w3.numel() * 4, M, K, 0, None, None)
-        for tag, extra in (('plain', (None, None, None)), ('coldot+bits', (wo, bo, yh))):
+        for tag, extra in (('plain', {}), ('coldot+bits', dict(col_w=wo, col_b=bo, col_y=yh))):
             def run():
-                call('tvae_linear_fwd_x6', w3, None, b, None, Y, M, Nt, K, Nt, Nt, 1, 0.01, *extra, xr, Wc, bc, LB, Np,
-                     bits if tag != 'plain' else None, nparts)
+                call('tvae_linear_fwd_x6', w3, None, b, None, Y, M, Nt, K, Nt, Nt, 1, 0.01, **extra, va_xr=xr, va_wc=Wc, va_bc=bc,
+                     va_lb=LB, va_np=Np, sign_bits=bits if tag != 'plain' else None, parts=nparts)
             for _ in range(2):
                 run()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

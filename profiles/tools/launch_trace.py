@@ -27,7 +27,7 @@ def traced(supported=()):
     """Inside: every ops.call is recorded instead of launched -- (name, arguments), a tensor as (shape, dtype, number of its
     buffer in order of first use) -- and ops.query answers `name in supported` to *_supported, 0 to *_ring, SIZE to the
     rest.  Yields the record: .launches, .paths (PATH_LOG), .parts (PARTS_LOG)."""
-    from tvae import ops
+    from tvae import _lib, ops
     rec = types.SimpleNamespace(launches=[], paths=set(), parts={})
     ids, alive = {}, []          # (every buffer is kept alive, so no address is handed out twice within a run)
 
@@ -37,7 +37,9 @@ def traced(supported=()):
         alive.append(a)
         return tuple(a.shape), str(a.dtype), ids.setdefault((a.untyped_storage().data_ptr(), a.storage_offset()), len(ids))
 
-    def call(name, *args):
+    def call(name, *args, **kwargs):
+        if kwargs:                   # the complete tuple: what the same launch written without keywords records
+            args = _lib.bind_args(name, args, kwargs)
         rec.launches.append((name,) + tuple(arg(a) for a in args))
 
     def query(name, *args):

@@ -3,11 +3,11 @@ linkage, t-SNE, alignment and class-statistics kernels.
 
 A library of its own beside libtvae_hip.so -- the ABI of the training kernels (tvae._lib.SIGNATURES, version 7) is not
 touched by the clustering half.  Same rules: no CPU fallback, tensors are checked by tvae._lib._ptr (GPU, contiguous,
-fp32 / int32) and every launch consults tvae._lib.CALL_HOOK exactly as tvae._lib.call does.
+fp32 / int32) and every launch goes through tvae._lib.dispatch, so it consults tvae._lib.CALL_HOOK as tvae._lib.call does.
 """
 from __future__ import annotations
 
-import ctypes
+import functools
 import os
 
 import torch
@@ -16,8 +16,7 @@ from . import _lib
 from ._lib import TvaeHipError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get('TVAE_CLUSTER_LIB') or os.path.join(os.path.dirname(_HERE), 'csrc', 'build',
-                                                              'libtvae_cluster.so')
+LIB_PATH = os.environ.get('TVAE_CLUSTER_LIB') or os.path.join(os.path.dirname(_HERE), 'csrc', 'build', 'libtvae_cluster.so')
 ABI_VERSION = 1
 
 # p = device pointer, i = int, l = long, f = float; the trailing stream argument is appended automatically
@@ -72,8 +71,6 @@ MAX_SIDE = 1024
 MAX_PLANES = 1 << 24
 MAX_CLASSES = 65535
 
-_cl = None
-
 
 def is_f32(t, contiguous=True) -> bool:
     """A CUDA fp32 tensor, contiguous unless the caller lays it out itself."""
@@ -101,59 +98,21 @@ def exported_symbols():
     return ['tvae_cluster_abi_version'] + sorted(SIGNATURES) + sorted(QUERIES)
 
 
+@functools.cache
 def lib():
     """Load the shared library once; fail loudly when it has not been built."""
-    global _cl
-    if _cl is None:
-        if not os.path.exists(LIB_PATH):
-            raise TvaeHipError(f'{LIB_PATH} not found: build it with `make -C target-vae_amd/csrc`.  '
-                               'There is no CPU fallback.')
-        L = ctypes.CDLL(LIB_PATH)
-        for name, sig in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = [_lib._CT[c] for c in sig] + [ctypes.c_void_p]
-        for name, (sig, ret) in QUERIES.items():
-            fn = getattr(L, name)
-            fn.restype = _lib._CT[ret]
-            fn.argtypes = [_lib._CT[c] for c in sig]
-        L.tvae_cluster_abi_version.restype = ctypes.c_int
-        if L.tvae_cluster_abi_version() != ABI_VERSION:
-            raise TvaeHipError(f'{LIB_PATH} has ABI version {L.tvae_cluster_abi_version()}, this package needs '
-                               f'{ABI_VERSION}: rebuild')
-        _cl = L
-    return _cl
+    return _lib.load_library(LIB_PATH, SIGNATURES, QUERIES, 'tvae_cluster_abi_version', ABI_VERSION,
+                             'build it with `make -C target-vae_amd/csrc`.  There is no CPU fallback.')
 
 
 def query(name, *args) -> int:
-    sig, _ = QUERIES[name]
-    if len(args) != len(sig):
-        raise TvaeHipError(f'{name}: expected {len(sig)} arguments, got {len(args)}')
-    return int(getattr(lib(), name)(*[int(a) for a in args]))
+    return _lib.run_query(lib, QUERIES, name, args)
 
 
 def call(name, *args):
     """Invoke an entry point of libtvae_cluster.so on the current torch stream."""
-    sig = SIGNATURES[name]
-    if len(args) != len(sig):
-        raise TvaeHipError(f'{name}: expected {len(sig)} arguments, got {len(args)}')
-    hook = _lib.CALL_HOOK
-    if hook is not None and not torch.cuda.is_current_stream_capturing():
-        return hook(name, sig, tuple(args), lambda a: _launch(name, sig, a))
-    _launch(name, sig, args)
+    return _lib.dispatch(lib, SIGNATURES, name, args)
 
 
 def _launch(name, sig, args):
-    conv = []
-    for pos, (c, a) in enumerate(zip(sig, args)):
-        if c == 'p':
-            conv.append(_lib._ptr(a, name, pos))
-        elif c == 'f':
-            conv.append(float(a))
-        else:
-            conv.append(int(a))
-    L = lib()
-    stream = torch.cuda.current_stream().cuda_stream
-    rc = getattr(L, name)(*conv, stream)
-    if rc != 0:
-        raise TvaeHipError(f'{name} failed with hipError_t {rc}')
+    _lib._launch(lib, name, sig, args)

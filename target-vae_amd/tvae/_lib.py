@@ -6,6 +6,7 @@ fp32/int32 CUDA(HIP) tensor, the call raises.  PyTorch is used only for device m
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 
 import torch
@@ -91,39 +92,43 @@ QUERIES = {
     'tvae_linear_wgrad_x6_ws_floats': ('iii', 'l'),
 }
 
-# trailing arguments a caller may leave out (beyond all-pointer tails, which are always optional)
-OPTIONAL_TAIL = {'tvae_linear_wgrad_x6': 6}      # rd_w, rd_ldw, rd_rowdot, a_amax, x_amax (ABI 5), x_amax_rows (ABI 6)
+# argument names of an entry point in header order (include/tvae_hip.h), for calls with keywords: everything before '|'
+# must be given, behind it only the names marked '!'; the rest default to NULL / 0 (bind_args)
+ARG_NAMES = {
+    'tvae_linear_fwd_x6': 'w3 X bias res Y M N K ldx ldy act slope | col_w col_b col_y va_xr va_wc va_bc va_lb va_np sign_bits parts! x_amax y_amax',
+    'tvae_linear_dgrad_x6': 'w3t dpre add aux dX M N K ldd ldx mask slope | in_xr in_wc in_gxr in_part in_part_floats vg_wo vg_gy vg_csum in_bc in_lb in_np rs_part rs_part_floats rs_wo rs_gysum rs_db rs_dwo parts! vg_bits rs_rowdot rs_bias x_amax y_amax',
+    'tvae_linear_wgrad_x6': 'dpre X dW ws ws_floats M N K ldd ldx accumulate | vg_wo vg_gy vg_act vg_slope! va_xr va_wc va_bc va_lb va_np vg_bits parts! rd_w rd_ldw rd_rowdot a_amax x_amax x_amax_rows',
+}
 
 _CT = {'p': ctypes.c_void_p, 'i': ctypes.c_int, 'l': ctypes.c_long, 'f': ctypes.c_float}
-_lib = None
+_REQUIRED = object()          # in the defaults of an entry point (_BINDINGS): no default, the caller must give the argument
 
 
 class TvaeHipError(RuntimeError):
     pass
 
 
+def load_library(path, signatures, queries, version_symbol, version, missing):
+    """CDLL of `path`, argument types set from the tables and ABI version checked; `missing`: what to do when it is not built."""
+    if not os.path.exists(path):
+        raise TvaeHipError(f'{path} not found: {missing}')
+    L = ctypes.CDLL(path)
+    launches = {name: (sig + 'p', 'i') for name, sig in signatures.items()}          # the stream goes last; a hipError_t comes back
+    for name, (sig, ret) in (launches | queries).items():
+        fn = getattr(L, name)
+        fn.restype = _CT[ret]
+        fn.argtypes = [_CT[c] for c in sig]
+    got = getattr(L, version_symbol)()
+    if got != version:
+        raise TvaeHipError(f'{path} has ABI version {got}, this package needs {version}: rebuild')
+    return L
+
+
+@functools.cache
 def lib():
     """Load the shared library once; fail loudly when it has not been built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise TvaeHipError(
-                f'{LIB_PATH} not found: build it with `make -C target-vae_amd/csrc` '
-                '(or __graft_entry__.build()).  There is no CPU fallback.')
-        L = ctypes.CDLL(LIB_PATH)
-        for name, sig in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = [_CT[c] for c in sig] + [ctypes.c_void_p]
-        for name, (sig, ret) in QUERIES.items():
-            fn = getattr(L, name)
-            fn.restype = _CT[ret]
-            fn.argtypes = [_CT[c] for c in sig]
-        L.tvae_abi_version.restype = ctypes.c_int
-        if L.tvae_abi_version() != ABI_VERSION:
-            raise TvaeHipError(f'{LIB_PATH} has ABI version {L.tvae_abi_version()}, this package needs {ABI_VERSION}: rebuild')
-        _lib = L
-    return _lib
+    return load_library(LIB_PATH, SIGNATURES, QUERIES, 'tvae_abi_version', ABI_VERSION,
+                        'build it with `make -C target-vae_amd/csrc` (or __graft_entry__.build()).  There is no CPU fallback.')
 
 
 ABI_VERSION = 7
@@ -273,12 +278,16 @@ def _rccl_rc(rc: int) -> str:
     return f'hipError_t {rc}'
 
 
-def query(name, *args) -> int:
-    """Pure host query of the library (geometry / workspace sizes); no GPU work."""
-    sig, _ = QUERIES[name]
+def run_query(lib, queries, name, args) -> int:
+    sig, _ = queries[name]
     if len(args) != len(sig):
         raise TvaeHipError(f'{name}: expected {len(sig)} arguments, got {len(args)}')
     return int(getattr(lib(), name)(*[int(a) for a in args]))
+
+
+def query(name, *args) -> int:
+    """Pure host query of the library (geometry / workspace sizes); no GPU work."""
+    return run_query(lib, QUERIES, name, args)
 
 
 # float64 arguments (the reference's ELBO / KL dtype), by (entry point, argument position): elbo / kld of tvae_elbo_reduce,
@@ -330,31 +339,60 @@ def set_call_hook(hook):
     return old
 
 
-def call(name, *args):
-    """Invoke a C-ABI entry point on the current torch stream."""
-    sig = SIGNATURES[name]
-    if len(args) < len(sig) and (set(sig[len(args):]) == {'p'} or len(sig) - len(args) <= OPTIONAL_TAIL.get(name, 0)):
-        # optional trailing arguments (added by later ABI versions): NULL pointers / zero strides
-        args = args + tuple(None if c == 'p' else 0 for c in sig[len(args):])
+def _binding(name):
+    lead, _, rest = ARG_NAMES[name].partition('|')
+    words = [w + '!' for w in lead.split()] + rest.split()
+    defaults = [(w.rstrip('!'), _REQUIRED if w.endswith('!') else {'p': None, 'i': 0, 'l': 0}[c])      # (a float never defaults)
+                for w, c in zip(words, SIGNATURES[name], strict=True)]
+    return [dict(defaults[n:]) for n in range(len(words) + 1)], [tuple(k for k, v in defaults[n:] if v is _REQUIRED) for n in range(len(words) + 1)]
+
+
+_BINDINGS = {name: _binding(name) for name in ARG_NAMES}  # name -> behind n positional arguments: ([n] name -> default, [n] required names)
+
+
+def bind_args(name, args, kwargs) -> tuple:
+    """The complete argument tuple of entry point `name` from a call's positional and keyword arguments: omitted optional
+    arguments of ARG_NAMES become None (pointers) / 0; without names, an all-pointer tail may be left off.  Pure host code."""
+    sig, n = SIGNATURES[name], len(args)
+    if n > len(sig):
+        raise TvaeHipError(f'{name}: expected {len(sig)} arguments, got {n}')
+    if name not in _BINDINGS:
+        if kwargs:
+            raise TvaeHipError(f'{name}: keyword argument {next(iter(kwargs))!r}, but the entry point has no ARG_NAMES')
+        if set(sig[n:]) - {'p'}:
+            raise TvaeHipError(f'{name}: expected {len(sig)} arguments, got {n}')
+        return tuple(args) + (None,) * (len(sig) - n)
+    rest, required = _BINDINGS[name][0][n], _BINDINGS[name][1][n]
+    full = {**rest, **kwargs}                        # (keeps the order of `rest`: a keyword replaces its default in place)
+    if len(full) != len(rest):
+        k = next(k for k in kwargs if k not in rest)
+        raise TvaeHipError(f'{name}: argument {k!r} ' + ('given twice (by position and by keyword)' if k in _BINDINGS[name][0][0] else 'is unknown'))
+    for k in required:
+        if full[k] is _REQUIRED:
+            raise TvaeHipError(f'{name}: required argument {k!r} missing')
+    return tuple(args) + tuple(full.values())
+
+
+def call(name, *args, **kwargs):
+    """Invoke a C-ABI entry point on the current torch stream; optional arguments of ARG_NAMES entries by keyword (bind_args)."""
+    if kwargs or len(args) != len(SIGNATURES[name]):
+        args = bind_args(name, args, kwargs)
+    return dispatch(lib, SIGNATURES, name, args)
+
+
+def dispatch(lib, signatures, name, args):
+    """Run entry point `name` of the library `lib()` on the complete argument tuple `args`, through CALL_HOOK when one is set."""
+    sig = signatures[name]
     if len(args) != len(sig):
         raise TvaeHipError(f'{name}: expected {len(sig)} arguments, got {len(args)}')
     hook = CALL_HOOK
     if hook is not None and not torch.cuda.is_current_stream_capturing():
-        return hook(name, sig, tuple(args), lambda a: _launch(name, sig, a))
-    _launch(name, sig, args)
+        return hook(name, sig, tuple(args), lambda a: _launch(lib, name, sig, a))
+    _launch(lib, name, sig, args)
 
 
-def _launch(name, sig, args):
-    L = lib()
-    conv = []
-    for pos, (c, a) in enumerate(zip(sig, args)):
-        if c == 'p':
-            conv.append(_ptr(a, name, pos))
-        elif c == 'f':
-            conv.append(float(a))
-        else:
-            conv.append(int(a))
-    stream = torch.cuda.current_stream().cuda_stream
-    rc = getattr(L, name)(*conv, stream)
+def _launch(lib, name, sig, args):
+    conv = [_ptr(a, name, pos) if c == 'p' else float(a) if c == 'f' else int(a) for pos, (c, a) in enumerate(zip(sig, args))]
+    rc = getattr(lib(), name)(*conv, torch.cuda.current_stream().cuda_stream)
     if rc != 0:
         raise TvaeHipError(f'{name} failed with hipError_t {rc}')

@@ -263,11 +263,11 @@ def _split_weight(W: torch.Tensor, rows: int, K: int, transpose: bool, key: str,
 
 
 def _wgrad(dpre, X, M, N, K, virt=None, va=None, act=0, bits=None, rowdot_w=None, a_amax=None, x_amax=None, ld=0):
-    """dW = dpre . X^T.  virt = (wo, gy, act): dpre is the saved activation H and the gradient wo[m]*gy[n]*act'(H) is formed
-    on the fly; va = (xr, Wc, bc, LB, Np): X is the coordinate layer's output act(..), recomputed (split-pipe path only).
+    """dW = dpre . X^T.  virt = dict(vg_wo, vg_gy, vg_act): dpre is the saved activation H, the gradient wo[m]*gy[n]*act'(H) is formed
+    on the fly; va = dict(va_xr, va_wc, va_bc, va_lb, va_np): X is the coordinate layer's output act(..), recomputed (split pipe only).
     bits: [H > 0] as stored sign bits (dpre may then be None).  rowdot_w = the layer's own weight [M][K]: also returns
     rowdot[m] = sum_k W[m][k] dW[m][k] / wo[m] (taken before the multiplication), as (dW, rowdot)."""
-    dev_ = (dpre if dpre is not None else (X if X is not None else virt[0])).device
+    dev_ = (dpre if dpre is not None else (X if X is not None else virt['vg_wo'])).device
     dW = torch.empty(M, K, dtype=torch.float32, device=dev_)
     need = 64 * max(M, 128) * max(K, 128)
     if split_pipe() and M >= 256 and K >= 128 and N % 16 == 0 and N >= 32:
@@ -275,17 +275,16 @@ def _wgrad(dpre, X, M, N, K, virt=None, va=None, act=0, bits=None, rowdot_w=None
         # h3 instance: the two-valued form from sign bits against the recomputed first-layer operand (two products per block)
         # ... or (round 4) against an operand from memory whose bound the caller supplies (x_amax), or two plain operands
         # from memory with both bounds (a_amax, x_amax)
-        lrf_bits = bits is not None and virt and virt[2] == ACT_LRELU
+        lrf_bits = bits is not None and virt and virt['vg_act'] == ACT_LRELU
         p = 2 if (parts() == 2 and ((lrf_bits and (va or x_amax is not None)) or
                                     (virt is None and va is None and a_amax is not None and x_amax is not None))) else _p3()
         rowdot = torch.empty(M, dtype=torch.float32, device=dev_) if rowdot_w is not None else None
-        with _timed('tvae_linear_wgrad_x6', p, bool(virt) and virt[2] == ACT_LRELU):
+        with _timed('tvae_linear_wgrad_x6', p, bool(virt) and virt['vg_act'] == ACT_LRELU):
+            bounds = dict(a_amax=a_amax, x_amax=x_amax) if p == 2 else {}
             call('tvae_linear_wgrad_x6', dpre, X, dW, ws, ws.numel(), M, N, K, ld or N, ld or N, 0,
-                 virt[0] if virt else None, virt[1] if virt else None, virt[2] if virt else act, LRELU_SLOPE,
-                 *(va if va else (None, None, None, None, 0)), bits, p,
-                 rowdot_w.contiguous() if rowdot_w is not None else None, K, rowdot,
-                 a_amax if p == 2 else None, x_amax if p == 2 else None,
-                 1 if (p == 2 and x_amax is not None and x_amax.numel() == K and K > 1) else 0)      # one bound per row of X
+                 **(virt or dict(vg_act=act)), vg_slope=LRELU_SLOPE, **(va or {}), vg_bits=bits, parts=p,
+                 rd_w=rowdot_w.contiguous() if rowdot_w is not None else None, rd_ldw=K, rd_rowdot=rowdot, **bounds,
+                 x_amax_rows=int(p == 2 and x_amax is not None and x_amax.numel() == K and K > 1))   # one bound per row of X
         return dW if rowdot_w is None else (dW, rowdot)
     _expect(virt is None and va is None and rowdot_w is None, 'implicit operands need the split-pipe weight gradient')
     ws = workspace(dev_, max(need, 1 << 24))
@@ -974,7 +973,7 @@ class DecoderFn(torch.autograd.Function):
         # without Fourier features the coordinate layer's output is two FMAs and an activation per element: the layers
         # that consume it (first hidden layer: forward, mask of the data gradient, weight gradient) recompute it and the
         # [hid][B*n^2] tensor is never written or read (virt_act)
-        va = (xr.view(Nt, 2), Wc.contiguous(), bc, LB, Np) if rt.virt_act else None
+        va = dict(va_xr=xr.view(Nt, 2), va_wc=Wc.contiguous(), va_bc=bc, va_lb=LB, va_np=Np) if rt.virt_act else None
         h = None if rt.virt_act else torch.empty(F_, ldn, dtype=torch.float32, device=dev)
         if rt.virt_act:
             _note('dec.virt_act')
@@ -1002,7 +1001,7 @@ class DecoderFn(torch.autograd.Function):
                 w3c = _split_weight(Wfull, F_, Ff + zx, False, 'x6_dense_wc', nparts=p_c)
                 with _timed('tvae_linear_fwd_x6', p_c):
                     call('tvae_linear_fwd_x6', w3c, feat_all, bc, None, h, F_, Nt, Ff + zx, ldn, ldn, act, LRELU_SLOPE,
-                         None, None, None, None, None, None, None, 0, None, p_c, feat_amax)
+                         parts=p_c, x_amax=feat_amax)
             else:
                 call('tvae_linear_fwd', Wc.contiguous(), feat, bc, LB, Np, None, h, F_, Nt, Ff, ldn, ldn, act, LRELU_SLOPE)
         else:
@@ -1055,8 +1054,8 @@ class DecoderFn(torch.autograd.Function):
                 emit = meas_words[li:li + 1] if (meas_words is not None and not last) else None
                 with _timed('tvae_linear_fwd_x6', p_l):
                     call('tvae_linear_fwd_x6', w3, hs[-1], b, hs[-1] if resid else None, hn, F_, Nt, F_, ldn, ldn, act,
-                         LRELU_SLOPE, Wo.contiguous() if fuse else None, bo if fuse else None, yh if fuse else None,
-                         *(va if va and li == 0 else (None, None, None, None, 0)), sbits, p_l, x_bound, emit)
+                         LRELU_SLOPE, **(dict(col_w=Wo.contiguous(), col_b=bo, col_y=yh) if fuse else {}),
+                         **(va if va and li == 0 else {}), sign_bits=sbits, parts=p_l, x_amax=x_bound, y_amax=emit)
                 h_meas[li + 1] = emit
                 _note('dec.fused_out' if fuse else 'dec.hidden_x6')
             else:
@@ -1130,7 +1129,7 @@ class DecoderFn(torch.autograd.Function):
                  part.numel(), tot)
         else:
             _note('dec.row_sums_in_dgrad')
-        vg = (Wo.contiguous().view(-1), gy.view(-1), act) if rt.virt_grad else None
+        vg = dict(vg_wo=Wo.contiguous().view(-1), vg_gy=gy.view(-1), vg_act=act) if rt.virt_grad else None
         if rt.virt_grad:
             _note('dec.virt_grad')
         dWo, drow = tot[1:], tot[0]
@@ -1149,13 +1148,13 @@ class DecoderFn(torch.autograd.Function):
             hprev = hs[li]
             use_vg = vg is not None and li == n_hidden - 1
             dsrc = hs[-1] if use_vg else d             # implicit operand: pass the saved activation instead
-            va = (xr.view(Nt, 2), Wc.contiguous(), bc, LB, Np) if hprev is None else None   # recomputed first layer
+            va = dict(va_xr=xr.view(Nt, 2), va_wc=Wc.contiguous(), va_bc=bc, va_lb=LB, va_np=Np) if hprev is None else None  # recomputed
             sbits = ctx.sbits if (use_vg and act == ACT_LRELU) else None      # [h > 0] as stored bits (two-valued form)
             # ... without the stored activation: the weight gradient also returns rowdot[m] = sum_k W[m][k] G[m][k] for dWo,
             # and the data gradient below the two row sums of the layer behind
             from_bits = use_vg and rt.no_h
             # h3 with the layer's input read from memory, under its bound: the two-valued form (round 4; its operand is
-            # gy[n] X[k][n], so times max |gy| -- vg[1] is gy: n_out == 1), or the plain form of two stored tensors (round 6)
+            # gy[n] X[k][n], so times max |gy| -- vg_gy is gy: n_out == 1), or the plain form of two stored tensors (round 6)
             xb = in_bound(li) if (rt.h3 and va is None and (sbits is not None if use_vg else d_bnd is not None)) else None
             plain_h3 = not use_vg and xb is not None
             if plain_h3:
@@ -1180,31 +1179,31 @@ class DecoderFn(torch.autograd.Function):
                     _note('dec.dgrad_h3_meas')
                 emit = dmeas[li:li + 1] if (dmeas is not None and not fuse_in) else None      # max |dprev| for its consumers
                 if two_val:
-                    w3t, csum = _split_weight(W, F_, F_, True, 'x6_dense_wt', scale=vg[0], nparts=p_d)
+                    w3t, csum = _split_weight(W, F_, F_, True, 'x6_dense_wt', scale=vg['vg_wo'], nparts=p_d)
                     _note('dec.virt_grad_2val')
                 else:
                     w3t, csum = _split_weight(W, F_, F_, True, 'x6_dense_wt', nparts=p_d), None
-                if fuse_in:
+                fin = {}
+                if fuse_in:                            # (hprev is None, so `va` is set, exactly here: hence in_bc / in_lb / in_np)
                     gxr_f = torch.empty(B, Np, 2, dtype=torch.float32, device=dev)
                     part_f = workspace(dev, (Nt // 128) * F_ * 3)
+                    fin = dict(in_xr=xr.view(Nt, 2), in_wc=Wc.contiguous(), in_gxr=gxr_f, in_part=part_f,
+                               in_part_floats=part_f.numel(), in_bc=bc, in_lb=LB, in_np=Np)
                 rs_part = _scratch(dev, 'dec_rs_part', (Nt // 128) * F_ * 2) if from_bits else None
+                rs = dict(rs_part=rs_part, rs_part_floats=rs_part.numel(), rs_wo=vg['vg_wo'], rs_gysum=dbo, rs_db=tot[0],
+                          rs_dwo=tot[1], vg_bits=sbits, rs_rowdot=rowdot, rs_bias=b) if from_bits else {}
                 with _timed('tvae_linear_dgrad_x6', p_d, two_val):
                     call('tvae_linear_dgrad_x6', w3t, dsrc, d if resid else None, hprev, dprev, F_, Nt, F_, ldn, ldn, act,
-                         LRELU_SLOPE, xr.view(Nt, 2) if fuse_in else None, Wc.contiguous() if fuse_in else None,
-                         gxr_f if fuse_in else None, part_f if fuse_in else None, part_f.numel() if fuse_in else 0,
-                         vg[0] if (use_vg and not two_val) else None, vg[1] if use_vg else None, csum,
-                         bc if va else None, LB if va else None, Np if va else 0,
-                         rs_part, rs_part.numel() if from_bits else 0, vg[0] if from_bits else None,
-                         dbo if from_bits else None, tot[0] if from_bits else None, tot[1] if from_bits else None, p_d,
-                         sbits if from_bits else None, rowdot, b if from_bits else None,
-                         d_bnd if (p_d == 2 and not two_val) else None, emit)
+                         LRELU_SLOPE, **fin, vg_wo=vg['vg_wo'] if (use_vg and not two_val) else None,
+                         vg_gy=vg['vg_gy'] if use_vg else None, vg_csum=csum, **rs, parts=p_d,
+                         x_amax=d_bnd if (p_d == 2 and not two_val) else None, y_amax=emit)
                 if fuse_in:
                     _note('dec.fuse_in')
                 d_bnd = emit
                 if two_val and li == 0 and has_f and rt.h3:
                     # the gradient this launch leaves in `dprev` is read again by the Fourier first layer's backward, under
                     # this analytic bound: |dX[k][n]| <= max |gy| * sum_m |wo[m] W[m][k]|
-                    d_bnd = gy_amax() * (W.detach().abs() * vg[0].detach().abs()[:, None]).sum(0).amax().reshape(1)
+                    d_bnd = gy_amax() * (W.detach().abs() * vg['vg_wo'].detach().abs()[:, None]).sum(0).amax().reshape(1)
             else:
                 call('tvae_linear_dgrad', W.contiguous(), d, d if resid else None, hprev, dprev, F_, Nt, F_, ldn, ldn,
                      act, LRELU_SLOPE)
@@ -1245,8 +1244,7 @@ class DecoderFn(torch.autograd.Function):
                 w3t = _split_weight(Wc, Ff, F_, True, 'x6_dense_wct', nparts=p_f)
                 with _timed('tvae_linear_dgrad_x6', p_f):
                     call('tvae_linear_dgrad_x6', w3t, d, None, None, dfeat, F_, Nt, Ff, ldn, ldn, ACT_NONE, LRELU_SLOPE,
-                         None, None, None, None, 0, None, None, None, None, None, 0, None, 0, None, None, None, None, p_f,
-                         None, None, None, d_bnd)
+                         parts=p_f, x_amax=d_bnd)
             else:
                 call('tvae_linear_dgrad', Wc.contiguous(), d, None, None, dfeat, F_, Nt, Ff, ldn, ldn, ACT_NONE, LRELU_SLOPE)
             call('tvae_fourier_bwd', xr, Wf.contiguous(), bf.contiguous(), sigma, dfeat, ldn, Ff, Nt, gxr)

@@ -46,9 +46,9 @@ def dev():
     return torch.device('cuda:0')
 
 
-def call(*a):
+def call(*a, **kw):
     from tvae._lib import call as c
-    return c(*a)
+    return c(*a, **kw)
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -173,10 +173,12 @@ class Case:
         if self.fuse:
             o['gxr'], o['part'] = nans(N, 2), nans(N // 128, K, 3)
         part = o.get('part')
-        call('tvae_linear_dgrad_x6', w3t, None, d['add'], d['aux'], o.get('dX_full'), M, N, K, N, self.ld, 1, SLOPE, d['xr'], d['wc'],
-             o.get('gxr'), part, part.numel() if self.fuse else 0, None, d['gy'], csum, d['bc'], d['lb'], self.Np, o['rs_part'],
-             o['rs_part'].numel(), d['wo'], d['gysum'], o['rs_db'] if fused_totals else None, o['rs_dwo'] if fused_totals else None,
-             parts, d['words'], d['rowdot'], d['bias'], None, amax)
+        call('tvae_linear_dgrad_x6', w3t, None, d['add'], d['aux'], o.get('dX_full'), M, N, K, N, self.ld, 1, SLOPE,
+             in_xr=d['xr'], in_wc=d['wc'], in_gxr=o.get('gxr'), in_part=part, in_part_floats=part.numel() if self.fuse else 0,
+             vg_gy=d['gy'], vg_csum=csum, in_bc=d['bc'], in_lb=d['lb'], in_np=self.Np, rs_part=o['rs_part'],
+             rs_part_floats=o['rs_part'].numel(), rs_wo=d['wo'], rs_gysum=d['gysum'],
+             rs_db=o['rs_db'] if fused_totals else None, rs_dwo=o['rs_dwo'] if fused_totals else None, parts=parts,
+             vg_bits=d['words'], rs_rowdot=d['rowdot'], rs_bias=d['bias'], y_amax=amax)
         if self.store:
             o['dX'] = o['dX_full'][:, :N]
         if self.fuse:
@@ -259,18 +261,19 @@ def test_dgrad_from_bits_chained_with_real_bits():
     assert float(pre.abs().min()) >= 1e-6
     H = torch.where(pre > 0, pre, 0.01 * pre)
     d = {k_: v.to(dev()) for k_, v in dict(xr=xr, wc=wc, bc=bc, lb=LB, W=W, b=b, wo=wo, gy=gy, cb=cb).items()}
-    va = (d['xr'], d['wc'], d['bc'], d['lb'], Np)
+    va = dict(va_xr=d['xr'], va_wc=d['wc'], va_bc=d['bc'], va_lb=d['lb'], va_np=Np)
     for parts in (3, 2):
         split = 'tvae_dense_split2h' if parts == 2 else 'tvae_dense_split3'
         w3 = torch.empty(query('tvae_dense_x6_bytes', M, K) // 4, device=dev())
         call(split, d['W'], K, w3, w3.numel() * 4, M, K, 0, None, None)
         words = torch.zeros(M, N // 32, dtype=torch.int32, device=dev())
         col_y = nans(N)
-        call('tvae_linear_fwd_x6', w3, None, d['b'], None, None, M, N, K, N, N, 1, SLOPE, d['wo'], d['cb'], col_y, *va, words, parts)
+        call('tvae_linear_fwd_x6', w3, None, d['b'], None, None, M, N, K, N, N, 1, SLOPE, col_w=d['wo'], col_b=d['cb'],
+             col_y=col_y, **va, sign_bits=words, parts=parts)
         ws = torch.empty(query('tvae_linear_wgrad_x6_ws_floats', M, N, K), device=dev())
         dW, rowdot = nans(M, K), nans(M)
-        call('tvae_linear_wgrad_x6', None, None, dW, ws, ws.numel(), M, N, K, N, N, 0, d['wo'], d['gy'], 1, SLOPE, *va, words, parts,
-             d['W'], K, rowdot)
+        call('tvae_linear_wgrad_x6', None, None, dW, ws, ws.numel(), M, N, K, N, N, 0, vg_wo=d['wo'], vg_gy=d['gy'], vg_act=1,
+             vg_slope=SLOPE, **va, vg_bits=words, parts=parts, rd_w=d['W'], rd_ldw=K, rd_rowdot=rowdot)
         host_words = words.cpu()
         bits = R.unpack(host_words)
         flips = int((bits != (pre > 0)).sum())
@@ -318,17 +321,17 @@ def test_dgrad_from_bits_refusals():
             if a[k_] is not None:
                 a[k_].fill_(NAN)
         with pytest.raises(Exception):
-            call('tvae_linear_dgrad_x6', *a.values())
+            call('tvae_linear_dgrad_x6', **a)
         for k_ in outputs:
             assert a[k_] is None or bool(torch.isnan(a[k_]).all()), k_
 
     base = setup(M)
-    call('tvae_linear_dgrad_x6', *base.values())                             # the unchanged arguments are a valid call
+    call('tvae_linear_dgrad_x6', **base)                                     # the unchanged arguments are a valid call
     assert all(bool(torch.isfinite(base[k_]).all()) for k_ in ('dX', 'rs_db', 'rs_dwo'))
     intail = dict(in_xr=xr.to(dev()), in_wc=wc.to(dev()), in_gxr=nans(N, 2), in_part=nans(N // 128, K, 3),
                   in_part_floats=(N // 128) * K * 3, in_bc=bc.to(dev()), in_lb=LB.to(dev()), in_np=Np, aux=None)
     fused = dict(base, **intail)
-    call('tvae_linear_dgrad_x6', *fused.values())                            # ... and so is the fused form that in_np = 96 changes
+    call('tvae_linear_dgrad_x6', **fused)                                    # ... and so is the fused form that in_np = 96 changes
     assert all(bool(torch.isfinite(fused[k_]).all()) for k_ in ('dX', 'in_gxr', 'in_part'))
     refused(base, vg_csum=None)                                              # vg_bits without vg_csum
     refused(base, rs_part=None, rs_part_floats=0)                            # vg_bits without rs_part

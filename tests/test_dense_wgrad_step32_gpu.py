@@ -32,9 +32,9 @@ def dev():
     return torch.device('cuda:0')
 
 
-def call(*a):
+def call(*a, **kw):
     from tvae._lib import call as c
-    return c(*a)
+    return c(*a, **kw)
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -84,8 +84,9 @@ def test_wgrad_from_bits_against_fp64(M, K, N, Np):
         tol = GEMM_TOL['f32'] if parts > 1 else BF16_TOL
         dW = torch.full((M, K), float('nan'), device=dev())
         rd = torch.full((M,), float('nan'), device=dev())
-        call('tvae_linear_wgrad_x6', None, None, dW, ws, ws.numel(), M, N, K, N, N, 0, wo_d, gy_d, 1, SLOPE, xr_d, Wc_d, bc_d,
-             LB_d, Np, bits_d, parts, W_d, K, rd)
+        call('tvae_linear_wgrad_x6', None, None, dW, ws, ws.numel(), M, N, K, N, N, 0, vg_wo=wo_d, vg_gy=gy_d, vg_act=1,
+             vg_slope=SLOPE, va_xr=xr_d, va_wc=Wc_d, va_bc=bc_d, va_lb=LB_d, va_np=Np, vg_bits=bits_d, parts=parts, rd_w=W_d,
+             rd_ldw=K, rd_rowdot=rd)
         e_dw, e_rd = rel_err(dW, ref_dW), rel_err(rd, ref_rd)
         print('M %d K %d N %d Np %d parts %d: rel_err dW %.3g rowdot %.3g' % (M, K, N, Np, parts, e_dw, e_rd))
         assert torch.isfinite(dW).all() and torch.isfinite(rd).all()

@@ -511,8 +511,8 @@ def test_trajectory_20_steps_golden(gemm_mode):
     out_arg = {'tvae_dec_l0_fwd': 4, 'tvae_linear_fwd': 6, 'tvae_conv1_fwd_dft': 3, 'tvae_conv1_fwd': 3, 'tvae_conv1_fwd_x6': 3}
     acts, real_call = [], ops.call
 
-    def recording_call(name, *args):
-        r = real_call(name, *args)
+    def recording_call(name, *args, **kwargs):
+        r = real_call(name, *args, **kwargs)
         if name in out_arg:
             acts.append(args[out_arg[name]].detach().clone())
         return r

@@ -38,9 +38,9 @@ def dev():
     return torch.device('cuda:0')
 
 
-def call(*a):
+def call(*a, **kw):
     from tvae._lib import call as c
-    return c(*a)
+    return c(*a, **kw)
 
 
 def query(*a):
@@ -216,8 +216,8 @@ def test_linear_fwd_dgrad_x6(M, N, K, act, use_res):
     cw, cb = rnd(M, seed=11), rnd(1, seed=12)
     cy = torch.empty(N, device=dev())
     fuse = M <= 512
-    call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), res.to(dev()) if use_res else None, Y, M, N, K, N, N, act,
-         SLOPE, cw.to(dev()) if fuse else None, cb.to(dev()) if fuse else None, cy if fuse else None, None, None, None, None, 0, None, 3)
+    call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), res.to(dev()) if use_res else None, Y, M, N, K, N, N, act, SLOPE,
+         col_w=cw.to(dev()) if fuse else None, col_b=cb.to(dev()) if fuse else None, col_y=cy if fuse else None, parts=3)
     if fuse:
         assert rel_err(cy, cw.double() @ ref + cb.double()) < GEMM_TOL['f32']
     assert rel_err(Y, ref) < GEMM_TOL['f32']
@@ -232,11 +232,11 @@ def test_linear_fwd_dgrad_x6(M, N, K, act, use_res):
     w3t = torch.empty(query('tvae_dense_x6_bytes', K, M) // 4, device=dev())
     call('tvae_dense_split3', Wd, K, w3t, w3t.numel() * 4, K, M, 1, None, None)
     dX = torch.empty(K, N, device=dev())
-    call('tvae_linear_dgrad_x6', w3t, d.to(dev()), add.to(dev()) if use_res else None, aux.to(dev()) if act else None,
-         dX, M, N, K, N, N, act, SLOPE, None, None, None, None, 0, None, None, None, None, None, 0, None, 0, None, None, None, None, 3)
+    call('tvae_linear_dgrad_x6', w3t, d.to(dev()), add.to(dev()) if use_res else None, aux.to(dev()) if act else None, dX, M, N,
+         K, N, N, act, SLOPE, parts=3)
     assert rel_err(dX, refg) < GEMM_TOL['f32']
     with pytest.raises(Exception):
-        call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, Y, M, N - 1, K, N, N, act, SLOPE, None, None, None, None, None, None, None, 0, None, 3)
+        call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, Y, M, N - 1, K, N, N, act, SLOPE, parts=3)
 
 
 @pytest.mark.parametrize('M,N,K,acc', [(512, 20000 // 16 * 16, 512, 0), (128, 8192, 128, 0), (300, 1600, 70, 1), (512, 4096, 512, 1)])
@@ -249,15 +249,16 @@ def test_linear_wgrad_x6(M, N, K, acc):
     from tvae._lib import query
     need = query('tvae_linear_wgrad_x6_ws_floats', M, N, K)
     assert 2 * M * K <= need <= ws.numel()
-    call('tvae_linear_wgrad_x6', d.to(dev()), X.to(dev()), dW, ws, ws.numel(), M, N, K, N, N, acc, None, None, 0, SLOPE, None, None, None, None, 0, None, 3)
+    call('tvae_linear_wgrad_x6', d.to(dev()), X.to(dev()), dW, ws, ws.numel(), M, N, K, N, N, acc, vg_slope=SLOPE, parts=3)
     assert rel_err(dW, ref) < GEMM_TOL['f32']
     dW2 = init.clone().to(dev()) if acc else torch.empty(M, K, device=dev())
-    call('tvae_linear_wgrad_x6', d.to(dev()), X.to(dev()), dW2, ws, need, M, N, K, N, N, acc, None, None, 0, SLOPE, None, None, None, None, 0, None, 3)
+    call('tvae_linear_wgrad_x6', d.to(dev()), X.to(dev()), dW2, ws, need, M, N, K, N, N, acc, vg_slope=SLOPE, parts=3)
     assert torch.equal(dW, dW2)          # the summation order does not depend on how much workspace is offered
     with pytest.raises(Exception):
-        call('tvae_linear_wgrad_x6', d.to(dev()), X.to(dev()), dW2, ws, need - 1, M, N, K, N, N, acc, None, None, 0, SLOPE, None, None, None, None, 0, None, 3)
+        call('tvae_linear_wgrad_x6', d.to(dev()), X.to(dev()), dW2, ws, need - 1, M, N, K, N, N, acc, vg_slope=SLOPE, parts=3)
     with pytest.raises(Exception):
-        call('tvae_linear_wgrad_x6', d.to(dev()), X.to(dev()), dW, ws, ws.numel(), M, N - 8, K, N, N, acc, None, None, 0, SLOPE, None, None, None, None, 0, None, 3)
+        call('tvae_linear_wgrad_x6', d.to(dev()), X.to(dev()), dW, ws, ws.numel(), M, N - 8, K, N, N, acc, vg_slope=SLOPE,
+             parts=3)
 
 
 @pytest.mark.parametrize('B,n,k,pad,C,R,act,Cin', [
@@ -536,8 +537,8 @@ def test_linear_dgrad_x6_fused_first_layer(F_, B, Np, M, act):
     call('tvae_dense_split3', W.to(dev()), F_, w3t, w3t.numel() * 4, F_, M, 1, None, None)
     gxr = torch.empty(Nt, 2, device=dev())
     part = torch.empty((Nt // 128) * F_ * 3, device=dev())
-    call('tvae_linear_dgrad_x6', w3t, d.to(dev()), None, aux.to(dev()), None, M, Nt, F_, Nt, Nt, act, SLOPE, xr.to(dev()),
-         Wc.to(dev()), gxr, part, part.numel(), None, None, None, None, None, 0, None, 0, None, None, None, None, 3)
+    call('tvae_linear_dgrad_x6', w3t, d.to(dev()), None, aux.to(dev()), None, M, Nt, F_, Nt, Nt, act, SLOPE, in_xr=xr.to(dev()),
+         in_wc=Wc.to(dev()), in_gxr=gxr, in_part=part, in_part_floats=part.numel(), parts=3)
     Simg = torch.empty(B, F_, device=dev())
     dbc = torch.empty(F_, device=dev())
     dWc = torch.empty(F_, 2, device=dev())
@@ -559,16 +560,16 @@ def test_linear_x6_implicit_gradient_operand():
     w3t = torch.empty(query('tvae_dense_x6_bytes', K, M) // 4, device=dev())
     call('tvae_dense_split3', W.to(dev()), K, w3t, w3t.numel() * 4, K, M, 1, None, None)
     dX = torch.empty(K, N, device=dev())
-    call('tvae_linear_dgrad_x6', w3t, H.to(dev()), None, aux.to(dev()), dX, M, N, K, N, N, 1, SLOPE, None, None, None,
-         None, 0, wo.to(dev()), gy.to(dev()), None, None, None, 0, None, 0, None, None, None, None, 3)
+    call('tvae_linear_dgrad_x6', w3t, H.to(dev()), None, aux.to(dev()), dX, M, N, K, N, N, 1, SLOPE, vg_wo=wo.to(dev()),
+         vg_gy=gy.to(dev()), parts=3)
     assert rel_err(dX, (W.double().t() @ d) * dact_ref(aux.double(), 1)) < GEMM_TOL['f32']
     # the same product in the two-valued form (LeakyReLU): weights scaled by wo before the split, 0 / 1 streamed operand
     csum = torch.empty(K, device=dev())
     call('tvae_dense_split3', W.to(dev()), K, w3t, w3t.numel() * 4, K, M, 1, wo.to(dev()), csum)
     assert rel_err(csum, (W.double() * wo.double()[:, None]).sum(0)) < TOL
     dX2 = torch.empty(K, N, device=dev())
-    call('tvae_linear_dgrad_x6', w3t, H.to(dev()), None, aux.to(dev()), dX2, M, N, K, N, N, 1, SLOPE, None, None, None,
-         None, 0, None, gy.to(dev()), csum, None, None, 0, None, 0, None, None, None, None, 3)
+    call('tvae_linear_dgrad_x6', w3t, H.to(dev()), None, aux.to(dev()), dX2, M, N, K, N, N, 1, SLOPE, vg_gy=gy.to(dev()),
+         vg_csum=csum, parts=3)
     assert rel_err(dX2, (W.double().t() @ d) * dact_ref(aux.double(), 1)) < GEMM_TOL['f32']
     # ... and with the row sums of the streamed activation against gy (ABI 3: what tvae_dec_out_bwd computes in a pass of its
     # own): the data gradient is bitwise the same launch result, db / dwo agree with fp64
@@ -578,19 +579,21 @@ def test_linear_x6_implicit_gradient_operand():
         csr = torch.empty(K, device=dev())
         call('tvae_dense_split3', W[:Mr].contiguous().to(dev()), K, w3r, w3r.numel() * 4, K, Mr, 1, wor.to(dev()), csr)
         dXa, dXb = torch.empty(K, N, device=dev()), torch.empty(K, N, device=dev())
-        call('tvae_linear_dgrad_x6', w3r, Hr.to(dev()), None, aux.to(dev()), dXa, Mr, N, K, N, N, 1, SLOPE, None, None, None,
-             None, 0, None, gy.to(dev()), csr, None, None, 0, None, 0, None, None, None, None, 3)
+        call('tvae_linear_dgrad_x6', w3r, Hr.to(dev()), None, aux.to(dev()), dXa, Mr, N, K, N, N, 1, SLOPE, vg_gy=gy.to(dev()),
+             vg_csum=csr, parts=3)
         rs_part = torch.full(((N // 128) * Mr * 2,), float('nan'), device=dev())
         gys = gy.sum().reshape(1).to(dev())
         rs_db, rs_dwo = torch.empty(Mr, device=dev()), torch.empty(Mr, device=dev())
-        call('tvae_linear_dgrad_x6', w3r, Hr.to(dev()), None, aux.to(dev()), dXb, Mr, N, K, N, N, 1, SLOPE, None, None, None,
-             None, 0, None, gy.to(dev()), csr, None, None, 0, rs_part, rs_part.numel(), wor.to(dev()), gys, rs_db, rs_dwo, 3)
+        call('tvae_linear_dgrad_x6', w3r, Hr.to(dev()), None, aux.to(dev()), dXb, Mr, N, K, N, N, 1, SLOPE, vg_gy=gy.to(dev()),
+             vg_csum=csr, rs_part=rs_part, rs_part_floats=rs_part.numel(), rs_wo=wor.to(dev()), rs_gysum=gys, rs_db=rs_db,
+             rs_dwo=rs_dwo, parts=3)
         assert torch.equal(dXa, dXb)
         assert rel_err(rs_db, (wor.double()[:, None] * gy.double()[None, :] * dact_ref(Hr.double(), 1)).sum(1)) < TOL
         assert rel_err(rs_dwo, Hr.double() @ gy.double()) < TOL
     with pytest.raises(Exception):         # the row sums need the two-valued form (csum) and a workspace of N/128 * M * 2
-        call('tvae_linear_dgrad_x6', w3t, H.to(dev()), None, aux.to(dev()), dX2, M, N, K, N, N, 1, SLOPE, None, None, None,
-             None, 0, None, gy.to(dev()), csum, None, None, 0, rs_part, 16, wo.to(dev()), gys, rs_db, rs_dwo, 3)
+        call('tvae_linear_dgrad_x6', w3t, H.to(dev()), None, aux.to(dev()), dX2, M, N, K, N, N, 1, SLOPE, vg_gy=gy.to(dev()),
+             vg_csum=csum, rs_part=rs_part, rs_part_floats=16, rs_wo=wo.to(dev()), rs_gysum=gys, rs_db=rs_db, rs_dwo=rs_dwo,
+             parts=3)
     # packed sign bits of the activation (the weight gradient below can read its 0 / 1 operand from them)
     def pack_bits(t):                      # bit (n & 31) of word n / 32 = [t[m][n] > 0]
         b = (t > 0).to(torch.int64).view(t.shape[0], -1, 32)
@@ -598,27 +601,26 @@ def test_linear_x6_implicit_gradient_operand():
         return (w - ((w >> 31) << 32)).to(torch.int32).contiguous()
     hb = pack_bits(H).to(dev())
     with pytest.raises(Exception):         # the two-valued form exists for LeakyReLU only
-        call('tvae_linear_dgrad_x6', w3t, H.to(dev()), None, aux.to(dev()), dX2, M, N, K, N, N, 2, SLOPE, None, None, None,
-             None, 0, None, gy.to(dev()), csum, None, None, 0, None, 0, None, None, None, None, 3)
+        call('tvae_linear_dgrad_x6', w3t, H.to(dev()), None, aux.to(dev()), dX2, M, N, K, N, N, 2, SLOPE, vg_gy=gy.to(dev()),
+             vg_csum=csum, parts=3)
     ws = torch.empty(1 << 26, device=dev())       # >= tvae_linear_wgrad_x6_ws_floats(M, N, K): slices x M x K
     for vact in (1, 2):                    # LeakyReLU: two-valued weight gradient; tanh: generic implicit operand
         dv = wo.double()[:, None] * gy.double()[None, :] * dact_ref(H.double(), vact)
         dW = torch.empty(M, K, device=dev())
-        call('tvae_linear_wgrad_x6', H.to(dev()), X.to(dev()), dW, ws, ws.numel(), M, N, K, N, N, 0, wo.to(dev()),
-             gy.to(dev()), vact, SLOPE, None, None, None, None, 0, None, 3)
+        call('tvae_linear_wgrad_x6', H.to(dev()), X.to(dev()), dW, ws, ws.numel(), M, N, K, N, N, 0, vg_wo=wo.to(dev()),
+             vg_gy=gy.to(dev()), vg_act=vact, vg_slope=SLOPE, parts=3)
         assert rel_err(dW, dv @ X.double().t()) < GEMM_TOL['f32'], vact
         if vact == 1:                      # the same from the packed sign bits: bitwise the same sums
             dWb = torch.empty(M, K, device=dev())
-            call('tvae_linear_wgrad_x6', None, X.to(dev()), dWb, ws, ws.numel(), M, N, K, N, N, 0, wo.to(dev()),
-                 gy.to(dev()), 1, SLOPE, None, None, None, None, 0, hb, 3)
+            call('tvae_linear_wgrad_x6', None, X.to(dev()), dWb, ws, ws.numel(), M, N, K, N, N, 0, vg_wo=wo.to(dev()),
+                 vg_gy=gy.to(dev()), vg_act=1, vg_slope=SLOPE, vg_bits=hb, parts=3)
             assert torch.equal(dWb, dW)
     # a LeakyReLU forward launch stores the sign bits of its output
     w3 = torch.empty(query('tvae_dense_x6_bytes', M, K) // 4, device=dev())
     call('tvae_dense_split3', W.to(dev()), K, w3, w3.numel() * 4, M, K, 0, None, None)
     Y = torch.empty(M, N, device=dev())
     yb = torch.empty(M, N // 32, dtype=torch.int32, device=dev())
-    call('tvae_linear_fwd_x6', w3, X.to(dev()), None, None, Y, M, N, K, N, N, 1, SLOPE, None, None, None, None, None,
-         None, None, 0, yb, 3)
+    call('tvae_linear_fwd_x6', w3, X.to(dev()), None, None, Y, M, N, K, N, N, 1, SLOPE, sign_bits=yb, parts=3)
     assert torch.equal(yb.cpu(), pack_bits(Y.cpu()))
     # dec_out_bwd without the gradient tensor: sums only
     F_ = M
@@ -645,7 +647,7 @@ def test_h3_decoder_entry_points(sw, sg, sx):
     call('tvae_dec_l0_fwd', xr, Wc, bc, LB, h0, Nt, F_, Nt, Np, act, SLOPE)
     W, b = rnd(M, F_, seed=5, scale=sw * F_ ** -0.5), rnd(M, seed=6, scale=sw)
     wo, gy = rnd(M, seed=8), rnd(Nt, seed=9) * sg
-    va = (xr, Wc, bc, LB, Np)
+    va = dict(va_xr=xr, va_wc=Wc, va_bc=bc, va_lb=LB, va_np=Np)
     H0 = h0.double().cpu()
     res = {}
     for nparts, split in ((3, 'tvae_dense_split3'), (2, 'tvae_dense_split2h')):
@@ -653,8 +655,8 @@ def test_h3_decoder_entry_points(sw, sg, sx):
         call(split, W.to(dev()), F_, w3, w3.numel() * 4, M, F_, 0, None, None)
         Y = torch.empty(M, Nt, device=dev())
         bits = torch.empty(M, Nt // 32, dtype=torch.int32, device=dev())
-        call('tvae_linear_fwd_x6', w3, None, b.to(dev()), None, Y, M, Nt, F_, Nt, Nt, act, SLOPE, None, None, None, *va, bits,
-             nparts)
+        call('tvae_linear_fwd_x6', w3, None, b.to(dev()), None, Y, M, Nt, F_, Nt, Nt, act, SLOPE, **va, sign_bits=bits,
+             parts=nparts)
         # two-valued data gradient of THIS layer's input from (wo, gy, Y): weights W^T diag(wo), 0 / 1 operand [Y > 0]
         w3t = torch.empty(query('tvae_dense_x6_bytes', F_, M) // 4, device=dev())
         csum = torch.empty(F_, device=dev())
@@ -663,12 +665,13 @@ def test_h3_decoder_entry_points(sw, sg, sx):
         rs_part = torch.full(((Nt // 128) * M * 2,), float('nan'), device=dev())
         gys = gy.sum().reshape(1).to(dev())
         rs_db, rs_dwo = torch.empty(M, device=dev()), torch.empty(M, device=dev())
-        call('tvae_linear_dgrad_x6', w3t, Y, None, h0, dX, M, Nt, F_, Nt, Nt, 1, SLOPE, None, None, None, None, 0, None,
-             gy.to(dev()), csum, None, None, 0, rs_part, rs_part.numel(), wo.to(dev()), gys, rs_db, rs_dwo, nparts)
+        call('tvae_linear_dgrad_x6', w3t, Y, None, h0, dX, M, Nt, F_, Nt, Nt, 1, SLOPE, vg_gy=gy.to(dev()), vg_csum=csum,
+             rs_part=rs_part, rs_part_floats=rs_part.numel(), rs_wo=wo.to(dev()), rs_gysum=gys, rs_db=rs_db, rs_dwo=rs_dwo,
+             parts=nparts)
         ws = torch.empty(query('tvae_linear_wgrad_x6_ws_floats', M, Nt, F_), device=dev())
         dW = torch.empty(M, F_, device=dev())
-        call('tvae_linear_wgrad_x6', None, None, dW, ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, wo.to(dev()), gy.to(dev()), 1, SLOPE,
-             *va, bits, nparts)
+        call('tvae_linear_wgrad_x6', None, None, dW, ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, vg_wo=wo.to(dev()),
+             vg_gy=gy.to(dev()), vg_act=1, vg_slope=SLOPE, **va, vg_bits=bits, parts=nparts)
         res[nparts] = (Y, dX, dW, rs_db, rs_dwo, bits)
         assert torch.isfinite(Y).all() and torch.isfinite(dX).all() and torch.isfinite(dW).all()
     Yd = res[3][0].double().cpu()                     # masks from the x6 forward (the two forwards may differ in a sign at 0)
@@ -699,8 +702,8 @@ def test_h3_decoder_entry_points(sw, sg, sx):
     w3h = torch.empty(query('tvae_dense_x6_bytes', M, F_) // 4, device=dev())
     call('tvae_dense_split2h', W.to(dev()), F_, w3h, w3h.numel() * 4, M, F_, 0, None, None)
     Yt = torch.empty(M, Nt, device=dev())
-    call('tvae_linear_fwd_x6', w3h, None, b.to(dev()), None, Yt, M, Nt, F_, Nt, Nt, 2, SLOPE, None, None, None, xr, Wc, bc, LB, Np,
-         None, 2)
+    call('tvae_linear_fwd_x6', w3h, None, b.to(dev()), None, Yt, M, Nt, F_, Nt, Nt, 2, SLOPE, va_xr=xr, va_wc=Wc, va_bc=bc,
+         va_lb=LB, va_np=Np, parts=2)
     assert rel_err(Yt, act_ref(W.double() @ h0t.double().cpu() + b.double()[:, None], 2)) < GEMM_TOL['f32']
 
 
@@ -716,26 +719,23 @@ def test_linear_x6_h3_memory_operand_bounds(slack):
     call('tvae_dense_split2h', W.to(dev()), K, w3, w3.numel() * 4, M, K, 0, None, None)
     xmax = (X.abs().max() * slack).reshape(1).to(dev())
     Y = torch.full((M, N), float('nan'), device=dev())
-    call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, Y, M, N, K, N, N, 1, SLOPE, None, None, None, None, None, None,
-         None, 0, None, 2, xmax)
+    call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, Y, M, N, K, N, N, 1, SLOPE, parts=2, x_amax=xmax)
     assert rel_err(Y, act_ref(W.double() @ X.double() + b.double()[:, None], 1)) < GEMM_TOL['f32']
     with pytest.raises(Exception):                       # h3 with an operand from memory needs its bound
-        call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, Y, M, N, K, N, N, 1, SLOPE, None, None, None, None, None,
-             None, None, 0, None, 2, None)
+        call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, Y, M, N, K, N, N, 1, SLOPE, parts=2)
     # plain data gradient dX = W^T d
     d = rnd(M, N, seed=4)
     w3t = torch.empty(query('tvae_dense_x6_bytes', K, M) // 4, device=dev())
     call('tvae_dense_split2h', W.to(dev()), K, w3t, w3t.numel() * 4, K, M, 1, None, None)
     dX = torch.full((K, N), float('nan'), device=dev())
     dmax = (d.abs().max() * slack).reshape(1).to(dev())
-    call('tvae_linear_dgrad_x6', w3t, d.to(dev()), None, None, dX, M, N, K, N, N, 0, SLOPE, None, None, None, None, 0, None, None,
-         None, None, None, 0, None, 0, None, None, None, None, 2, None, None, None, dmax)
+    call('tvae_linear_dgrad_x6', w3t, d.to(dev()), None, None, dX, M, N, K, N, N, 0, SLOPE, parts=2, x_amax=dmax)
     assert rel_err(dX, W.double().t() @ d.double()) < GEMM_TOL['f32']
     # plain weight gradient dW = d X^T
     ws = torch.empty(query('tvae_linear_wgrad_x6_ws_floats', M, N, K), device=dev())
     dW = torch.full((M, K), float('nan'), device=dev())
-    call('tvae_linear_wgrad_x6', d.to(dev()), X.to(dev()), dW, ws, ws.numel(), M, N, K, N, N, 0, None, None, 0, SLOPE, None, None,
-         None, None, 0, None, 2, None, 0, None, dmax, xmax)
+    call('tvae_linear_wgrad_x6', d.to(dev()), X.to(dev()), dW, ws, ws.numel(), M, N, K, N, N, 0, vg_slope=SLOPE, parts=2,
+         a_amax=dmax, x_amax=xmax)
     assert rel_err(dW, d.double() @ X.double().t()) < GEMM_TOL['f32']
 
 
@@ -774,12 +774,12 @@ def test_h3_row_dynamic_range_decoder(e):
     W[r0] *= s; b[r0] *= s                                # output row r0 of the layer
     W[:, k0] *= s                                         # input feature k0: row k0 of W^T (the data gradient's operand)
     wo, gy = rnd(M, seed=8), rnd(Nt, seed=9)
-    va = (xr, Wc, bc, LB, Np)
+    va = dict(va_xr=xr, va_wc=Wc, va_bc=bc, va_lb=LB, va_np=Np)
     w3 = torch.empty(query('tvae_dense_x6_bytes', M, F_) // 4, device=dev())
     call('tvae_dense_split2h', W.to(dev()), F_, w3, w3.numel() * 4, M, F_, 0, None, None)
     Y = torch.empty(M, Nt, device=dev())
     bits = torch.empty(M, Nt // 32, dtype=torch.int32, device=dev())
-    call('tvae_linear_fwd_x6', w3, None, b.to(dev()), None, Y, M, Nt, F_, Nt, Nt, act, SLOPE, None, None, None, *va, bits, 2)
+    call('tvae_linear_fwd_x6', w3, None, b.to(dev()), None, Y, M, Nt, F_, Nt, Nt, act, SLOPE, **va, sign_bits=bits, parts=2)
     ref_Y = act_ref(W.double() @ H0 + b.double()[:, None], act)
     assert row_rel_err(Y, ref_Y) < ROW_TOL
     assert float(ref_Y[r0].abs().max()) < 64 * s          # (the scaled row really is that small)
@@ -791,15 +791,15 @@ def test_h3_row_dynamic_range_decoder(e):
     rs_part = torch.empty((Nt // 128) * M * 2, device=dev())
     gys = gy.sum().reshape(1).to(dev())
     rs_db, rs_dwo = torch.empty(M, device=dev()), torch.empty(M, device=dev())
-    call('tvae_linear_dgrad_x6', w3t, Y, None, h0, dX, M, Nt, F_, Nt, Nt, 1, SLOPE, None, None, None, None, 0, None,
-         gy.to(dev()), csum, None, None, 0, rs_part, rs_part.numel(), wo.to(dev()), gys, rs_db, rs_dwo, 2)
+    call('tvae_linear_dgrad_x6', w3t, Y, None, h0, dX, M, Nt, F_, Nt, Nt, 1, SLOPE, vg_gy=gy.to(dev()), vg_csum=csum,
+         rs_part=rs_part, rs_part_floats=rs_part.numel(), rs_wo=wo.to(dev()), rs_gysum=gys, rs_db=rs_db, rs_dwo=rs_dwo, parts=2)
     d = wo.double()[:, None] * gy.double()[None, :] * dact_ref(Yd, 1)
     ref_dX = (W.double().t() @ d) * dact_ref(H0, 1)
     assert row_rel_err(dX, ref_dX) < ROW_TOL
     ws = torch.empty(query('tvae_linear_wgrad_x6_ws_floats', M, Nt, F_), device=dev())
     dW = torch.empty(M, F_, device=dev())
-    call('tvae_linear_wgrad_x6', None, None, dW, ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, wo.to(dev()), gy.to(dev()), 1, SLOPE,
-         *va, bits, 2)
+    call('tvae_linear_wgrad_x6', None, None, dW, ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, vg_wo=wo.to(dev()), vg_gy=gy.to(dev()),
+         vg_act=1, vg_slope=SLOPE, **va, vg_bits=bits, parts=2)
     ref_dW = d @ H0.t()
     assert row_rel_err(dW, ref_dW, dim=1) < ROW_TOL      # per COLUMN of dW = per row of the X operand
     assert float(ref_dW[:, u0].abs().max()) < 1e4 * s
@@ -808,13 +808,13 @@ def test_h3_row_dynamic_range_decoder(e):
     # exact to itself; with ONE bound for the tensor it loses the bits the unit lies below the others (measured here)
     rows = ((Wc.abs().sum(1) * xr.abs().max() + (bc[None, :] + LB).abs().amax(0)) * gy.abs().max()).contiguous()
     dWm = torch.empty(M, F_, device=dev())
-    call('tvae_linear_wgrad_x6', None, h0, dWm, ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, wo.to(dev()), gy.to(dev()), 1, SLOPE,
-         None, None, None, None, 0, bits, 2, None, 0, None, None, rows, 1)
+    call('tvae_linear_wgrad_x6', None, h0, dWm, ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, vg_wo=wo.to(dev()), vg_gy=gy.to(dev()),
+         vg_act=1, vg_slope=SLOPE, vg_bits=bits, parts=2, x_amax=rows, x_amax_rows=1)
     assert row_rel_err(dWm, ref_dW, dim=1) < ROW_TOL
     if e >= 24:
         dW1 = torch.empty(M, F_, device=dev())
-        call('tvae_linear_wgrad_x6', None, h0, dW1, ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, wo.to(dev()), gy.to(dev()), 1, SLOPE,
-             None, None, None, None, 0, bits, 2, None, 0, None, None, rows.amax().reshape(1), 0)
+        call('tvae_linear_wgrad_x6', None, h0, dW1, ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, vg_wo=wo.to(dev()),
+             vg_gy=gy.to(dev()), vg_act=1, vg_slope=SLOPE, vg_bits=bits, parts=2, x_amax=rows.amax().reshape(1))
         err1 = float(((dW1.double().cpu() - ref_dW)[:, u0]).abs().max() / ref_dW[:, u0].abs().max())
         assert err1 > 10 * ROW_TOL, err1                  # (the per-tensor bound really is the weaker form: the reason for the rows)
 
@@ -921,12 +921,11 @@ def test_linear_x6_recomputed_first_layer_operand(F_, B, Np, act, has_lb):
     w3t = torch.empty(query('tvae_dense_x6_bytes', F_, M) // 4, device=dev())
     call('tvae_dense_split3', W.to(dev()), F_, w3, w3.numel() * 4, M, F_, 0, None, None)
     call('tvae_dense_split3', W.to(dev()), F_, w3t, w3t.numel() * 4, F_, M, 1, None, None)
-    va = (xr, Wc, bc, LB, Np)
+    va = dict(va_xr=xr, va_wc=Wc, va_bc=bc, va_lb=LB, va_np=Np)
     # forward
     Y = [torch.empty(M, Nt, device=dev()) for _ in range(2)]
-    call('tvae_linear_fwd_x6', w3, h0, b.to(dev()), None, Y[0], M, Nt, F_, Nt, Nt, act, SLOPE, None, None, None,
-         None, None, None, None, 0, None, 3)
-    call('tvae_linear_fwd_x6', w3, None, b.to(dev()), None, Y[1], M, Nt, F_, Nt, Nt, act, SLOPE, None, None, None, *va, None, 3)
+    call('tvae_linear_fwd_x6', w3, h0, b.to(dev()), None, Y[0], M, Nt, F_, Nt, Nt, act, SLOPE, parts=3)
+    call('tvae_linear_fwd_x6', w3, None, b.to(dev()), None, Y[1], M, Nt, F_, Nt, Nt, act, SLOPE, **va, parts=3)
     assert torch.equal(Y[0], Y[1])
     assert rel_err(Y[0], act_ref(W.double() @ h0.double().cpu() + b.double()[:, None], act)) < GEMM_TOL['f32']
     # data gradient with the fused coordinate-layer backward
@@ -934,8 +933,9 @@ def test_linear_x6_recomputed_first_layer_operand(F_, B, Np, act, has_lb):
     for virt in (False, True):
         gxr = torch.empty(Nt, 2, device=dev())
         part = torch.empty((Nt // 128) * F_ * 3, device=dev())
-        call('tvae_linear_dgrad_x6', w3t, d, None, None if virt else h0, None, M, Nt, F_, Nt, Nt, act, SLOPE, xr, Wc,
-             gxr, part, part.numel(), None, None, None, bc if virt else None, LB if virt else None, Np if virt else 0, None, 0, None, None, None, None, 3)
+        call('tvae_linear_dgrad_x6', w3t, d, None, None if virt else h0, None, M, Nt, F_, Nt, Nt, act, SLOPE, in_xr=xr,
+             in_wc=Wc, in_gxr=gxr, in_part=part, in_part_floats=part.numel(), in_bc=bc if virt else None,
+             in_lb=LB if virt else None, in_np=Np if virt else 0, parts=3)
         outs.append((gxr, part))
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     d0 = (W.double().t() @ d.double().cpu()) * dact_ref(h0.double().cpu(), act)
@@ -943,15 +943,15 @@ def test_linear_x6_recomputed_first_layer_operand(F_, B, Np, act, has_lb):
     # weight gradient
     ws = torch.empty(1 << 26, device=dev())       # >= tvae_linear_wgrad_x6_ws_floats(M, N, K): slices x M x K
     dW = [torch.empty(M, F_, device=dev()) for _ in range(2)]
-    call('tvae_linear_wgrad_x6', d, h0, dW[0], ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, None, None, act, SLOPE,
-         None, None, None, None, 0, None, 3)
-    call('tvae_linear_wgrad_x6', d, None, dW[1], ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, None, None, act, SLOPE, *va, None, 3)
+    call('tvae_linear_wgrad_x6', d, h0, dW[0], ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, vg_act=act, vg_slope=SLOPE, parts=3)
+    call('tvae_linear_wgrad_x6', d, None, dW[1], ws, ws.numel(), M, Nt, F_, Nt, Nt, 0, vg_act=act, vg_slope=SLOPE, **va,
+         parts=3)
     assert torch.equal(dW[0], dW[1])
     assert rel_err(dW[1], d.double().cpu() @ h0.double().cpu().t()) < GEMM_TOL['f32']
     # images that are not whole column tiles are refused
     with pytest.raises(Exception):
-        call('tvae_linear_fwd_x6', w3, None, b.to(dev()), None, Y[1], M, Nt, F_, Nt, Nt, act, SLOPE, None, None, None,
-             xr, Wc, bc, LB, 96, None, 3)
+        call('tvae_linear_fwd_x6', w3, None, b.to(dev()), None, Y[1], M, Nt, F_, Nt, Nt, act, SLOPE, va_xr=xr, va_wc=Wc,
+             va_bc=bc, va_lb=LB, va_np=96, parts=3)
 
 
 def test_reductions():
@@ -1514,8 +1514,8 @@ def test_implicit_wgrad_and_multi_tile_dft_fp64():
     H = torch.randn(M, N, generator=g).clamp(-0.9, 0.9); X = torch.randn(K, N, generator=g)
     wo = torch.randn(M, generator=g); gy = torch.randn(N, generator=g)
     dW = torch.empty(M, K, device=dev()); ws = torch.empty(1 << 26, device=dev())       # >= tvae_linear_wgrad_x6_ws_floats(M, N, K): slices x M x K
-    call('tvae_linear_wgrad_x6', H.to(dev()), X.to(dev()), dW, ws, ws.numel(), M, N, K, N, N, 0, wo.to(dev()), gy.to(dev()), 1, 0.01,
-         None, None, None, None, 0, None, 3)
+    call('tvae_linear_wgrad_x6', H.to(dev()), X.to(dev()), dW, ws, ws.numel(), M, N, K, N, N, 0, vg_wo=wo.to(dev()),
+         vg_gy=gy.to(dev()), vg_act=1, vg_slope=0.01, parts=3)
     d = wo.double()[:, None] * gy.double()[None, :] * torch.where(H.double() > 0, 1.0, 0.01)
     e1 = rel(dW, d @ X.double().t())
     # frequency-domain convolution, forward + weight gradient, a batch whose (image, row) columns span several tiles
@@ -1685,8 +1685,8 @@ def test_linear_x6_lean_store_epilogue_and_measured_maximum(M, K, parts):
     for act in (1, 0):
         Y = torch.full((M, N), float('nan'), device=dev())
         amax = torch.zeros(1, device=dev())
-        call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, Y, M, N, K, N, N, act, SLOPE, None, None, None, None, None, None,
-             None, 0, None, parts, xmax, amax)
+        call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, Y, M, N, K, N, N, act, SLOPE, parts=parts, x_amax=xmax,
+             y_amax=amax)
         ref = act_ref(W.double() @ X.double() + b.double()[:, None], act)
         assert rel_err(Y, ref) < tol
         assert float(amax) == float(Y.abs().max())
@@ -1698,14 +1698,14 @@ def test_linear_x6_lean_store_epilogue_and_measured_maximum(M, K, parts):
     dmax = d.abs().max().reshape(1).to(dev()) if parts == 2 else None
     dX = torch.full((M, N), float('nan'), device=dev())
     amax = torch.zeros(1, device=dev())
-    call('tvae_linear_dgrad_x6', w3t, d.to(dev()), None, aux.to(dev()), dX, K, N, M, N, N, 1, SLOPE, None, None, None, None, 0, None,
-         None, None, None, None, 0, None, 0, None, None, None, None, parts, None, None, None, dmax, amax)
+    call('tvae_linear_dgrad_x6', w3t, d.to(dev()), None, aux.to(dev()), dX, K, N, M, N, N, 1, SLOPE, parts=parts, x_amax=dmax,
+         y_amax=amax)
     refg = (Wt.double().t() @ d.double()) * dact_ref(aux.double(), 1)
     assert rel_err(dX, refg) < tol
     assert float(amax) == float(dX.abs().max())
     with pytest.raises(Exception):                       # y_amax needs a stored output with nothing fused behind it
-        call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, None, M, N, K, N, N, 1, SLOPE, None, None, None, None, None, None,
-             None, 0, None, parts, xmax, amax)
+        call('tvae_linear_fwd_x6', w3, X.to(dev()), b.to(dev()), None, None, M, N, K, N, N, 1, SLOPE, parts=parts, x_amax=xmax,
+             y_amax=amax)
 
 
 # ---- the guard itself on the real library, and the entry points no other test of this file reaches --------------------------
@@ -1915,8 +1915,9 @@ def test_dgrad_rowsum_total(Mr, nparts):
         dX = torch.full((K, N), float('nan'), device=dev())
         part = torch.full(((N // 128) * Mr * 2,), float('nan'), device=dev())
         db, dwo = torch.full((Mr,), float('nan'), device=dev()), torch.full((Mr,), float('nan'), device=dev())
-        call('tvae_linear_dgrad_x6', w3, Hd, None, auxd, dX, Mr, N, K, N, N, 1, SLOPE, None, None, None, None, 0, None, gyd, cs,
-             None, None, 0, part, part.numel(), wod, gys, db if fused else None, dwo if fused else None, nparts)
+        call('tvae_linear_dgrad_x6', w3, Hd, None, auxd, dX, Mr, N, K, N, N, 1, SLOPE, vg_gy=gyd, vg_csum=cs, rs_part=part,
+             rs_part_floats=part.numel(), rs_wo=wod, rs_gysum=gys, rs_db=db if fused else None, rs_dwo=dwo if fused else None,
+             parts=nparts)
         if not fused:
             assert torch.isnan(db).all() and torch.isnan(dwo).all()
             call('tvae_dgrad_rowsum_total', part, N // 128, Mr, wod, gys, SLOPE, db, dwo, None, None)

@@ -26,13 +26,18 @@ def test_library_exports_every_declared_symbol():
     assert L.tvae_abi_version() == _lib.ABI_VERSION == 7
 
 
+def _declared_args(hdr, name):
+    """The parameter declarators of entry point `name` in the header text, the trailing stream included."""
+    m = re.search(r'\bint\s+' + name + r'\s*\(([^;]*?)\)\s*;', hdr, re.S)
+    assert m, name
+    return [a.strip() for a in m.group(1).split(',')]
+
+
 def test_signature_arity_matches_header():
     from tvae import _lib
     hdr = open(os.path.join(ROOT, 'include', 'tvae_hip.h')).read()
     for name, sig in _lib.SIGNATURES.items():
-        m = re.search(r'\bint\s+' + name + r'\s*\(([^;]*?)\)\s*;', hdr, re.S)
-        assert m, name
-        args = [a.strip() for a in m.group(1).split(',')]
+        args = _declared_args(hdr, name)
         assert args[-1].startswith('tvae_stream_t'), name
         assert len(args) - 1 == len(sig), (name, len(args) - 1, len(sig))
         for a, c in zip(args[:-1], sig):
@@ -44,6 +49,82 @@ def test_signature_arity_matches_header():
                 assert a.startswith('long '), (name, a)
             else:
                 assert a.startswith('int ') and '*' not in a, (name, a)
+
+
+def test_arg_names_match_header():
+    """ARG_NAMES spells the header's parameter names (the last identifier of each declarator), in order, one per code."""
+    from tvae import _lib
+    hdr = open(os.path.join(ROOT, 'include', 'tvae_hip.h')).read()
+    assert set(_lib.ARG_NAMES) == {'tvae_linear_fwd_x6', 'tvae_linear_dgrad_x6', 'tvae_linear_wgrad_x6'}
+    for name in _lib.ARG_NAMES:
+        declared = [re.findall(r'[A-Za-z_]\w*', a)[-1] for a in _declared_args(hdr, name)[:-1]]
+        rest, required = _lib._BINDINGS[name]
+        names, defaults = list(rest[0]), list(rest[0].values())
+        assert names == declared and len(names) == len(_lib.SIGNATURES[name]), name
+        for n in range(len(names) + 1):                # behind n positional arguments: the remaining defaults, the required names
+            assert list(rest[n].items()) == list(zip(names, defaults))[n:]
+            assert required[n] == tuple(k for k, d in rest[n].items() if d is _lib._REQUIRED)
+        # required: the leading run up to slope (wgrad: accumulate), parts, and every float; the others default to NULL / 0
+        lead = names.index('accumulate' if 'wgrad' in name else 'slope') + 1
+        for i, (n, c, d) in enumerate(zip(names, _lib.SIGNATURES[name], defaults)):
+            if i < lead or n == 'parts' or c == 'f':
+                assert d is _lib._REQUIRED, (name, n)
+            else:
+                assert d is None if c == 'p' else (d == 0 and isinstance(d, int)), (name, n)
+
+
+def test_bind_args_binds_like_the_positional_calls():
+    """Keyword calls of the three dense entry points against the complete positional tuples they replaced (sentinels in
+    place of tensors: bind_args looks at no argument), and the refusals."""
+    from tvae._lib import TvaeHipError, bind_args
+
+    class S:
+        def __init__(self, n):
+            self.n = n
+
+        def __repr__(self):
+            return self.n
+    w3t, d, dfeat, d_bnd, F_, Nt, Ff, ldn, p_f, SL = S('w3t'), S('d'), S('dfeat'), S('d_bnd'), 512, 6272, 1026, 6336, 2, 0.01
+    # the Fourier data gradient of DecoderFn.backward
+    full = (w3t, d, None, None, dfeat, F_, Nt, Ff, ldn, ldn, 0, SL,
+            None, None, None, None, 0, None, None, None, None, None, 0, None, 0, None, None, None, None, p_f,
+            None, None, None, d_bnd, None)
+    assert bind_args('tvae_linear_dgrad_x6', (w3t, d, None, None, dfeat, F_, Nt, Ff, ldn, ldn, 0, SL),
+                     dict(parts=p_f, x_amax=d_bnd)) == full
+    assert bind_args('tvae_linear_dgrad_x6', full, {}) == full                 # a complete positional tuple: unchanged
+    # the data gradient with the row sums of the layer behind (rs_*)
+    w3r, Hr, aux, dXb, gy, csr, rs_part, wor, gys, rs_db, rs_dwo = (S(n) for n in 'w3r Hr aux dXb gy csr rs_part wor gys rs_db rs_dwo'.split())
+    Mr, N, K = 160, 384, 128
+    full = (w3r, Hr, None, aux, dXb, Mr, N, K, N, N, 1, SL, None, None, None,
+            None, 0, None, gy, csr, None, None, 0, rs_part, 98304, wor, gys, rs_db, rs_dwo, 3, None, None, None, None, None)
+    assert bind_args('tvae_linear_dgrad_x6', (w3r, Hr, None, aux, dXb, Mr, N, K, N, N, 1, SL),
+                     dict(vg_gy=gy, vg_csum=csr, rs_part=rs_part, rs_part_floats=98304, rs_wo=wor, rs_gysum=gys, rs_db=rs_db,
+                          rs_dwo=rs_dwo, parts=3)) == full
+    # a forward with the recomputed first layer (*va), sign bits and parts
+    w3, b, Y, xr, Wc, bc, LB, bits = (S(n) for n in 'w3 b Y xr Wc bc LB bits'.split())
+    va = dict(va_xr=xr, va_wc=Wc, va_bc=bc, va_lb=LB, va_np=196)
+    full = (w3, None, b, None, Y, 512, Nt, 512, Nt, Nt, 1, SL, None, None, None, xr, Wc, bc, LB, 196, bits, 2, None, None)
+    assert bind_args('tvae_linear_fwd_x6', (w3, None, b, None, Y, 512, Nt, 512, Nt, Nt, 1, SL),
+                     dict(**va, sign_bits=bits, parts=2)) == full
+    assert bind_args('tvae_linear_fwd_x6', full[:22], {}) == full             # ... and the all-pointer tail left off
+    # a weight gradient with rd_* and the bounds
+    dW, ws, W, rowdot, am, xm = (S(n) for n in 'dW ws W rowdot am xm'.split())
+    full = (d, None, dW, ws, 1 << 24, 512, Nt, 512, ldn, ldn, 0, None, None, 1, SL, None, None, None, None, 0, bits, 2,
+            W, 512, rowdot, am, xm, 1)
+    assert bind_args('tvae_linear_wgrad_x6', (d, None, dW, ws, 1 << 24, 512, Nt, 512, ldn, ldn, 0),
+                     dict(vg_act=1, vg_slope=SL, vg_bits=bits, parts=2, rd_w=W, rd_ldw=512, rd_rowdot=rowdot, a_amax=am,
+                          x_amax=xm, x_amax_rows=1)) == full
+    lead = (w3, None, b, None, Y, 512, Nt, 512, Nt, Nt, 1, SL)
+    for name, args, kwargs, word in (
+            ('tvae_linear_fwd_x6', lead, dict(parts=2, col_z=Y), 'col_z'),                    # an unknown keyword
+            ('tvae_linear_fwd_x6', lead, dict(parts=2, slope=SL), 'slope'),                   # given twice
+            ('tvae_linear_fwd_x6', lead, dict(x_amax=xm), 'parts'),                           # a required one missing
+            ('tvae_linear_fwd_x6', lead[:-1], dict(parts=2), 'slope'),
+            ('tvae_linear_wgrad_x6', (d, None, dW, ws, 1 << 24, 512, Nt, 512, ldn, ldn, 0), dict(parts=2), 'vg_slope'),
+            ('tvae_linear_fwd_x6', full, {}, '28'),                                           # too many positional arguments
+            ('tvae_act_bwd', (d, d, d, 4, 1), dict(slope=SL), 'slope')):                      # a keyword without ARG_NAMES
+        with pytest.raises(TvaeHipError, match=name + '.*' + word):
+            bind_args(name, args, kwargs)
 
 
 def test_product_path_refuses_cpu_tensors():
