@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "../../include/tvae_hip.h"
 #include "gemm_f32_mfma.hpp"
@@ -36,6 +37,31 @@ static hipError_t allow_big_lds(KernelT kernel, size_t bytes) {
     if (bytes <= 48 * 1024) return hipSuccess;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)bytes);
+}
+// ONE launch: raises the kernel's dynamic-LDS limit where `lds` needs it, launches, returns the launch's error.  The arguments
+// convert to the kernel's parameter types implicitly, as in a direct launch.
+template <class KernelT, class... A>
+static int launch(KernelT kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, A... args) {
+    const hipError_t e = allow_big_lds(kernel, lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    return (int)hipGetLastError();
+}
+// A runtime number of parts (1: bf16 throughput mode, 2: h3, 3: exact split) as a compile-time constant:
+//   by_parts(parts, [&](auto np) { return launch(some_kernel<np.value>, ...); })
+// instantiates f for all THREE values, so it serves the kernels that exist in all three; by_flag does the same for a bool.
+template <class F>
+static int by_parts(int parts, F&& f) {
+    switch (parts) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return (int)hipErrorInvalidValue;
+    }
+}
+template <class F>
+static int by_flag(bool on, F&& f) {
+    return on ? f(std::true_type{}) : f(std::false_type{});
 }
 // number of split-K slices that brings a GEMM with `tiles` output tiles to ~4 workgroups per CU
 static inline int pick_splits(int tiles, long K) {

@@ -349,38 +349,31 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
     float* a1max = amax + q.o_a1max;
     float* EO = tab;
     float* ED = EO + ((q.eo_floats + 3) & ~3L);
-    hipError_t e = q.mixed ? allow_big_lds(dft_spectra_x_kernel, q.lds_sp) : allow_big_lds(dft_spectra_kernel, q.lds_sp);
-    if (e != hipSuccess) return (int)e;
     if (q.Mb != 2 * q.M) {                             // rows that pad 2M to the 512-row tile must be zero
-        e = dft_zero(W, q.w_floats, st);
+        hipError_t e = dft_zero(W, q.w_floats, st);
         if (e != hipSuccess) return (int)e;
     }
     constexpr bool spectra_mf = true;
     const int smax_ = n > ksz ? n : ksz;
-    if (q.mixed && spectra_mf && smax_ <= 128) {         // row transform on the fp32 matrix pipe (dft_spectra_x_mf_kernel)
-#define TVAE_SPX_MF(KSR_)                                                                                            \
-    do {                                                                                                            \
-        e = allow_big_lds(dft_spectra_x_mf_kernel<KSR_>, q.lds_sp);                                                 \
-        if (e != hipSuccess) return (int)e;                                                                         \
-        hipLaunchKernelGGL(dft_spectra_x_mf_kernel<KSR_>, dim3((unsigned)(B * Cin * q.nblk + q.M * Cin * q.nblkf)), dim3(256), \
-                           q.lds_sp, st, y, at, B, Cin, n, pad, q.Ho, q.NBpad, bank, W, ksz, q.M, q.Mb, q.L, q.Lh, q.FXB, q.nblk, \
-                           q.FXBf, q.nblkf, mxp);                                                                   \
-    } while (0)
-        if (smax_ <= 32) TVAE_SPX_MF(16); else if (smax_ <= 64) TVAE_SPX_MF(32); else TVAE_SPX_MF(64);
-#undef TVAE_SPX_MF
-    } else if (q.mixed)
-        hipLaunchKernelGGL(dft_spectra_x_kernel, dim3((unsigned)(B * Cin * q.nblk + q.M * Cin * q.nblkf)), dim3(256), q.lds_sp, st,
-                           y, at, B, Cin, n, pad, q.Ho, q.NBpad, bank, W, ksz, q.M, q.Mb, q.L, q.Lh, q.FXB, q.nblk, q.FXBf, q.nblkf,
-                           mxp);
-    else
-    hipLaunchKernelGGL(dft_spectra_kernel, dim3((unsigned)((B + q.M) * Cin * q.nblk)), dim3(256), q.lds_sp, st, y, at, B, Cin,
-                       n, pad, q.Ho, q.NBpad, bank, W, ksz, q.M, q.Mb, q.L, q.Lh, q.FXB, q.nblk, mxp);
-    TVAE_CHECK_LAUNCH();
+    int rc = 0;
+    if (q.mixed) {
+        auto go = [&](auto kernel) {
+            return launch(kernel, dim3((unsigned)(B * Cin * q.nblk + q.M * Cin * q.nblkf)), dim3(256), q.lds_sp, st, y, at, B, Cin, n,
+                          pad, q.Ho, q.NBpad, bank, W, ksz, q.M, q.Mb, q.L, q.Lh, q.FXB, q.nblk, q.FXBf, q.nblkf, mxp);
+        };
+        if (!spectra_mf || smax_ > 128) rc = go(dft_spectra_x_kernel);
+        else if (smax_ <= 32) rc = go(dft_spectra_x_mf_kernel<16>);    // row transform on the fp32 matrix pipe
+        else if (smax_ <= 64) rc = go(dft_spectra_x_mf_kernel<32>);
+        else rc = go(dft_spectra_x_mf_kernel<64>);
+    } else {
+        rc = launch(dft_spectra_kernel, dim3((unsigned)((B + q.M) * Cin * q.nblk)), dim3(256), q.lds_sp, st, y, at, B, Cin, n, pad,
+                    q.Ho, q.NBpad, bank, W, ksz, q.M, q.Mb, q.L, q.Lh, q.FXB, q.nblk, mxp);
+    }
+    if (rc) return rc;
     hipLaunchKernelGGL(dft_fmax_kernel, dim3(q.Lh), dim3(256), 0, st, (const float*)mxp.cmax, mxp.fmax, B);
     TVAE_CHECK_LAUNCH();
     // split the stacked spectral weights [Lh*2M rows][2L] into cells, then ONE batched launch of the split dense GEMM
     const int rows = q.Lh * q.Mb;
-    int rc = 0;
     if (h3) {
         const int Rp = x6_round_up(rows, DX6_ROWS), K8p = dense_k8pad(q.K2);
         rc = dense_split2h(W, q.K2, (uint4*)W3, rows, Rp, q.K2, K8p, 0, nullptr, mxp.wmax, st);
@@ -423,29 +416,29 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
             const long vt = (long)q.M * ((q.NB + 31) / 32);           // tiles with at least one real column
             const int cus = dev_cu_count();
             const int grid = (int)((vt + 3) / 4 < cus ? (vt + 3) / 4 : cus);
-#define TVAE_OUT_RING_ONE(L_, N_, R_, H_, TH_, T16_)                                                                  \
-    do {                                                                                                            \
-        const size_t lds_r = (size_t)4 * 3 * ((T16_) ? (2 * L_ + 15) / 16 : (L_ + 3) / 4) * 1024;                   \
-        e = allow_big_lds(dft_out_ring_kernel<L_, N_, R_, H_, TH_, T16_>, lds_r);                                   \
-        if (e != hipSuccess) return (int)e;                                                                         \
-        hipLaunchKernelGGL((dft_out_ring_kernel<L_, N_, R_, H_, TH_, T16_>), dim3(grid), dim3(256), lds_r, st,      \
-                           (const float*)T, (const float*)EO, bias, out, q.M, R, B, q.Lh, act, slope, a1max);       \
-    } while (0)
-#define TVAE_OUT_RING(L_, N_, R_, H_)                                                                               \
-    do {                                                                                                            \
-        if (act == ACT_TANH) { if (t16) TVAE_OUT_RING_ONE(L_, N_, R_, H_, true, true); else TVAE_OUT_RING_ONE(L_, N_, R_, H_, true, false); } \
-        else { if (t16) TVAE_OUT_RING_ONE(L_, N_, R_, H_, false, true); else TVAE_OUT_RING_ONE(L_, N_, R_, H_, false, false); } \
-    } while (0)
-            if (q.ring == 1) TVAE_OUT_RING(19, 1, false, 17);
-            else if (q.ring == 2) TVAE_OUT_RING(41, 1, true, 33);
-            else if (q.ring == 3) { if (act == ACT_TANH) TVAE_OUT_RING_ONE(31, 2, false, 39, true, false); else TVAE_OUT_RING_ONE(31, 2, false, 39, false, false); }
-            else if (q.ring == 4) TVAE_OUT_RING(23, 1, false, 17);
-            else if (q.ring == 5) TVAE_OUT_RING(49, 1, true, 33);
-            else TVAE_OUT_RING(34, 2, false, 39);
-#undef TVAE_OUT_RING
-#undef TVAE_OUT_RING_ONE
-            TVAE_CHECK_LAUNCH();
-            return 0;
+            // three ring slots per wave; the instance's frame constant is this frame's Lh, T in 2- or 4-byte elements
+            const size_t lds_r = (size_t)4 * 3 * (t16 ? (2 * q.Lh + 15) / 16 : (q.Lh + 3) / 4) * 1024;
+            auto go = [&](auto kernel) {
+                return launch(kernel, dim3(grid), dim3(256), lds_r, st, (const float*)T, (const float*)EO, bias, out, q.M, R, B, q.Lh,
+                              act, slope, a1max);
+            };
+            // dft_out_ring_kernel<Lh, NT, REM1, Ho, tanh, bf16 T>
+            return by_flag(act == ACT_TANH, [&](auto th) {
+                constexpr bool TH = decltype(th)::value;
+                switch (q.ring) {
+                    case 1: return t16 ? go(dft_out_ring_kernel<19, 1, false, 17, TH, true>)
+                                       : go(dft_out_ring_kernel<19, 1, false, 17, TH, false>);
+                    case 2: return t16 ? go(dft_out_ring_kernel<41, 1, true, 33, TH, true>)
+                                       : go(dft_out_ring_kernel<41, 1, true, 33, TH, false>);
+                    case 3: return go(dft_out_ring_kernel<31, 2, false, 39, TH, false>);       // (never bf16 storage: dft_t16)
+                    case 4: return t16 ? go(dft_out_ring_kernel<23, 1, false, 17, TH, true>)
+                                       : go(dft_out_ring_kernel<23, 1, false, 17, TH, false>);
+                    case 5: return t16 ? go(dft_out_ring_kernel<49, 1, true, 33, TH, true>)
+                                       : go(dft_out_ring_kernel<49, 1, true, 33, TH, false>);
+                    default: return t16 ? go(dft_out_ring_kernel<34, 2, false, 39, TH, true>)
+                                        : go(dft_out_ring_kernel<34, 2, false, 39, TH, false>);
+                }
+            });
         }
         if (r_out == DFT_R_H3) {
             // round 6: large frames in the h3 arithmetic leave the fp32 matrix pipe (which bounds them: conv_dft_h3_kernels.hpp)
@@ -459,14 +452,10 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
             frexpf(2.f * norm, &ex);                     // 2 norm in [2^(ex-1), 2^ex): h3_scale = 2^(15 - ex)
             const float eo_inv = ldexpf(1.f, ex - 15);
             constexpr size_t lds_h = ((size_t)16 * OH3_KS * 32 + 2 * 2 * OH3_KS * 32 * 4 + 32 + OH3_NWT * 32 * 33) * 4;
-            e = allow_big_lds(dft_out_h3_kernel<OH3_KS, OH3_NWT, OH3_NLD>, lds_h);
-            if (e != hipSuccess) return (int)e;
             const int cus = dev_cu_count();
             const int grid = (int)(ntiles < 2L * cus ? ntiles : 2L * cus);
-            hipLaunchKernelGGL((dft_out_h3_kernel<OH3_KS, OH3_NWT, OH3_NLD>), dim3(grid), dim3(64 * OH3_NWT), lds_h, st,
-                               (const float*)T, (const uint4*)EOc, bias, out, q.M, R, B, q.Ho, q.Lh, q.NBpad, act, slope, eo_inv, a1max);
-            TVAE_CHECK_LAUNCH();
-            return 0;
+            return launch(dft_out_h3_kernel<OH3_KS, OH3_NWT, OH3_NLD>, dim3(grid), dim3(64 * OH3_NWT), lds_h, st, (const float*)T,
+                          (const uint4*)EOc, bias, out, q.M, R, B, q.Ho, q.Lh, q.NBpad, act, slope, eo_inv, a1max);
         }
         // large frames (galaxy shape): a workgroup per tile, its waves split the output rows (dft_out_wide_kernel); the single
         // last column of Ho = 32 k + 1 outputs goes to the vector ALU instead of a whole wave
@@ -477,57 +466,48 @@ int tvae_conv1_fwd_dft(const float* y, const float* bank, const float* bias, flo
             const long fit = (long)(150 * 1024 / lds_w);
             const long wg_per_cu = fit < 2 ? fit : 2;
             const int grid = (int)(ntiles < wg_per_cu * cus ? ntiles : wg_per_cu * cus);
-#define TVAE_OUT_WIDE(LHR_, NLD_)                                                                                    \
-    do {                                                                                                            \
-        e = allow_big_lds(dft_out_wide_kernel<LHR_, NLD_>, lds_w);                                                  \
-        if (e != hipSuccess) return (int)e;                                                                         \
-        hipLaunchKernelGGL((dft_out_wide_kernel<LHR_, NLD_>), dim3(grid), dim3(64 * NTW), lds_w, st, (const float*)T, \
-                           (const float*)EO, bias, out, q.M, R, B, q.Ho, q.Lh, q.NBpad, q.NT, NTW, act, slope, a1max); \
-    } while (0)
+            auto go = [&](auto kernel) {
+                return launch(kernel, dim3(grid), dim3(64 * NTW), lds_w, st, (const float*)T, (const float*)EO, bias, out, q.M, R, B,
+                              q.Ho, q.Lh, q.NBpad, q.NT, NTW, act, slope, a1max);
+            };
             // float4 pieces per thread and tile: cdiv(16 Lh, 64 NTW) <= 6 in the 82-wide slot, <= 8 in the 96-wide one
-            if (r_out == DFT_R_OUT_WIDE82) TVAE_OUT_WIDE(82, 6); else TVAE_OUT_WIDE(DFT_WIDE_LH, 8);
-#undef TVAE_OUT_WIDE
-            TVAE_CHECK_LAUNCH();
-            return 0;
+            if (r_out == DFT_R_OUT_WIDE82) return go(dft_out_wide_kernel<82, 6>);
+            return go(dft_out_wide_kernel<DFT_WIDE_LH, 8>);
         }
         if (r_out > DFT_R_OUT_GEN && r_out <= DFT_R_OUT_GEN + 5) {
             const int grid = (int)((ntiles + 3) / 4 < 4096 ? (ntiles + 3) / 4 : 4096);
-#define TVAE_OUT_GEN(N_)                                                                                            \
-    hipLaunchKernelGGL(dft_out_gen_kernel<N_>, dim3(grid), dim3(256), 0, st, (const float*)T, (const float*)EO, bias, out, \
-                       q.M, R, B, q.Ho, q.Lh, q.NBpad, act, slope, a1max)
-            switch (r_out - DFT_R_OUT_GEN) {
-                case 1: TVAE_OUT_GEN(1); break;
-                case 2: TVAE_OUT_GEN(2); break;
-                case 3: TVAE_OUT_GEN(3); break;
-                case 4: TVAE_OUT_GEN(4); break;
-                default: TVAE_OUT_GEN(5); break;
+            auto go = [&](auto kernel) {
+                return launch(kernel, dim3(grid), dim3(256), 0, st, (const float*)T, (const float*)EO, bias, out, q.M, R, B, q.Ho,
+                              q.Lh, q.NBpad, act, slope, a1max);
+            };
+            switch (r_out - DFT_R_OUT_GEN) {             // NT
+                case 1: return go(dft_out_gen_kernel<1>);
+                case 2: return go(dft_out_gen_kernel<2>);
+                case 3: return go(dft_out_gen_kernel<3>);
+                case 4: return go(dft_out_gen_kernel<4>);
+                default: return go(dft_out_gen_kernel<5>);
             }
-#undef TVAE_OUT_GEN
-            TVAE_CHECK_LAUNCH();
-            return 0;
         }
-        if (r_out <= DFT_R_OUT_MF || r_out > DFT_R_OUT_MF + 9) return (int)hipErrorInvalidValue;
-        const int mf_l = (r_out - DFT_R_OUT_MF - 1) / 3, mf_v = (r_out - DFT_R_OUT_MF - 1) % 3;      // LHP 23 / 49 / 64; instance
         const size_t lds_o = ((size_t)q.LHP * NTT * 64 + (size_t)4 * 32 * (q.Ho | 1)) * 4;
         const int grid = (int)((ntiles + 3) / 4 < 768 ? (ntiles + 3) / 4 : 768);
         const int iters = (int)((ntiles + 4L * grid - 1) / (4L * grid));
-#define TVAE_OUT_MF(L_, N_, R_)                                                                                     \
-    do {                                                                                                            \
-        e = allow_big_lds(dft_out_mf_kernel<L_, N_, R_>, lds_o);                                                    \
-        if (e != hipSuccess) return (int)e;                                                                         \
-        hipLaunchKernelGGL((dft_out_mf_kernel<L_, N_, R_>), dim3(grid), dim3(256), lds_o, st, (const float*)T,      \
-                           (const float*)EO, bias, out, q.M, R, B, q.Ho, q.Lh, q.NBpad, act, slope, iters, a1max); \
-    } while (0)
-#define TVAE_OUT_MF_L(L_)                                                                                           \
-    do {                                                                                                            \
-        if (mf_v == 1) TVAE_OUT_MF(L_, 1, true); else if (mf_v == 0) TVAE_OUT_MF(L_, 1, false); else TVAE_OUT_MF(L_, 2, false); \
-    } while (0)
-        if (mf_l == 0) TVAE_OUT_MF_L(23); else if (mf_l == 1) TVAE_OUT_MF_L(49); else TVAE_OUT_MF_L(64);
-#undef TVAE_OUT_MF_L
-#undef TVAE_OUT_MF
-        TVAE_CHECK_LAUNCH();
+        auto go = [&](auto kernel) {
+            return launch(kernel, dim3(grid), dim3(256), lds_o, st, (const float*)T, (const float*)EO, bias, out, q.M, R, B, q.Ho,
+                          q.Lh, q.NBpad, act, slope, iters, a1max);
+        };
+        switch (r_out - DFT_R_OUT_MF) {                  // 3 i + v (DftRouteId): dft_out_mf_kernel<LHP, NT, REM1>
+            case 1: return go(dft_out_mf_kernel<23, 1, false>);
+            case 2: return go(dft_out_mf_kernel<23, 1, true>);
+            case 3: return go(dft_out_mf_kernel<23, 2, false>);
+            case 4: return go(dft_out_mf_kernel<49, 1, false>);
+            case 5: return go(dft_out_mf_kernel<49, 1, true>);
+            case 6: return go(dft_out_mf_kernel<49, 2, false>);
+            case 7: return go(dft_out_mf_kernel<64, 1, false>);
+            case 8: return go(dft_out_mf_kernel<64, 1, true>);
+            case 9: return go(dft_out_mf_kernel<64, 2, false>);
+            default: return (int)hipErrorInvalidValue;
+        }
     }
-    return 0;
 }
 
 int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float* dbias, float* ws, long ws_floats, int B,
@@ -553,6 +533,7 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
     float* EO = tab;
     float* ED = EO + ((q.eo_floats + 3) & ~3L);
     {
+        int rc = 0;
         hipLaunchKernelGGL(dft_wtab_kernel, dim3(64), dim3(256), 0, st, EO, ED, q.L, q.Lh, q.Ho, q.LHP, q.NT,
                            q.NT + q.REM1, q.NS, q.NRT, q.mixed ? 1.f / (float)q.L : 1.f / ((float)q.L * (float)q.L));
         TVAE_CHECK_LAUNCH();
@@ -560,26 +541,22 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
         if (r_dy == q.ring) {                                         // ring ids 1 .. 6
             const int cus = dev_cu_count();
             const int grid = (int)((ntiles + 3) / 4 < 2 * cus ? (ntiles + 3) / 4 : 2 * cus);
-            hipError_t er = hipSuccess;
-#define TVAE_DY_RING_ONE(S_, T_, L2_, H_, Q_, S16_)                                                                  \
-    do {                                                                                                            \
-        const size_t lds_r = (size_t)4 * 2 * ((32 * H_ + 63) / 64) * 256;                                           \
-        er = allow_big_lds(dft_dy_ring_kernel<S_, T_, L2_, H_, Q_, S16_>, lds_r);                                   \
-        if (er != hipSuccess) return (int)er;                                                                       \
-        hipLaunchKernelGGL((dft_dy_ring_kernel<S_, T_, L2_, H_, Q_, S16_>), dim3(grid), dim3(256), lds_r, st, dpre, \
-                           (const float*)ED, Sp, q.M, R, B, q.Lh, q.NBpad, smax);                                   \
-    } while (0)
-#define TVAE_DY_RING(S_, T_, L2_, H_, Q_)                                                                           \
-    do { if (s16) TVAE_DY_RING_ONE(S_, T_, L2_, H_, Q_, true); else TVAE_DY_RING_ONE(S_, T_, L2_, H_, Q_, false); } while (0)
-            if (q.ring == 1) TVAE_DY_RING(9, 2, 38, 17, false);
-            else if (q.ring == 2) TVAE_DY_RING(17, 3, 82, 33, false);
-            else if (q.ring == 3) TVAE_DY_RING(20, 2, 62, 39, false);
-            else if (q.ring == 4) TVAE_DY_RING(9, 2, 46, 17, false);
-            else if (q.ring == 5) TVAE_DY_RING(17, 3, 98, 33, true);
-            else TVAE_DY_RING(20, 3, 68, 39, false);
-#undef TVAE_DY_RING
-#undef TVAE_DY_RING_ONE
-            TVAE_CHECK_LAUNCH();
+            const size_t lds_r = (size_t)4 * 2 * ((32 * q.Ho + 63) / 64) * 256;     // (the instance's HO is this frame's Ho)
+            auto go = [&](auto kernel) {
+                return launch(kernel, dim3(grid), dim3(256), lds_r, st, dpre, (const float*)ED, Sp, q.M, R, B, q.Lh, q.NBpad, smax);
+            };
+            // dft_dy_ring_kernel<NS, NRT, 2 Lh, Ho, Nyquist pair on the vector ALU, bf16 S'>
+            rc = by_flag(s16, [&](auto s16_) {
+                constexpr bool S16 = decltype(s16_)::value;
+                switch (q.ring) {
+                    case 1: return go(dft_dy_ring_kernel<9, 2, 38, 17, false, S16>);
+                    case 2: return go(dft_dy_ring_kernel<17, 3, 82, 33, false, S16>);
+                    case 3: return go(dft_dy_ring_kernel<20, 2, 62, 39, false, S16>);
+                    case 4: return go(dft_dy_ring_kernel<9, 2, 46, 17, false, S16>);
+                    case 5: return go(dft_dy_ring_kernel<17, 3, 98, 33, true, S16>);
+                    default: return go(dft_dy_ring_kernel<20, 3, 68, 39, false, S16>);
+                }
+            });
         } else if (r_dy == DFT_R_H3) {
             // round 6: the same transform on the 16-bit matrix pipe (conv_dft_h3_kernels.hpp)
             uint4* EOc = reinterpret_cast<uint4*>(ED + ((q.ed_floats + 3) & ~3L) + ((q.M + 3) & ~3L));
@@ -588,13 +565,10 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
                                DH3_NKT, q.mixed ? 1.f / (float)q.L : 1.f / ((float)q.L * (float)q.L));
             TVAE_CHECK_LAUNCH();
             const size_t lds_h = ((size_t)((32 * (q.Ho | 1) + 3) & ~3) + 2 * 2 * DH3_WS * 32 * 4 + 32) * 4;
-            hipError_t eh = allow_big_lds(dft_dy_h3_kernel<DH3_WS, DH3_NKT, DH3_NLD>, lds_h);
-            if (eh != hipSuccess) return (int)eh;
             const int cus = dev_cu_count();
             const int gridh = (int)(ntiles < 2L * cus ? ntiles : 2L * cus);
-            hipLaunchKernelGGL((dft_dy_h3_kernel<DH3_WS, DH3_NKT, DH3_NLD>), dim3(gridh), dim3(64 * DH3_NKT), lds_h, st, dpre,
-                               (const uint4*)EDc, Sp, q.M, R, B, q.Ho, q.Lh, q.NBpad, ldexpf(1.f, -14), smax);
-            TVAE_CHECK_LAUNCH();
+            rc = launch(dft_dy_h3_kernel<DH3_WS, DH3_NKT, DH3_NLD>, dim3(gridh), dim3(64 * DH3_NKT), lds_h, st, dpre,
+                        (const uint4*)EDc, Sp, q.M, R, B, q.Ho, q.Lh, q.NBpad, ldexpf(1.f, -14), smax);
         } else if (r_dy >= DFT_R_DY_WIDE50 && r_dy <= DFT_R_DY_WIDE80) {
             // large frames (galaxy shape): a workgroup per tile, its waves split the rows of S' (dft_dy_wide_kernel)
             const int NSR = r_dy == DFT_R_DY_WIDE50 ? 50 : (r_dy == DFT_R_DY_WIDE66 ? 66 : DFT_WIDE_NS);   // the instance's slot
@@ -603,53 +577,38 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
             const long fit = (long)(150 * 1024 / lds_w);
             const long wg_per_cu = fit < 2 ? fit : 2;
             const int gridw = (int)(ntiles < wg_per_cu * cus ? ntiles : wg_per_cu * cus);
-            hipError_t ew = hipSuccess;
-#define TVAE_DY_WIDE(NSR_, NLD_, WPE_)                                                                               \
-    do {                                                                                                            \
-        ew = allow_big_lds(dft_dy_wide_kernel<NSR_, NLD_, WPE_>, lds_w);                                            \
-        if (ew != hipSuccess) return (int)ew;                                                                       \
-        hipLaunchKernelGGL((dft_dy_wide_kernel<NSR_, NLD_, WPE_>), dim3(gridw), dim3(64 * q.NRT), lds_w, st, dpre,  \
-                           (const float*)ED, Sp, q.M, R, B, q.Ho, q.Lh, q.NBpad, q.NS, q.NRT, smax);                \
-    } while (0)
+            auto go = [&](auto kernel) {
+                return launch(kernel, dim3(gridw), dim3(64 * q.NRT), lds_w, st, dpre, (const float*)ED, Sp, q.M, R, B, q.Ho, q.Lh,
+                              q.NBpad, q.NS, q.NRT, smax);
+            };
             // (an instance at three waves per SIMD -- two of the galaxy shape's six-wave workgroups per CU, 168 registers with 17
             //  spilled -- measured 2.17 ms against 2.05 for this one)
-            if (NSR == 50) TVAE_DY_WIDE(50, 16, 2);
-            else if (NSR == 66) TVAE_DY_WIDE(66, 16, 2);
-            else TVAE_DY_WIDE(DFT_WIDE_NS, 16, 2);
-#undef TVAE_DY_WIDE
-            TVAE_CHECK_LAUNCH();
+            if (NSR == 50) rc = go(dft_dy_wide_kernel<50, 16, 2>);
+            else if (NSR == 66) rc = go(dft_dy_wide_kernel<66, 16, 2>);
+            else rc = go(dft_dy_wide_kernel<DFT_WIDE_NS, 16, 2>);
         } else if (r_dy == DFT_R_DY_GEN) {
             const size_t lds_g = (size_t)4 * 32 * ((2 * q.NS) | 1) * 4;
-            hipError_t eg = allow_big_lds(dft_dy_gen_kernel, lds_g);
-            if (eg != hipSuccess) return (int)eg;
             const int gridg = (int)((ntiles + 3) / 4 < 4096 ? (ntiles + 3) / 4 : 4096);
-            hipLaunchKernelGGL(dft_dy_gen_kernel, dim3(gridg), dim3(256), lds_g, st, dpre, (const float*)ED, Sp, q.M, R, B,
-                               q.Ho, q.Lh, q.NBpad, q.NS, q.NRT, smax);
-            TVAE_CHECK_LAUNCH();
+            rc = launch(dft_dy_gen_kernel, dim3(gridg), dim3(256), lds_g, st, dpre, (const float*)ED, Sp, q.M, R, B, q.Ho, q.Lh,
+                        q.NBpad, q.NS, q.NRT, smax);
         } else {
-        if (r_dy <= DFT_R_DY_MF || r_dy > DFT_R_DY_MF + 5) return (int)hipErrorInvalidValue;
-        const size_t lds_d = ((size_t)q.NS * q.NRT * 64 + (size_t)4 * (32 * ((2 * q.NS) | 1) + 64)) * 4;
-        const int grid = (int)((ntiles + 3) / 4 < 768 ? (ntiles + 3) / 4 : 768);
-        const int iters = (int)((ntiles + 4L * grid - 1) / (4L * grid));
-        hipError_t e0 = hipSuccess;
-#define TVAE_DY_MF(S_, T_, L2_, A_)                                                                                 \
-    do {                                                                                                            \
-        e0 = allow_big_lds(dft_dy_mf_kernel<S_, T_, L2_, A_>, lds_d);                                               \
-        if (e0 != hipSuccess) return (int)e0;                                                                       \
-        hipLaunchKernelGGL((dft_dy_mf_kernel<S_, T_, L2_, A_>), dim3(grid), dim3(256), lds_d, st, dpre,             \
-                           (const float*)ED, Sp, q.M, R, B, q.Ho, q.Lh, q.NBpad, iters,                             \
-                           smax);                                                        \
-    } while (0)
-        switch (r_dy - DFT_R_DY_MF) {
-            case 1: TVAE_DY_MF(9, 2, 46, true); break;
-            case 2: TVAE_DY_MF(9, 2, 0, true); break;
-            case 3: TVAE_DY_MF(17, 4, 98, true); break;
-            case 4: TVAE_DY_MF(17, 4, 0, true); break;
-            default: TVAE_DY_MF(32, 4, 0, false); break;
+            const size_t lds_d = ((size_t)q.NS * q.NRT * 64 + (size_t)4 * (32 * ((2 * q.NS) | 1) + 64)) * 4;
+            const int grid = (int)((ntiles + 3) / 4 < 768 ? (ntiles + 3) / 4 : 768);
+            const int iters = (int)((ntiles + 4L * grid - 1) / (4L * grid));
+            auto go = [&](auto kernel) {
+                return launch(kernel, dim3(grid), dim3(256), lds_d, st, dpre, (const float*)ED, Sp, q.M, R, B, q.Ho, q.Lh, q.NBpad,
+                              iters, smax);
+            };
+            switch (r_dy - DFT_R_DY_MF) {                // (DftRouteId)
+                case 1: rc = go(dft_dy_mf_kernel<9, 2, 46, true>); break;
+                case 2: rc = go(dft_dy_mf_kernel<9, 2, 0, true>); break;
+                case 3: rc = go(dft_dy_mf_kernel<17, 4, 98, true>); break;
+                case 4: rc = go(dft_dy_mf_kernel<17, 4, 0, true>); break;
+                case 5: rc = go(dft_dy_mf_kernel<32, 4, 0, false>); break;
+                default: return (int)hipErrorInvalidValue;
+            }
         }
-#undef TVAE_DY_MF
-        TVAE_CHECK_LAUNCH();
-        }
+        if (rc) return rc;
     }
     if (dbias) {
         float* dbpart = ED + ((q.ed_floats + 3) & ~3L);           // M floats behind the transform tables (then the h3 cell tables)
@@ -680,24 +639,14 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
     }
     // both contractions on the fp32 matrix pipe where the tiles are not mostly padding (ksz <= 64, >= 17 frequencies per block)
     constexpr bool dbank_mf = true;
-    if (q.mixed) {       // the tap rows are spatial already: x stage only
-        hipError_t e = allow_big_lds(dft_dbank_x_kernel, q.lds_db);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(dft_dbank_x_kernel, dim3(q.M * Cin), dim3(256), q.lds_db, st, (const float*)slabs, nslabs, q.g_floats,
-                           dbank, ksz, q.L, q.Lh, q.M, Cin);
-    } else if (dbank_mf && ksz <= 64 && q.FXBd >= 17 && q.FXBd <= 64) {
-        hipError_t e = allow_big_lds(dft_dbank_mf_kernel, q.lds_db);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(dft_dbank_mf_kernel, dim3(q.M * Cin), dim3(256), q.lds_db, st, (const float*)slabs, nslabs,
-                           q.g_floats, dbank, ksz, q.L, q.Lh, q.M, Cin, q.FXBd);
-    } else {
-        hipError_t e = allow_big_lds(dft_dbank_kernel, q.lds_db);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(dft_dbank_kernel, dim3(q.M * Cin), dim3(256), q.lds_db, st, (const float*)slabs, nslabs, q.g_floats,
-                           dbank, ksz, q.L, q.Lh, q.M, Cin, q.FXBd);
-    }
-    TVAE_CHECK_LAUNCH();
-    return 0;
+    if (q.mixed)         // the tap rows are spatial already: x stage only
+        return launch(dft_dbank_x_kernel, dim3(q.M * Cin), dim3(256), q.lds_db, st, (const float*)slabs, nslabs, q.g_floats, dbank,
+                      ksz, q.L, q.Lh, q.M, Cin);
+    if (dbank_mf && ksz <= 64 && q.FXBd >= 17 && q.FXBd <= 64)
+        return launch(dft_dbank_mf_kernel, dim3(q.M * Cin), dim3(256), q.lds_db, st, (const float*)slabs, nslabs, q.g_floats, dbank,
+                      ksz, q.L, q.Lh, q.M, Cin, q.FXBd);
+    return launch(dft_dbank_kernel, dim3(q.M * Cin), dim3(256), q.lds_db, st, (const float*)slabs, nslabs, q.g_floats, dbank, ksz,
+                  q.L, q.Lh, q.M, Cin, q.FXBd);
 }
 
 }  // extern "C"

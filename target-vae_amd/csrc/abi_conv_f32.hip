@@ -32,27 +32,17 @@ int tvae_conv1_fwd(const float* y, const float* bank, const float* bias, float* 
         if (nblk > 2147483647L) return (int)hipErrorInvalidValue;
         const bool vec = (K % BK == 0) && (M % BM == 0);
         const size_t lds2 = conv_img_lds_bytes(Cin, rows, n, pad, 2);
-        hipError_t e;
         if (vec && M % (2 * BM) == 0 && lds2 <= CONV_IMG_LDS_MAX) {
             // 256 x 128 tile: each wave 128 x 64 (8 MFMAs per operand wait)
             const long nblk2 = (long)(M / (2 * BM)) * B * tilesPerImg;
-            e = allow_big_lds(conv1_fwd_img_kernel<true, 2>, lds2);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((conv1_fwd_img_kernel<true, 2>), dim3((unsigned)nblk2), dim3(GEMM_THREADS), lds2,
-                               S(stream), bank, y, g, ep, M, K, tilesPerImg, rows);
-        } else if (vec) {
-            e = allow_big_lds(conv1_fwd_img_kernel<true, 1>, lds);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((conv1_fwd_img_kernel<true, 1>), dim3((unsigned)nblk), dim3(GEMM_THREADS), lds, S(stream),
-                               bank, y, g, ep, M, K, tilesPerImg, rows);
-        } else {
-            e = allow_big_lds(conv1_fwd_img_kernel<false, 1>, lds);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((conv1_fwd_img_kernel<false, 1>), dim3((unsigned)nblk), dim3(GEMM_THREADS), lds, S(stream),
-                               bank, y, g, ep, M, K, tilesPerImg, rows);
+            return launch(conv1_fwd_img_kernel<true, 2>, dim3((unsigned)nblk2), dim3(GEMM_THREADS), lds2, S(stream), bank, y, g,
+                          ep, M, K, tilesPerImg, rows);
         }
-        TVAE_CHECK_LAUNCH();
-        return 0;
+        if (vec)
+            return launch(conv1_fwd_img_kernel<true, 1>, dim3((unsigned)nblk), dim3(GEMM_THREADS), lds, S(stream), bank, y, g, ep,
+                          M, K, tilesPerImg, rows);
+        return launch(conv1_fwd_img_kernel<false, 1>, dim3((unsigned)nblk), dim3(GEMM_THREADS), lds, S(stream), bank, y, g, ep, M,
+                      K, tilesPerImg, rows);
     }
     // generic path (padded image does not fit in LDS): implicit im2col staged through LDS
     LoadKContig al{bank, (long)K, M};
@@ -93,32 +83,24 @@ int tvae_conv1_wgrad(const float* y, const float* dpre, float* dbank, float* ws,
         const int rows2 = conv_wgrad_img_rows(Cin, n, ksz, pad, 2);
         const size_t ldsn = conv_img_lds_bytes(Cin, rows2, n, pad, 1, 32);
         const size_t lds32 = conv_img_lds_bytes(Cin, rows, n, pad, 1, 32);
-        hipError_t e;
+        int rc;
         if (N % (2 * BN) == 0 && ldsn * 2 <= 160 * 1024) {
             const int tilesN2 = N / (2 * BN);
             sp = slices(tilesM * tilesN2, 2, ips);
-            e = allow_big_lds(conv1_wgrad_img_kernel<1, 32, 2>, ldsn);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((conv1_wgrad_img_kernel<1, 32, 2>), dim3((unsigned)(tilesM * tilesN2 * sp)),
-                               dim3(GEMM_THREADS), ldsn, S(stream), dpre, (long)B * R * g.P, y, g, ep, M, N, ips,
-                               sp > 1 ? ws : nullptr, tilesN2, rows2, sp, tilesM * sp);
+            rc = launch(conv1_wgrad_img_kernel<1, 32, 2>, dim3((unsigned)(tilesM * tilesN2 * sp)), dim3(GEMM_THREADS), ldsn,
+                        S(stream), dpre, (long)B * R * g.P, y, g, ep, M, N, ips, sp > 1 ? ws : nullptr, tilesN2, rows2, sp,
+                        tilesM * sp);
         } else if (lds32 * 3 <= 160 * 1024) {
             // 128 x 128 tile, 32 positions per k-step: half the barriers, still 3 workgroups per CU
             sp = slices(tiles, 3, ips);
-            e = allow_big_lds(conv1_wgrad_img_kernel<1, 32, 1>, lds32);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((conv1_wgrad_img_kernel<1, 32, 1>), dim3((unsigned)(tiles * sp)), dim3(GEMM_THREADS),
-                               lds32, S(stream), dpre, (long)B * R * g.P, y, g, ep, M, N, ips, sp > 1 ? ws : nullptr,
-                               tilesN, rows, sp, tilesM * sp);
+            rc = launch(conv1_wgrad_img_kernel<1, 32, 1>, dim3((unsigned)(tiles * sp)), dim3(GEMM_THREADS), lds32, S(stream), dpre,
+                        (long)B * R * g.P, y, g, ep, M, N, ips, sp > 1 ? ws : nullptr, tilesN, rows, sp, tilesM * sp);
         } else {
             sp = slices(tiles, 3, ips);
-            e = allow_big_lds(conv1_wgrad_img_kernel<1, 16, 1>, lds);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL((conv1_wgrad_img_kernel<1, 16, 1>), dim3((unsigned)(tiles * sp)), dim3(GEMM_THREADS),
-                               lds, S(stream), dpre, (long)B * R * g.P, y, g, ep, M, N, ips, sp > 1 ? ws : nullptr,
-                               tilesN, rows, sp, tilesM * sp);
+            rc = launch(conv1_wgrad_img_kernel<1, 16, 1>, dim3((unsigned)(tiles * sp)), dim3(GEMM_THREADS), lds, S(stream), dpre,
+                        (long)B * R * g.P, y, g, ep, M, N, ips, sp > 1 ? ws : nullptr, tilesN, rows, sp, tilesM * sp);
         }
-        TVAE_CHECK_LAUNCH();
+        if (rc) return rc;
         return sp > 1 ? splitk_finalize(ws, sp, M, N, ep, S(stream)) : 0;
     }
     LoadConvDY al{dpre, (long)B * R * g.P, M, R, g.P};

@@ -79,12 +79,8 @@ int tvae_conv1_fwd_x6(const float* y, const void* a3, const float* bias, float* 
     const int tilesPerImg = cdiv(g.P, BN);
     const long nblk = (long)(q.Mpad / 256) * B * tilesPerImg;
     if (nblk > 2147483647L) return (int)hipErrorInvalidValue;
-    hipError_t e = allow_big_lds(conv1_fwd_x6_kernel, q.lds_f);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(conv1_fwd_x6_kernel, dim3((unsigned)nblk), dim3(GEMM_THREADS), q.lds_f, S(stream),
-                       (const uint4*)a3, y, g, ep, q.M, q.Mpad, q.K8pad, q.opr, tilesPerImg, q.rows_f, q.Wp, q.arr_f);
-    TVAE_CHECK_LAUNCH();
-    return 0;
+    return launch(conv1_fwd_x6_kernel, dim3((unsigned)nblk), dim3(GEMM_THREADS), q.lds_f, S(stream), (const uint4*)a3, y, g, ep,
+                  q.M, q.Mpad, q.K8pad, q.opr, tilesPerImg, q.rows_f, q.Wp, q.arr_f);
 }
 
 int tvae_dy_split3(const float* dpre, void* d3, long d3_bytes, int B, int Cin, int n, int ksz, int pad, int C, int R,
@@ -95,12 +91,8 @@ int tvae_dy_split3(const float* dpre, void* d3, long d3_bytes, int B, int Cin, i
     if (d3_bytes < q.dy_cells * 16 || !aligned16(d3)) return (int)hipErrorInvalidValue;
     const size_t tile_bytes = (size_t)R * g.P * sizeof(float);
     if (tile_bytes > 150 * 1024) return (int)hipErrorInvalidValue;
-    hipError_t e0 = allow_big_lds(dy_split3_kernel, tile_bytes);
-    if (e0 != hipSuccess) return (int)e0;
-    hipLaunchKernelGGL(dy_split3_kernel, dim3(B, q.Mpad / R), dim3(256), tile_bytes, S(stream), dpre, (long)B * R * g.P,
-                       (uint4*)d3, B, C, R, g.Ho, q.kk.opwf, q.kk.opc, q.kk.row_cells, q.kk.cells, q.kk.QP, q.Mpad);
-    TVAE_CHECK_LAUNCH();
-    return 0;
+    return launch(dy_split3_kernel, dim3(B, q.Mpad / R), dim3(256), tile_bytes, S(stream), dpre, (long)B * R * g.P, (uint4*)d3, B,
+                  C, R, g.Ho, q.kk.opwf, q.kk.opc, q.kk.row_cells, q.kk.cells, q.kk.QP, q.Mpad);
 }
 
 int tvae_conv1_wgrad_x6(const float* y, const void* d3, float* dbank, float* ws, long ws_floats, int B, int Cin, int n,
@@ -121,12 +113,10 @@ int tvae_conv1_wgrad_x6(const float* y, const void* d3, float* dbank, float* ws,
     if (sp < 1) sp = 1;
     const int ips = cdiv(B, sp);
     sp = cdiv(B, ips);
-    hipError_t e = allow_big_lds(conv1_wgrad_x6_kernel, q.lds_w);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(conv1_wgrad_x6_kernel, dim3((unsigned)(otiles * sp)), dim3(GEMM_THREADS), q.lds_w, S(stream),
-                       (const uint4*)d3, y, g, M, q.Mpad, N, q.kk, ips, ws, tilesN, q.rows_w, q.Wp, q.arr_w, q.PT,
-                       q.arr_t, sp, tilesM * sp);
-    TVAE_CHECK_LAUNCH();
+    const int rc = launch(conv1_wgrad_x6_kernel, dim3((unsigned)(otiles * sp)), dim3(GEMM_THREADS), q.lds_w, S(stream),
+                          (const uint4*)d3, y, g, M, q.Mpad, N, q.kk, ips, ws, tilesN, q.rows_w, q.Wp, q.arr_w, q.PT, q.arr_t, sp,
+                          tilesM * sp);
+    if (rc) return rc;
     Epilogue ep;
     ep.C = dbank; ep.ldc = N;
     return splitk_finalize(ws, sp, M, N, ep, S(stream));

@@ -34,26 +34,29 @@ static __global__ void dense_absmax_kernel(const float* __restrict__ W, long ldw
     h3_block_amax(mx, amax);
 }
 
+// the launcher of a number of parts (1, 2 or 3; anything else: nullptr).  Here and not in the header: where the definition of
+// dense_wgrad_x6_launch is visible (dense_wgrad_x6_instance.hip), naming all three would instantiate all three.
+static auto dense_wgrad_x6_launcher(int parts) -> int (*)(TVAE_WG_LAUNCH_ARGS) {
+    return parts == 1 ? dense_wgrad_x6_launch<1> : parts == 2 ? dense_wgrad_x6_launch<2> : parts == 3 ? dense_wgrad_x6_launch<3> : nullptr;
+}
+
 int dense_wgrad_x6_batched(const float* dY, long ldd, const float* X, long ldx, float* slabs, int M, int Kf, int N,
                            int nchunk, const TileMap& tm, const DenseBatch& bt, long dy_stride, const ATile& atile,
                            int parts, hipStream_t st, H3Scale hs, bool a_bf16, bool wide) {
-    const VirtGrad vg{nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0};
-    const VirtAct va{nullptr, nullptr, nullptr, nullptr, 1, 0, 0.f};
     if (a_bf16) {        // dY holds 2-byte bf16 elements (ldd, dy_stride, atile in elements): one-part mode only
         if (parts != 1 || dy_stride % 2 != 0) return (int)hipErrorInvalidValue;
-        return dense_wgrad_x6_launch_p1_abf(0, dY, ldd, X, ldx, slabs, M, Kf, N, nchunk, tm, bt, dy_stride, vg, va, atile, st, hs);
+        return dense_wgrad_x6_launch_abf(WG_PLAIN, dY, ldd, X, ldx, slabs, M, Kf, N, nchunk, tm, bt, dy_stride, VIRTGRAD_NONE,
+                                         VIRTACT_NONE, atile, st, hs);
     }
+    if (parts == 2 && !(hs.amax_a && hs.amax_x)) return (int)hipErrorInvalidValue;
     if (wide) {          // exact-fit tile (tm / bt in 256-row tiles, one column tile); two- and three-part arithmetic
-        if (parts == 2 && hs.amax_a && hs.amax_x)
-            return dense_wgrad_x6_wide_p2(dY, ldd, X, ldx, slabs, M, Kf, N, nchunk, tm, bt, dy_stride, atile, st, hs);
-        if (parts == 3) return dense_wgrad_x6_wide_p3(dY, ldd, X, ldx, slabs, M, Kf, N, nchunk, tm, bt, dy_stride, atile, st, hs);
+        if (parts == 2) return dense_wgrad_x6_wide<2>(dY, ldd, X, ldx, slabs, M, Kf, N, nchunk, tm, bt, dy_stride, atile, st, hs);
+        if (parts == 3) return dense_wgrad_x6_wide<3>(dY, ldd, X, ldx, slabs, M, Kf, N, nchunk, tm, bt, dy_stride, atile, st, hs);
         return (int)hipErrorInvalidValue;
     }
-    if (parts == 1) return dense_wgrad_x6_launch_p1(0, dY, ldd, X, ldx, slabs, M, Kf, N, nchunk, tm, bt, dy_stride, vg, va, atile, st, hs);
-    if (parts == 2 && hs.amax_a && hs.amax_x)
-        return dense_wgrad_x6_launch_p2(0, dY, ldd, X, ldx, slabs, M, Kf, N, nchunk, tm, bt, dy_stride, vg, va, atile, st, hs);
-    if (parts == 3) return dense_wgrad_x6_launch_p3(0, dY, ldd, X, ldx, slabs, M, Kf, N, nchunk, tm, bt, dy_stride, vg, va, atile, st, hs);
-    return (int)hipErrorInvalidValue;
+    const auto wg = dense_wgrad_x6_launcher(parts);
+    if (!wg) return (int)hipErrorInvalidValue;
+    return wg(WG_PLAIN, dY, ldd, X, ldx, slabs, M, Kf, N, nchunk, tm, bt, dy_stride, VIRTGRAD_NONE, VIRTACT_NONE, atile, st, hs);
 }
 }  // namespace tvae
 
@@ -135,16 +138,14 @@ int tvae_linear_wgrad_x6(const float* dpre, const float* X, float* dW, float* ws
     const TileMap tmk{tilesM, tilesK, splits};
     // the implicit LeakyReLU gradient runs in its two-valued form (0 / 1 streamed operand, see the kernel)
     const bool lrf = vg_wo && vg_act == ACT_LRELU;
-    const int variant = (vg_wo ? 1 : 0) | (va_xr ? 2 : 0) | (lrf ? (from_bits ? 8 : 4) : 0);
-    int rc;
+    const WgVariant variant{vg_wo != nullptr, va_xr != nullptr, !lrf ? WG_LRF_OFF : (from_bits ? WG_LRF_BITS : WG_LRF_H)};
+    H3Scale hs = H3_NONE;
     if (parts == 2 && !h3_recomp) {
-        rc = dense_wgrad_x6_launch_p2(variant, dpre, ldd, X, ldx, ws, M, K, N, nchunk, tmk, DenseBatch{0, 0, 0}, 0L, vgs, vas,
-                                      ATILE_PLAIN, S(stream),
-                                      // x_amax_rows: one bound per ROW of X (= per column of dW) instead of one for the tensor
-                                      H3Scale{a_amax, x_amax, 0, 0, 0, x_amax_rows ? 1 : 0, x_amax_rows ? K : 0});
+        // x_amax_rows: one bound per ROW of X (= per column of dW) instead of one for the tensor
+        hs = H3Scale{a_amax, x_amax, 0, 0, 0, x_amax_rows ? 1 : 0, x_amax_rows ? K : 0};
     } else if (parts == 2) {
         float* slots = ws + (long)splits * per;
-        rc = h3_zero_slots(slots, 4 + K, 256, S(stream));
+        int rc = h3_zero_slots(slots, 4 + K, 256, S(stream));
         if (rc) return rc;
         const long nlb = va_lb ? (long)(N / vas.Np) * K : 0;
         rc = dec_l0_bound(va_xr, N, va_wc, va_bc, va_lb, nlb, K, slots, S(stream));
@@ -152,15 +153,11 @@ int tvae_linear_wgrad_x6(const float* dpre, const float* X, float* dW, float* ws
         hipLaunchKernelGGL(dense_absmax_kernel, dim3(grid1d((long)N, 256 * 8, 512)), dim3(256), 0, S(stream), vg_gy, (long)N, 1, N,
                            0, (const float*)nullptr, slots + 3);
         TVAE_CHECK_LAUNCH();
-        rc = dense_wgrad_x6_launch_p2(variant, dpre, ldd, X, ldx, ws, M, K, N, nchunk, tmk, DenseBatch{0, 0, 0}, 0L, vgs, vas,
-                                      ATILE_PLAIN, S(stream), H3Scale{nullptr, slots, 0, 0, 0, 0, 0});
-    } else {
-        rc = parts == 1
-            ? dense_wgrad_x6_launch_p1(variant, dpre, ldd, X, ldx, ws, M, K, N, nchunk, tmk, DenseBatch{0, 0, 0}, 0L, vgs, vas, ATILE_PLAIN, S(stream), H3_NONE)
-            : dense_wgrad_x6_launch_p3(variant, dpre, ldd, X, ldx, ws, M, K, N, nchunk, tmk, DenseBatch{0, 0, 0}, 0L, vgs, vas, ATILE_PLAIN, S(stream), H3_NONE);
+        hs = H3Scale{nullptr, slots, 0, 0, 0, 0, 0};
     }
+    int rc = dense_wgrad_x6_launcher(parts)(variant, dpre, ldd, X, ldx, ws, M, K, N, nchunk, tmk, DenseBatch{0, 0, 0}, 0L, vgs, vas,
+                                            ATILE_PLAIN, S(stream), hs);
     if (rc) return rc;
-    TVAE_CHECK_LAUNCH();
     Epilogue ep;
     ep.C = dW; ep.ldc = K;
     ep.accumulate = accumulate;

@@ -53,37 +53,27 @@ int dense_x6_batched(const void* w3, const float* X, long ldx, const Epilogue& e
     if (N % 128 != 0 || !aligned16(w3)) return (int)hipErrorInvalidValue;
     if (parts != 1 && parts != 2 && parts != 3) return (int)hipErrorInvalidValue;
     if (parts == 2 && (!hs.amax_a || !hs.amax_x)) return (int)hipErrorInvalidValue;
-    // the spectral contraction's own shape (plain column-tiled output, whole row tiles): lean store epilogue (round 6: the
-    // generic one took ~40 % of these launches)
-    const bool lean = !ep.bias && !ep.res && !ep.aux && ep.act == ACT_NONE && ep.mask == ACT_NONE && ep.ctile > 0 && ep.C &&
-                      !ep.accumulate && !ep.amax_out && rows_per_problem % DX6_ROWS == 0 && ep.ldc * 8 * 4 < (1L << 31);
+    const bool lean = dense_x6_lean_store(ep, rows_per_problem, DX6_ROWS, true);      // (EPI 4 does not flush ep.amax_out)
     return dense_x6_dispatch(0, lean ? 4 : 0, parts, (const uint4*)w3, X, ldx, ep, rows_per_problem, Rpad, N, K, K8pad, tm, bt,
-                             ColDot{nullptr, nullptr, nullptr},
-                             InTail{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1},
-                             VirtGrad{nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0},
-                             VirtAct{nullptr, nullptr, nullptr, nullptr, 1, 0, 0.f}, st, hs);
+                             COLDOT_NONE, INTAIL_NONE, VIRTGRAD_NONE, VIRTACT_NONE, st, hs);
 }
 int dense_x6_batched4(const void* w3, const float* X, long ldx, const Epilogue& ep, int rows_per_problem, int rows_total,
                       int N, int K, const TileMap& tm, const DenseBatch& bt, int parts, hipStream_t st, H3Scale hs, bool out_bf16) {
     const int Rpad = x6_round_up(rows_total, DX6_ROWS), K8pad = dense_k8pad(K);     // the cells keep their 512-row padding
     if (N % 128 != 0 || !aligned16(w3) || (parts != 1 && parts != 2 && parts != 3)) return (int)hipErrorInvalidValue;
     if (parts == 2 && (!hs.amax_a || !hs.amax_x)) return (int)hipErrorInvalidValue;
-    // the spectral contraction's own shape (plain column-tiled output, whole row tiles) has a lean store epilogue
-    const bool lean = !ep.bias && !ep.res && !ep.aux && ep.act == ACT_NONE && ep.mask == ACT_NONE && ep.ctile > 0 && ep.C &&
-                      !ep.accumulate && rows_per_problem % DX4_ROWS == 0 && ep.ldc * 8 * 4 < (1L << 31);
-#define TVAE_DX4_LAUNCH(NP_, E_)                                                                                       \
-    hipLaunchKernelGGL((dense_x6_plain4_kernel<NP_, E_>), dim3(tm.grid()), dim3(DX4_THREADS), 0, st, (const uint4*)w3, X, ldx, \
-                       ep, rows_per_problem, Rpad, N, K, K8pad, tm, bt, hs)
+    const bool lean = dense_x6_lean_store(ep, rows_per_problem, DX4_ROWS, false);
+    auto go = [&](auto kernel) {
+        return launch(kernel, dim3(tm.grid()), dim3(DX4_THREADS), 0, st, (const uint4*)w3, X, ldx, ep, rows_per_problem, Rpad, N, K,
+                      K8pad, tm, bt, hs);
+    };
     if (out_bf16) {      // bf16 STORAGE of the output (one-part mode only; the caller reads 2-byte elements)
         if (!lean || parts != 1) return (int)hipErrorInvalidValue;
-        TVAE_DX4_LAUNCH(1, 2);
-        return (int)hipGetLastError();
+        return go(dense_x6_plain4_kernel<1, 2>);
     }
-    if (parts == 3) { if (lean) TVAE_DX4_LAUNCH(3, 1); else TVAE_DX4_LAUNCH(3, 0); }
-    else if (parts == 2) { if (lean) TVAE_DX4_LAUNCH(2, 1); else TVAE_DX4_LAUNCH(2, 0); }
-    else { if (lean) TVAE_DX4_LAUNCH(1, 1); else TVAE_DX4_LAUNCH(1, 0); }
-#undef TVAE_DX4_LAUNCH
-    return (int)hipGetLastError();
+    return by_parts(parts, [&](auto np) {
+        return lean ? go(dense_x6_plain4_kernel<np.value, 1>) : go(dense_x6_plain4_kernel<np.value, 0>);
+    });
 }
 // The same contraction with the streamed panel resident in LDS (dense_x6_xres_kernel): false when the shape is not its own
 // (the caller then takes dense_x6_batched4).  ep as for the lean store epilogue; Mb = rows per problem in the cell array.
@@ -92,8 +82,7 @@ bool dense_x6_batched_xres(const void* w3, const float* X, long ldx, const Epilo
     constexpr bool on = true;
     const int K8pad = dense_k8pad(K), nk = K8pad / 2;
     const size_t lds = (size_t)nk * parts * 256 * 16 + (size_t)(Mb + 128) * 4;
-    const bool lean = !ep.bias && !ep.res && !ep.aux && ep.act == ACT_NONE && ep.mask == ACT_NONE && ep.ctile > 0 && ep.C &&
-                      !ep.accumulate && rows_per_problem % DX6_ROWS == 0 && ep.ldc * 8 * 4 < (1L << 31);
+    const bool lean = dense_x6_lean_store(ep, rows_per_problem, DX6_ROWS, false);
     // twelve k-steps only (the 96-wide frame of the 64 x 64 configuration): at six steps (28 x 28: 44-wide frame) the stores per
     // step double and the kernel measured 213 us against dense_x6_plain4_kernel's 195; nine steps (50 x 50) were not measured.
     // Two parts (h3): 1.21 against 1.38 ms; three (x6): 1.76 against 1.80.
@@ -104,18 +93,13 @@ bool dense_x6_batched_xres(const void* w3, const float* X, long ldx, const Epilo
         return false;
     const int Rpad = x6_round_up(nprob * Mb, DX6_ROWS), tilesN = N / 128, nch = 4, cs = cdiv(tilesN, nch);
     const unsigned grid = 8u * cdiv(nprob * nch, 8) * cs;
-#define TVAE_XRES_LAUNCH(NP_, NK_)                                                                                     \
-    do {                                                                                                               \
-        hipError_t e_ = allow_big_lds(dense_x6_xres_kernel<NP_, NK_>, lds);                                            \
-        if (e_ != hipSuccess) { *rc = (int)e_; return true; }                                                          \
-        hipLaunchKernelGGL((dense_x6_xres_kernel<NP_, NK_>), dim3(grid), dim3(256), lds, st, (const uint4*)w3, X, ldx, ep.C,  \
-                           ep.ldc, ep.ctile, rows_per_problem, Mb, Rpad, K, nprob, tilesN, nch, x_stride, c_stride, hs);  \
-    } while (0)
-    if (nk == 12) { if (parts == 3) TVAE_XRES_LAUNCH(3, 12); else TVAE_XRES_LAUNCH(2, 12); }
-    else if (nk == 10) { if (parts == 3) TVAE_XRES_LAUNCH(3, 10); else TVAE_XRES_LAUNCH(2, 10); }
-    else { if (parts == 3) TVAE_XRES_LAUNCH(3, 8); else TVAE_XRES_LAUNCH(2, 8); }
-#undef TVAE_XRES_LAUNCH
-    *rc = (int)hipGetLastError();
+    auto go = [&](auto kernel) {
+        return launch(kernel, dim3(grid), dim3(256), lds, st, (const uint4*)w3, X, ldx, ep.C, ep.ldc, ep.ctile, rows_per_problem, Mb,
+                      Rpad, K, nprob, tilesN, nch, x_stride, c_stride, hs);
+    };
+    if (nk == 12) *rc = parts == 3 ? go(dense_x6_xres_kernel<3, 12>) : go(dense_x6_xres_kernel<2, 12>);
+    else if (nk == 10) *rc = parts == 3 ? go(dense_x6_xres_kernel<3, 10>) : go(dense_x6_xres_kernel<2, 10>);
+    else *rc = parts == 3 ? go(dense_x6_xres_kernel<3, 8>) : go(dense_x6_xres_kernel<2, 8>);
     return true;
 }
 }  // namespace tvae
@@ -192,25 +176,23 @@ int tvae_dense_split2h(const float* W, long ldw, void* a3, long a3_bytes, int ro
                        const float* scale, float* rowsum, tvae_stream_t stream) {
     return dense_split(W, ldw, a3, a3_bytes, rows, K, transpose, scale, rowsum, 2, stream);
 }
+// One forward / data-gradient launch: the route (abi_dense_x6.hpp: dense_x6_route) says which instance runs and where the h3 bound
+// of the streamed operand comes from; every refusal has happened before the first launch.
 static int launch_dense_x6(const void* a3, const float* X, long ldx, const Epilogue& ep, int rows, int N, int K, int parts,
-                           hipStream_t st, ColDot cd = ColDot{nullptr, nullptr, nullptr},
-                           InTail it = InTail{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1},
-                           VirtGrad vg = VirtGrad{nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0},
-                           VirtAct va = VirtAct{nullptr, nullptr, nullptr, nullptr, 1, 0, 0.f}, const float* x_amax = nullptr) {
-    if ((cd.w || it.xr) && rows > DX6_ROWS) return (int)hipErrorInvalidValue;   // the fused tails need ONE row tile
-    if (rows <= 0 || N <= 0) return 0;
-    if (N % 128 != 0 || !aligned16(a3) || (parts != 1 && parts != 2 && parts != 3)) return (int)hipErrorInvalidValue;
+                           hipStream_t st, const ColDot& cd, const InTail& it, const VirtGrad& vg, const VirtAct& va,
+                           const float* x_amax) {
+    const DenseRoute r = dense_x6_route(a3, X, ep, rows, N, K, parts, cd, it, vg, va, x_amax != nullptr);
+    if (r.xv == DENSE_EMPTY) return 0;
+    if (r.xv < 0) return (int)hipErrorInvalidValue;
     const int Rpad = x6_round_up(rows, DX6_ROWS), K8pad = dense_k8pad(K);
     TileMap tm{Rpad / DX6_ROWS, N / 128, 1};
     tm.pack = 1;                                         // eight adjacent column tiles per XCD (TileMap: the sign-bit lines)
     H3Scale hs = H3_NONE;
     if (parts == 2) {
-        // h3 instances: the recomputed first-layer activation (its bound is formed here) and the exact 0 / 1 operand of the
-        // two-valued gradient; an operand streamed from memory would need its maximum from its producer (not wired: x6)
         float* tr = h3_trailer(a3, rows, K);             // one maximum per row (tvae_dense_split2h)
         hs.amax_a = tr;
         hs.a_rows = 1;
-        if (va.xr) {
+        if (r.xbound == H3X_RECOMPUTED) {
             float* bw = tr + Rpad;                       // bound words of the recomputed operand: [4 + K]
             int rc = h3_zero_slots(bw, 4 + K, 256, st);
             if (rc) return rc;
@@ -218,54 +200,12 @@ static int launch_dense_x6(const void* a3, const float* X, long ldx, const Epilo
             rc = dec_l0_bound(va.xr, N, va.wc, va.bc, va.lb, nlb, K, bw, st);
             if (rc) return rc;
             hs.amax_x = bw;
-        } else if (x_amax && !vg.wo && !vg.csum) {
-            // an operand streamed from memory: the caller supplies max |X| or an upper bound of it (one device word) -- e.g.
-            // |cos| <= 1 for Fourier features, the first-layer bound for a stored coordinate layer, a row-sum bound for the
-            // output of a layer (tvae/ops.py: _h3_bounds)
+        } else if (r.xbound == H3X_CALLER) {
             hs.amax_x = x_amax;
-        } else if (!vg.csum) {
-            return (int)hipErrorInvalidValue;
         }
     }
-    // the recomputed operands need tiles inside one image and tables of <= 512 entries
-    if ((va.xr && (K > 512 || va.Np % 128 != 0 || vg.wo || vg.csum)) || (vg.csum && (!vg.gy || vg.act != ACT_LRELU)) || (it.bc && it.Np % 128 != 0) ||
-        (!va.xr && !X && !(vg.bits && vg.csum && vg.rpart)))
-        return (int)hipErrorInvalidValue;
-    const DenseBatch nb{0, 0, 0};
-    if (vg.csum && vg.rpart && vg.bits) {                                // operand and row sums from the stored sign bits
-        if (K > DX6_ROWS || N % 32 != 0) return (int)hipErrorInvalidValue;
-        // the hot shape has its own lean instance: ONE full row tile, result not stored, fused first-layer backward with the
-        // recomputed LeakyReLU mask, nothing else switched on
-        if (rows == DX6_ROWS && !ep.C && it.xr && it.bc && !ep.res && ep.mask == ACT_LRELU && !cd.w && !cd.bits)
-            return dense_x6_dispatch(5, 2, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-        // ... its result stored under the LeakyReLU mask of a saved activation (Fourier decoders), whole row tiles: lean store
-        if (rows % DX6_ROWS == 0 && ep.C && !it.xr && !ep.res && ep.mask == ACT_LRELU && ep.aux && !cd.w && !cd.bits && !ep.ctile &&
-            ep.ldc * 8 * 4 < (1L << 31) && ep.ldaux * 8 * 4 < (1L << 31))
-            return dense_x6_dispatch(5, 3, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-        return dense_x6_dispatch(5, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    }
-    if (vg.csum && vg.rpart) {
-        if (K > DX6_ROWS) return (int)hipErrorInvalidValue;              // the row sums live in one 512-row LDS table
-        return dense_x6_dispatch(4, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    }
-    if (vg.csum) return dense_x6_dispatch(3, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    // forward of the decoder's last hidden layer with its activation not stored: lean instance (one full row tile)
-    // (cd.bits == nullptr with no output either: the inference-mode forward -- only the fused column dot leaves the launch)
-    if (va.xr && rows == DX6_ROWS && !ep.C && cd.w && !it.xr && !ep.res && ep.mask == ACT_NONE && ep.act == ACT_LRELU)
-        return dense_x6_dispatch(2, 1, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    if (va.xr) return dense_x6_dispatch(2, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    // the same layer with its input read from memory (28 x 28 shapes, Fourier decoders): lean instance of the plain operand
-    if (!vg.wo && X && rows == DX6_ROWS && N % 128 == 0 && !ep.C && cd.w && !it.xr && !ep.res && ep.mask == ACT_NONE &&
-        ep.act == ACT_LRELU)
-        return dense_x6_dispatch(0, 1, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    if (vg.wo) return dense_x6_dispatch(1, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    // plain hidden layer that stores its output (round 6): whole 512-row tiles, bias + LeakyReLU | none (forward) or the
-    // LeakyReLU mask of the saved activation (data gradient), nothing fused behind it: lean store epilogue
-    if (X && rows % DX6_ROWS == 0 && ep.C && !ep.res && !cd.w && !cd.bits && !it.xr && !ep.ctile && !ep.accumulate && !ep.gbias &&
-        ((ep.mask == ACT_NONE && (ep.act == ACT_LRELU || ep.act == ACT_NONE)) || (ep.mask == ACT_LRELU && ep.aux && ep.act == ACT_NONE && !ep.bias)) &&
-        ep.ldc * 8 * 4 < (1L << 31) && ep.ldaux * 8 * 4 < (1L << 31))
-        return dense_x6_dispatch(0, 3, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
-    return dense_x6_dispatch(0, 0, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, nb, cd, it, vg, va, st, hs);
+    return dense_x6_dispatch(r.xv, r.epi, parts, (const uint4*)a3, X, ldx, ep, rows, Rpad, N, K, K8pad, tm, DenseBatch{0, 0, 0}, cd,
+                             it, vg, va, st, hs);
 }
 int tvae_linear_fwd_x6(const void* w3, const float* X, const float* bias, const float* res, float* Y, int M, int N,
                        int K, long ldx, long ldy, int act, float slope, const float* col_w, const float* col_b,
@@ -281,9 +221,8 @@ int tvae_linear_fwd_x6(const void* w3, const float* X, const float* bias, const 
     ep.bias = bias;
     ep.res = res; ep.ldres = ldy;
     ep.act = act; ep.slope = slope;
-    return launch_dense_x6(w3, X, ldx, ep, M, N, K, parts, S(stream), ColDot{col_w, col_b, col_y, (unsigned*)sign_bits},
-                           InTail{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1}, VirtGrad{nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0},
-                           VirtAct{va_xr, va_wc, va_bc, va_lb, va_np > 0 ? va_np : 1, act, slope}, x_amax);
+    return launch_dense_x6(w3, X, ldx, ep, M, N, K, parts, S(stream), ColDot{col_w, col_b, col_y, (unsigned*)sign_bits}, INTAIL_NONE,
+                           VIRTGRAD_NONE, VirtAct{va_xr, va_wc, va_bc, va_lb, va_np > 0 ? va_np : 1, act, slope}, x_amax);
 }
 int tvae_linear_dgrad_x6(const void* w3t, const float* dpre, const float* add, const float* aux, float* dX, int M,
                          int N, int K, long ldd, long ldx, int mask, float slope, const float* in_xr,
@@ -316,10 +255,9 @@ int tvae_linear_dgrad_x6(const void* w3t, const float* dpre, const float* add, c
             rs_part_floats < (long)(N / 128) * M * 2 || (reinterpret_cast<size_t>(rs_part) & 7))
             return (int)hipErrorInvalidValue;
     }
-    int rc = launch_dense_x6(w3t, dpre, ldd, ep, K, N, M, parts, S(stream), ColDot{nullptr, nullptr, nullptr},
+    int rc = launch_dense_x6(w3t, dpre, ldd, ep, K, N, M, parts, S(stream), COLDOT_NONE,
                              InTail{in_xr, in_wc, in_gxr, in_part, in_bc, in_lb, in_np > 0 ? in_np : 1},
-                             VirtGrad{vg_wo, vg_gy, mask, slope, vg_csum, (const unsigned*)vg_bits, rs_part, 0},
-                             VirtAct{nullptr, nullptr, nullptr, nullptr, 1, 0, 0.f}, x_amax);
+                             VirtGrad{vg_wo, vg_gy, mask, slope, vg_csum, (const unsigned*)vg_bits, rs_part, 0}, VIRTACT_NONE, x_amax);
     if (rc || !rs_part || !rs_db || N <= 0 || K <= 0) return rc;
     hipLaunchKernelGGL(dgrad_rowsum_total_kernel, dim3(M), dim3(256), 0, S(stream), (const float*)rs_part, N / 128, M, rs_wo,
                        rs_gysum, slope, rs_db, rs_dwo, rs_rowdot, rs_bias);

@@ -22,12 +22,8 @@ constexpr long ET_MAX_LD = 1L << 25;   // lane offsets are 32-bit BYTE offsets o
 inline bool ld_ok(long a) { return a < ET_MAX_LD; }
 
 template <int NP, bool DG, int ACT>
-int launch(const EtWide& a, hipStream_t st) {
-    const size_t lds = (size_t)2 * NP * 16 * ET_C * 16;
-    hipError_t e = allow_big_lds(enc_tail_wide_kernel<NP, DG, ACT>, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((enc_tail_wide_kernel<NP, DG, ACT>), dim3(et_grid(a.N)), dim3(ET_THREADS), lds, st, a);
-    return (int)hipGetLastError();
+int launch_wide(const EtWide& a, hipStream_t st) {
+    return launch(enc_tail_wide_kernel<NP, DG, ACT>, dim3(et_grid(a.N)), dim3(ET_THREADS), (size_t)2 * NP * 16 * ET_C * 16, st, a);
 }
 }  // namespace
 
@@ -56,13 +52,13 @@ int tvae_enc_tail_fwd_wide(const void* w3, const void* wh3, const float* A1, lon
     a.amax_x = amax_a1; a.nx = ET_C;
     const hipStream_t st = S(stream);
     if (parts == 2) {
-        if (act == ACT_LRELU) return launch<2, false, ACT_LRELU>(a, st);
-        if (act == ACT_TANH) return launch<2, false, ACT_TANH>(a, st);
-        return launch<2, false, ACT_NONE>(a, st);
+        if (act == ACT_LRELU) return launch_wide<2, false, ACT_LRELU>(a, st);
+        if (act == ACT_TANH) return launch_wide<2, false, ACT_TANH>(a, st);
+        return launch_wide<2, false, ACT_NONE>(a, st);
     }
-    if (act == ACT_LRELU) return launch<1, false, ACT_LRELU>(a, st);
-    if (act == ACT_TANH) return launch<1, false, ACT_TANH>(a, st);
-    return launch<1, false, ACT_NONE>(a, st);
+    if (act == ACT_LRELU) return launch_wide<1, false, ACT_LRELU>(a, st);
+    if (act == ACT_TANH) return launch_wide<1, false, ACT_TANH>(a, st);
+    return launch_wide<1, false, ACT_NONE>(a, st);
 }
 
 int tvae_enc_tail_dgrad_wide(const void* wht3, const void* w3p, const float* dheads, long ldd, int nh, const void* bits_h,
@@ -84,7 +80,7 @@ int tvae_enc_tail_dgrad_wide(const void* wht3, const void* w3p, const float* dhe
     a.amax_wa = parts == 2 ? h3_trailer(wht3, ET_C, nh) : nullptr;
     a.amax_wb = parts == 2 ? h3_trailer(w3p, ET_C, ET_C) : nullptr;
     a.amax_x = amax_dheads; a.nx = 1;
-    return parts == 2 ? launch<2, true, ACT_LRELU>(a, S(stream)) : launch<1, true, ACT_LRELU>(a, S(stream));
+    return parts == 2 ? launch_wide<2, true, ACT_LRELU>(a, S(stream)) : launch_wide<1, true, ACT_LRELU>(a, S(stream));
 }
 
 }  // extern "C"

@@ -40,25 +40,10 @@ int tvae_enc_tail_fwd_x6(const void* w3, const float* A1, long lda, const float*
     const int Rpad = x6_round_up(ET_C, DX6_ROWS);
     const size_t lds = (size_t)parts * 16 * ET_C * 16;
     const H3Scale hs = parts == 2 ? H3Scale{h3_trailer(w3, ET_C, ET_C), amax_a1, 1, 0, 0, 0, 0} : H3_NONE;
-    hipError_t e;
-    if (parts == 3) {
-        e = allow_big_lds(enc_tail_fwd_x6_kernel<3>, lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((enc_tail_fwd_x6_kernel<3>), dim3(et_grid(N)), dim3(ET_THREADS), lds, S(stream), (const uint4*)w3,
-                           Rpad, A1, lda, b2, Wh, bh, nh, H, ldh, heads, ldo, N, act, slope, (uint4*)bits_h, (uint4*)bits_a, hs);
-    } else if (parts == 2) {
-        e = allow_big_lds(enc_tail_fwd_x6_kernel<2>, lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((enc_tail_fwd_x6_kernel<2>), dim3(et_grid(N)), dim3(ET_THREADS), lds, S(stream), (const uint4*)w3,
-                           Rpad, A1, lda, b2, Wh, bh, nh, H, ldh, heads, ldo, N, act, slope, (uint4*)bits_h, (uint4*)bits_a, hs);
-    } else {
-        e = allow_big_lds(enc_tail_fwd_x6_kernel<1>, lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((enc_tail_fwd_x6_kernel<1>), dim3(et_grid(N)), dim3(ET_THREADS), lds, S(stream), (const uint4*)w3,
-                           Rpad, A1, lda, b2, Wh, bh, nh, H, ldh, heads, ldo, N, act, slope, (uint4*)bits_h, (uint4*)bits_a, hs);
-    }
-    TVAE_CHECK_LAUNCH();
-    return 0;
+    return by_parts(parts, [&](auto np) {
+        return launch(enc_tail_fwd_x6_kernel<np.value>, dim3(et_grid(N)), dim3(ET_THREADS), lds, S(stream), (const uint4*)w3, Rpad,
+                      A1, lda, b2, Wh, bh, nh, H, ldh, heads, ldo, N, act, slope, (uint4*)bits_h, (uint4*)bits_a, hs);
+    });
 }
 
 int tvae_enc_tail_dgrad_x6(const void* w3p, const void* wh3, const float* dheads, long ldd, int nh, const void* bits_h,
@@ -72,28 +57,11 @@ int tvae_enc_tail_dgrad_x6(const void* w3p, const void* wh3, const float* dheads
     // parts == 2 (h3): w3p = tvae_dense_split2h cells (two fp16 parts), wh3 = tvae_dense_split3 cells (the skinny GEMM stays exact)
     const size_t lds = ((size_t)parts * 16 + (parts == 2 ? 3 : parts) * 2) * ET_C * 16;
     const float* amax_a = parts == 2 ? h3_trailer(w3p, ET_C, ET_C) : nullptr;
-    hipError_t e;
-    if (parts == 3) {
-        e = allow_big_lds(enc_tail_dgrad_x6_kernel<3>, lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((enc_tail_dgrad_x6_kernel<3>), dim3(et_grid(N)), dim3(ET_THREADS), lds, S(stream),
-                           (const uint4*)w3p, Rpad, (const uint4*)wh3, Rpad, dheads, ldd, nh, (const uint4*)bits_h,
-                           (const uint4*)bits_a, dA1, lda, N, slope, amax_a);
-    } else if (parts == 2) {
-        e = allow_big_lds(enc_tail_dgrad_x6_kernel<2>, lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((enc_tail_dgrad_x6_kernel<2>), dim3(et_grid(N)), dim3(ET_THREADS), lds, S(stream),
-                           (const uint4*)w3p, Rpad, (const uint4*)wh3, Rpad, dheads, ldd, nh, (const uint4*)bits_h,
-                           (const uint4*)bits_a, dA1, lda, N, slope, amax_a);
-    } else {
-        e = allow_big_lds(enc_tail_dgrad_x6_kernel<1>, lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((enc_tail_dgrad_x6_kernel<1>), dim3(et_grid(N)), dim3(ET_THREADS), lds, S(stream),
-                           (const uint4*)w3p, Rpad, (const uint4*)wh3, Rpad, dheads, ldd, nh, (const uint4*)bits_h,
-                           (const uint4*)bits_a, dA1, lda, N, slope, amax_a);
-    }
-    TVAE_CHECK_LAUNCH();
-    return 0;
+    return by_parts(parts, [&](auto np) {
+        return launch(enc_tail_dgrad_x6_kernel<np.value>, dim3(et_grid(N)), dim3(ET_THREADS), lds, S(stream), (const uint4*)w3p,
+                      Rpad, (const uint4*)wh3, Rpad, dheads, ldd, nh, (const uint4*)bits_h, (const uint4*)bits_a, dA1, lda, N,
+                      slope, amax_a);
+    });
 }
 
 static long ew_slab_floats(long N) {
@@ -114,30 +82,18 @@ int tvae_enc_tail_wgrad_x6(const float* A1, long lda, const float* dheads, long 
     const long nchunks = N / EW_NC;
     const int grid = (int)(nchunks < cu_count() ? nchunks : cu_count());
     float* slots = ws + ew_slab_floats(N);
-    hipError_t e;
-    if (parts == 3) {
-        e = allow_big_lds(enc_tail_wgrad_x6_kernel<3>, EW_LDS);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((enc_tail_wgrad_x6_kernel<3>), dim3(grid), dim3(ET_THREADS), EW_LDS, S(stream), A1, lda, dheads, ldd,
-                           nh, (const uint4*)bits_h, Wh, ws, N, slope, amax_a1, (const float*)slots);
-    } else if (parts == 2) {
-        // max |dheads|: one pass over nh x N floats (62 MB at the bench shape)
+    if (parts == 2) {    // max |dheads|: one pass over nh x N floats (62 MB at the bench shape)
         const int rc = h3_zero_slots(slots, 1, 64, S(stream));
         if (rc) return rc;
         hipLaunchKernelGGL(h3_absmax_rows_kernel, dim3(grid1d(N / 16 + 1, 256, 96), nh), dim3(256), 0, S(stream), dheads, ldd, N,
                            slots);
         TVAE_CHECK_LAUNCH();
-        e = allow_big_lds(enc_tail_wgrad_x6_kernel<2>, EW_LDS);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((enc_tail_wgrad_x6_kernel<2>), dim3(grid), dim3(ET_THREADS), EW_LDS, S(stream), A1, lda, dheads, ldd,
-                           nh, (const uint4*)bits_h, Wh, ws, N, slope, amax_a1, (const float*)slots);
-    } else {
-        e = allow_big_lds(enc_tail_wgrad_x6_kernel<1>, EW_LDS);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((enc_tail_wgrad_x6_kernel<1>), dim3(grid), dim3(ET_THREADS), EW_LDS, S(stream), A1, lda, dheads, ldd,
-                           nh, (const uint4*)bits_h, Wh, ws, N, slope, amax_a1, (const float*)slots);
     }
-    TVAE_CHECK_LAUNCH();
+    const int rc = by_parts(parts, [&](auto np) {
+        return launch(enc_tail_wgrad_x6_kernel<np.value>, dim3(grid), dim3(ET_THREADS), EW_LDS, S(stream), A1, lda, dheads, ldd, nh,
+                      (const uint4*)bits_h, Wh, ws, N, slope, amax_a1, (const float*)slots);
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(enc_tail_wgrad_total_kernel, dim3(ET_C * ET_C / 64), dim3(256), 0, S(stream), (const float*)ws, grid, dW2);
     TVAE_CHECK_LAUNCH();
     return 0;
@@ -154,11 +110,9 @@ int tvae_enc_tail_wgrad_wide(const float* D, long ldd, int rows_d, const float* 
         return (int)hipErrorInvalidValue;
     const long nchunks = N / EW_NC;
     const int grid = (int)(nchunks < cu_count() ? nchunks : cu_count());
-    hipError_t e = allow_big_lds(enc_tail_wgrad_plain_kernel, PW_LDS);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(enc_tail_wgrad_plain_kernel, dim3(grid), dim3(ET_THREADS), PW_LDS, S(stream), D, ldd, rows_d, A, lda, ws, N,
-                       amax_d, amax_a);
-    TVAE_CHECK_LAUNCH();
+    const int rc = launch(enc_tail_wgrad_plain_kernel, dim3(grid), dim3(ET_THREADS), PW_LDS, S(stream), D, ldd, rows_d, A, lda, ws,
+                          N, amax_d, amax_a);
+    if (rc) return rc;
     hipLaunchKernelGGL(enc_tail_wgrad_total_kernel, dim3(ET_C * ET_C / 64), dim3(256), 0, S(stream), (const float*)ws, grid, dW);
     TVAE_CHECK_LAUNCH();
     return 0;

@@ -117,6 +117,7 @@ struct VirtGrad {          // the streamed gradient operand given implicitly (ba
     // sum_k W[m][k] G[m][k] from the raw sums: wgrad_lrf_finalize_kernel)
     int raw;
 };
+constexpr VirtGrad VIRTGRAD_NONE = {nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, 0};
 __device__ __forceinline__ float virt_value(const VirtGrad& vg, float h, float wo, float g) {
     const float dv = vg.act == ACT_LRELU ? (h > 0.f ? 1.f : vg.slope) : (vg.act == ACT_TANH ? 1.f - h * h : 1.f);
     return wo * g * dv;
@@ -131,6 +132,7 @@ struct VirtAct {           // a streamed ACTIVATION operand given implicitly: th
     int act;
     float slope;
 };
+constexpr VirtAct VIRTACT_NONE = {nullptr, nullptr, nullptr, nullptr, 1, 0, 0.f};
 
 struct InTail {            // optional fused backward of SpatialGenerator's FIRST layer (h0 = act(Wc x' + ..), in_dim 2,
     const float* xr;       // src/models.py:107-118) on the output dX of a data-gradient launch (single row tile, panels
@@ -141,6 +143,7 @@ struct InTail {            // optional fused backward of SpatialGenerator's FIRS
     const float* lb;       //   instead of being read from ep.aux
     int Np;
 };
+constexpr InTail INTAIL_NONE = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1};
 
 struct ColDot {            // optional fused skinny layer on the OUTPUT of this one (single row tile, one output):
     const float* w;        //   y[n] = b[0] + sum_m w[m] * Y[m][n]   (SpatialGenerator's last Linear, src/models.py:121-123)
@@ -151,6 +154,7 @@ struct ColDot {            // optional fused skinny layer on the OUTPUT of this 
     // dense_wgrad_x6_dma_kernel LRF) needs nothing else of Y: its data / weight gradient then stream 1/32 of the bytes.
     unsigned* bits;
 };
+constexpr ColDot COLDOT_NONE = {nullptr, nullptr, nullptr, nullptr};
 
 // Sum over the 32 lanes of each half wave, left in every lane of the half: four DPP adds inside the 16-lane rows (quad
 // swaps, half-mirror, mirror: vector-ALU only) and ONE cross-row exchange, instead of five dependent ds_bpermute round
@@ -483,7 +487,7 @@ struct DenseBatch {        // batched launch: row tile t belongs to problem t / 
 //       for the problems that take THIS tile (reductions > 256: several input channels, wide frames) -- round 6
 //   3 = dense_x6_epilogue_lean_store: plain stored output, bias + LeakyReLU | none (forward) or the LeakyReLU mask of a saved
 //       activation (data gradient), whole 512-row tiles; Epilogue.amax_out supported
-// The host picks the instance (abi_dense_x6.hip: launch_dense_x6) when the call has exactly that shape.
+// The host picks the instance (abi_dense_x6.hpp: dense_x6_route) when the call has exactly that shape.
 template <int XV, int NP, int EPI = 0>
 static __global__ __launch_bounds__(DX6_THREADS, 2)
 void dense_x6_kernel(const uint4* __restrict__ A3, const float* __restrict__ X, long ldx, Epilogue ep, int M, int Mpad,

@@ -6,7 +6,7 @@ pre-activation is exact in fp32 in any evaluation order (|pre| <= 40, a multiple
 element sits at zero to rounding, nothing is excluded and every arithmetic is held to its plain bound.
 
 Names as in include/tvae_hip.h: M = rows of H = the reduction (16-row steps), K = rows of dX (512-row tiles), N in 128-column
-tiles.  There is no query for the instance a call took; which branch of launch_dense_x6 (csrc/abi_dense_x6.hip) a case
+tiles.  There is no query for the instance a call took; which branch of dense_x6_route (csrc/abi_dense_x6.hpp) a case
 satisfies, from the arguments alone:
 
   lean_in  <5, NP, 2>   K == 512, dX NULL, in_xr AND in_bc given, no add, mask LeakyReLU (the first `if` of the bits branch)

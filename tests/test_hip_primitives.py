@@ -954,6 +954,32 @@ def test_linear_x6_recomputed_first_layer_operand(F_, B, Np, act, has_lb):
              va_bc=bc, va_lb=LB, va_np=96, parts=3)
 
 
+def test_linear_fwd_x6_h3_refuses_before_its_bound_prepass():
+    """h3 forward with the recomputed first-layer operand (parts = 2, va_*): the entry point forms the operand's bound words in
+    the trailer of the cell buffer (behind the row maxima of tvae_dense_split2h) before its GEMM.  With va_np = 96 (images that
+    are not whole column tiles) the call is refused, and refused BEFORE that pre-pass: the NaN-filled output stays all NaN and
+    the whole cell buffer is bit for bit what it was.  The refused call comes first, while the bound words still hold the zeros
+    the buffer was made with (a pre-pass that ran would leave the bounds there; after a valid call it would only rewrite the
+    same values).  With va_np = 128 the same call is valid: fp64 reference at the fp32 tolerance."""
+    M, K, N, Np, act = 32, 64, 384, 128, 1
+    xr, Wc, bc, LB = rnd(N, 2, seed=1), rnd(K, 2, seed=2), rnd(K, seed=3), rnd(N // Np, K, seed=4)
+    W, b = rnd(M, K, seed=5, scale=K ** -0.5), rnd(M, seed=6)
+    w3 = torch.zeros(query('tvae_dense_x6_bytes', M, K) // 4, device=dev())
+    call('tvae_dense_split2h', W.to(dev()), K, w3, w3.numel() * 4, M, K, 0, None, None)
+    va = dict(va_xr=xr.to(dev()), va_wc=Wc.to(dev()), va_bc=bc.to(dev()), va_lb=LB.to(dev()))
+    Y = torch.full((M, N), float('nan'), device=dev())
+    before = w3.clone()
+    with pytest.raises(Exception):
+        call('tvae_linear_fwd_x6', w3, None, b.to(dev()), None, Y, M, N, K, N, N, act, SLOPE, **va, va_np=96, parts=2)
+    assert bool(torch.isnan(Y).all())
+    assert torch.equal(w3.view(torch.int32), before.view(torch.int32))
+    call('tvae_linear_fwd_x6', w3, None, b.to(dev()), None, Y, M, N, K, N, N, act, SLOPE, **va, va_np=Np, parts=2)
+    h0 = act_ref(Wc.double() @ xr.double().t() + bc.double()[:, None] + LB.double().t().repeat_interleave(Np, dim=1), act)
+    assert bool(torch.isfinite(Y).all())
+    assert rel_err(Y, act_ref(W.double() @ h0 + b.double()[:, None], act)) < GEMM_TOL['f32']
+    assert not torch.equal(w3.view(torch.int32), before.view(torch.int32))      # (the valid call did write its bound words)
+
+
 def test_reductions():
     M, N = 37, 10007
     X = rnd(M, N, seed=1)
