@@ -6,6 +6,7 @@ happens in the HIP library on the current torch stream; torch only provides devi
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from typing import NamedTuple, Optional
@@ -262,29 +263,31 @@ def _split_weight(W: torch.Tensor, rows: int, K: int, transpose: bool, key: str,
     return w3 if scale is None else (w3, csum)
 
 
-def _wgrad(dpre, X, M, N, K, virt=None, va=None, act=0, bits=None, rowdot_w=None, a_amax=None, x_amax=None, ld=0):
+def _wgrad(dpre, X, M, N, K, virt=None, va=None, act=0, bits=None, rowdot_w=None, a_amax=None, x_amax=None, ld=0,
+           nparts=None, x_amax_rows=False, two_val=False):
     """dW = dpre . X^T.  virt = dict(vg_wo, vg_gy, vg_act): dpre is the saved activation H, the gradient wo[m]*gy[n]*act'(H) is formed
     on the fly; va = dict(va_xr, va_wc, va_bc, va_lb, va_np): X is the coordinate layer's output act(..), recomputed (split pipe only).
     bits: [H > 0] as stored sign bits (dpre may then be None).  rowdot_w = the layer's own weight [M][K]: also returns
-    rowdot[m] = sum_k W[m][k] dW[m][k] / wo[m] (taken before the multiplication), as (dW, rowdot)."""
+    rowdot[m] = sum_k W[m][k] dW[m][k] / wo[m] (taken before the multiplication), as (dW, rowdot).
+    The arithmetic is the caller's: nparts of the split-pipe launch (None: _p3()), two_val = the two-valued form of the
+    implicit LeakyReLU gradient (then with `bits`).  Two parts (h3) take the bounds of what is streamed from memory: the
+    two-valued form x_amax unless X is recomputed (va), two plain operands a_amax and x_amax; x_amax_rows = x_amax holds one
+    bound per row of X, not a single word."""
     dev_ = (dpre if dpre is not None else (X if X is not None else virt['vg_wo'])).device
     dW = torch.empty(M, K, dtype=torch.float32, device=dev_)
     need = 64 * max(M, 128) * max(K, 128)
     if split_pipe() and M >= 256 and K >= 128 and N % 16 == 0 and N >= 32:
+        p = _p3() if nparts is None else nparts
+        _expect(p != 2 or (two_val and bits is not None and (va is not None or x_amax is not None)) or
+                (virt is None and va is None and a_amax is not None and x_amax is not None),
+                'two-part weight gradient without the bounds of its streamed operands')
         ws = workspace(dev_, max(query('tvae_linear_wgrad_x6_ws_floats', M, N, K), 1 << 24))
-        # h3 instance: the two-valued form from sign bits against the recomputed first-layer operand (two products per block)
-        # ... or (round 4) against an operand from memory whose bound the caller supplies (x_amax), or two plain operands
-        # from memory with both bounds (a_amax, x_amax)
-        lrf_bits = bits is not None and virt and virt['vg_act'] == ACT_LRELU
-        p = 2 if (parts() == 2 and ((lrf_bits and (va or x_amax is not None)) or
-                                    (virt is None and va is None and a_amax is not None and x_amax is not None))) else _p3()
         rowdot = torch.empty(M, dtype=torch.float32, device=dev_) if rowdot_w is not None else None
-        with _timed('tvae_linear_wgrad_x6', p, bool(virt) and virt['vg_act'] == ACT_LRELU):
-            bounds = dict(a_amax=a_amax, x_amax=x_amax) if p == 2 else {}
+        with _timed('tvae_linear_wgrad_x6', p, two_val):
             call('tvae_linear_wgrad_x6', dpre, X, dW, ws, ws.numel(), M, N, K, ld or N, ld or N, 0,
                  **(virt or dict(vg_act=act)), vg_slope=LRELU_SLOPE, **(va or {}), vg_bits=bits, parts=p,
-                 rd_w=rowdot_w.contiguous() if rowdot_w is not None else None, rd_ldw=K, rd_rowdot=rowdot, **bounds,
-                 x_amax_rows=int(p == 2 and x_amax is not None and x_amax.numel() == K and K > 1))   # one bound per row of X
+                 rd_w=rowdot_w.contiguous() if rowdot_w is not None else None, rd_ldw=K, rd_rowdot=rowdot, a_amax=a_amax,
+                 x_amax=x_amax, x_amax_rows=int(x_amax_rows))
         return dW if rowdot_w is None else (dW, rowdot)
     _expect(virt is None and va is None and rowdot_w is None, 'implicit operands need the split-pipe weight gradient')
     ws = workspace(dev_, max(need, 1 << 24))
@@ -918,6 +921,82 @@ def decoder_route(B: int, Np: int, F_: int, n_hidden: int, n_out: int, act: int,
         no_h=sign_bits and F_ <= 512, h3=parts() == 2 and split, infer=infer)
 
 
+class DecoderLayer(NamedTuple):
+    """The launches of one hidden layer of DecoderFn (split-pipe routes; the f32 launches take none of it).  A bound is
+    named by where it comes from, '' = none: the operand is exact, recomputed, or the launch runs three-part."""
+    # forward (tvae_linear_fwd_x6)
+    parts: int
+    x_bound: str         # bound of the streamed input: 'virt' (recomputed coordinate layer: none needed), 'rows' (the first
+    #                      layer's analytic bound), 'meas' (the maximum the layer in front left)
+    y_max: bool          # leaves max |output| for the layer behind
+    fused_out: bool      # applies the single-output Linear too
+    store_h: bool        # writes its activation
+    store_bits: bool     # writes [h > 0] as bits
+    # backward
+    virt_grad: bool      # its pre-activation gradient is re-formed from the saved activation / bits, not stored
+    two_val: bool        # ... in the two-valued LeakyReLU form
+    from_bits: bool      # ... with no stored activation: row sums and dWo come out of the two GEMMs
+    wgrad_parts: int
+    wgrad_bound: str     # 'two_val' (input bound x max |gy|), 'plain' (gradient word and input bound)
+    wgrad_x_rows: bool   # ... the input bound is one value per unit (the row-sum chain exists), not a single word
+    dgrad_parts: int
+    d_bound: str         # bound word of the stored gradient it streams: 'top' (analytic, behind the output layer), 'meas'
+    dgrad_max: bool      # the data gradient leaves max |result| for the layer in front
+    fuse_in: bool        # the data gradient feeds the recomputed coordinate layer's backward; its result is not stored
+
+
+class DecoderPlan(NamedTuple):
+    """Arithmetic and bounds of every DecoderFn launch, decided once by decoder_plan() and kept on ctx with the route."""
+    layers: tuple        # of DecoderLayer, one per hidden layer
+    first_parts: int     # Fourier first layer on the split pipe (under max(1, max |z|) in h3)
+    four_bound: str      # bound word of the gradient the Fourier layer's backward streams: 'top', 'two_val' (analytic, behind
+    #                      a two-valued data gradient), 'meas'
+    four_wgrad_parts: int
+    four_dgrad_parts: int
+    chain: bool          # per-unit analytic bounds of the stored activations (row-sum chain from the first layer)
+    h_words: bool        # words for the measured maxima of the hidden activations
+    top_bound: bool      # analytic bound word of the stored top gradient
+    d_words: bool        # words for the measured maxima of the stored gradients
+
+
+def decoder_plan(rt: DecoderRoute, n_hidden: int, resid: bool, fourier: bool) -> DecoderPlan:
+    """Per-launch decisions of DecoderFn on route `rt` (which holds what the activation decides: sign_bits) in the current
+    arithmetic.  Pure: no tensor, no launch.  The only place where the arithmetic turns into a `parts` value or a bound for
+    the decoder; h3 (two parts) runs
+      forward: the layer behind a recomputed coordinate layer; behind a stored first layer under its analytic bound (round
+        4; a residual first hidden layer stays three-part); every deeper layer under the maximum the layer in front
+        measured (round 6: an analytic chain would lose ~5 bits of fp16's exponent per layer);
+      backward: the two-valued implicit gradient (exact 0 / 1 operand), and every stored gradient under its bound word
+        -- the top one analytic, every later one measured by the data gradient that stores it."""
+    return _decoder_plan(rt, n_hidden, resid, bool(fourier), parts(), _p3())
+
+
+@functools.lru_cache(maxsize=None)
+def _decoder_plan(rt, n_hidden, resid, fourier, p, p3):
+    h3 = rt.h3
+    layers = []
+    for li in range(n_hidden):
+        first, last = li == 0, li == n_hidden - 1
+        virt_in = first and rt.virt_act
+        x_bound = 'virt' if virt_in else '' if not h3 else 'meas' if not first else '' if resid else 'rows'
+        virt_grad, two_val = last and rt.virt_grad, last and rt.sign_bits
+        wgrad_bound = '' if (not h3 or virt_in or (virt_grad and not two_val)) else 'two_val' if two_val else 'plain'
+        layers.append(DecoderLayer(
+            parts=2 if (h3 and x_bound) else p3, x_bound=x_bound, y_max=h3 and not last, fused_out=last and rt.fused_out,
+            store_h=not (last and rt.no_h), store_bits=two_val and not rt.infer,
+            virt_grad=virt_grad, two_val=two_val, from_bits=last and rt.no_h,
+            wgrad_parts=2 if (h3 and (two_val or wgrad_bound)) else p3, wgrad_bound=wgrad_bound,
+            wgrad_x_rows=bool(wgrad_bound) and not rt.virt_act,
+            dgrad_parts=2 if (h3 and (two_val or not virt_grad)) else p3,
+            d_bound='' if (not h3 or virt_grad) else 'top' if last else 'meas',
+            dgrad_max=h3 and (n_hidden >= 2 or fourier) and not virt_in, fuse_in=virt_in))
+    four_bound = '' if not (h3 and fourier) else 'top' if not layers else 'two_val' if layers[0].two_val else 'meas'
+    return DecoderPlan(
+        layers=tuple(layers), first_parts=p, four_bound=four_bound, four_wgrad_parts=2 if four_bound else p3,
+        four_dgrad_parts=2 if four_bound else p3, chain=h3 and not rt.virt_act, h_words=h3 and n_hidden >= 2,
+        top_bound=h3 and not rt.virt_grad, d_words=h3 and (n_hidden >= 2 or fourier))
+
+
 def decoder_padded_pixels(Np: int, B: int, F_: int, n_hidden: int, n_out: int, resid: bool, fourier: bool, act: int) -> int:
     """Round 5: images whose pixel count is not a multiple of the 128-column GEMM tile (28 x 28 = 784, 50 x 50 = 2 500) cannot
     take the decoder's fast path -- first layer recomputed inside its consumers, lean epilogues, fused first-layer backward --
@@ -933,6 +1012,96 @@ def decoder_padded_pixels(Np: int, B: int, F_: int, n_hidden: int, n_out: int, r
     return Np_p
 
 
+class _DecoderBounds:
+    """The h3 bound words of one DecoderFn call (include/tvae_hip.h: x_amax, a_amax, y_amax), formed as the plan asks and
+    handed to the launches by where the plan says they come from.  Forward: rows[l], the per-unit analytic bound of the
+    stored activation hs[l] (the first layer's, then |act(W h + b [+ h])| <= |W| rows + |b| [+ rows] unit by unit), and
+    meas, one word per hidden activation that the launch storing it fills with its maximum.  Kept on ctx; begin_backward()
+    adds the words of the stored gradients (dmeas) and max |gy|, formed on first use."""
+
+    def __init__(self, plan: DecoderPlan, n_hidden: int, dev):
+        self.plan, self.rows, self.h_bound = plan, [None], None
+        self.meas = torch.zeros(max(n_hidden, 1), dtype=torch.float32, device=dev) if plan.h_words else None
+
+    def _first(self, rows):
+        self.rows, self.h_bound = [rows], rows.amax().reshape(1)
+
+    def first_fourier(self, Wfull, bc, z_rows):
+        """Fourier first layer: the streamed operand is cos(.) <= 1 over the latent rows, so its bound max(1, max |z|) is
+        known without looking at it (returned); the layer's output is bounded by the absolute row sums of the weights."""
+        feat_amax = torch.clamp(_inf_norm(z_rows), min=1.0) if z_rows is not None else \
+            torch.ones(1, dtype=torch.float32, device=Wfull.device)
+        self._first(Wfull.detach().abs().sum(1) * feat_amax + bc.detach().abs())
+        return feat_amax
+
+    def first_coord(self, xr, Wc, bc, LB):
+        """The stored coordinate layer: |act(pre)| <= |pre| <= this bound."""
+        self._first(_inf_norm(xr) * Wc.detach().abs().sum(1) +
+                    ((bc.detach()[None, :] + LB).abs().amax(0) if LB is not None else bc.detach().abs()))
+
+    def next_layer(self, W, b, resid):
+        r = self.rows[-1]
+        self.rows.append(torch.addmv(b.detach().abs(), W.detach().abs(), r) + (r if resid else 0.0)
+                         if self.plan.chain else None)
+
+    def fwd_x(self, li, lp):
+        return self.h_bound if lp.x_bound == 'rows' else self.meas[li - 1:li] if lp.x_bound == 'meas' else None
+
+    def fwd_y(self, li, lp):
+        return self.meas[li:li + 1] if lp.y_max else None
+
+    def begin_backward(self, gy, Wo, n_hidden):
+        """(per backward call: nothing of an earlier one is reused.)  The top gradient's word: |d[m][n]| <=
+        max_m sum_o |Wo[o][m]| max |gy| (act' <= 1).  Measured words only where a stored gradient is streamed again -- a
+        second hidden layer, or the Fourier first layer behind the first one; other configurations launch no fill."""
+        self.gy, self.gy_max = gy, None
+        self.top = (self.gy_amax() * Wo.detach().abs().sum(0).amax()).reshape(1) if self.plan.top_bound else None
+        self.dmeas = torch.zeros(n_hidden + 1, dtype=torch.float32, device=gy.device) if self.plan.d_words else None
+
+    def gy_amax(self):
+        if self.gy_max is None:
+            self.gy_max = _inf_norm(self.gy)         # (one reduction over the output gradient)
+        return self.gy_max
+
+    def h_in(self, li):
+        """Bound of hidden layer li's stored input: the first layer's analytic per-unit bound, or a deeper layer's measured
+        maximum, capped unit by unit by the row-sum chain where the forward formed it (a unit far below the others keeps
+        its own scale)."""
+        if li == 0:
+            return self.rows[0]
+        m = self.meas[li - 1:li]
+        return torch.minimum(self.rows[li], m) if self.plan.chain else m
+
+    def wgrad_x(self, li, lp):
+        """x_amax of layer li's weight gradient; the two-valued form's operand is gy[n] X[k][n] (vg_gy is gy: n_out == 1)."""
+        return self.h_in(li) * self.gy_amax() if lp.wgrad_bound == 'two_val' else self.h_in(li) if lp.wgrad_bound else None
+
+    def d_word(self, src, li):
+        """Bound word of the stored gradient in front of hidden layer li (li = n_hidden: the top one; 'meas': what layer li's
+        data gradient left)."""
+        return self.top if src == 'top' else self.dmeas[li:li + 1] if src == 'meas' else None
+
+    def behind_two_val(self, W, wo):
+        """The gradient a two-valued data gradient leaves is read again by the Fourier first layer's backward, under this
+        analytic bound: |dX[k][n]| <= max |gy| * sum_m |wo[m] W[m][k]|."""
+        return self.gy_amax() * (W.detach().abs() * wo.detach().abs()[:, None]).sum(0).amax().reshape(1)
+
+    def dgrad_y(self, li, lp):
+        return self.dmeas[li:li + 1] if lp.dgrad_max else None
+
+
+def _decoder_params(params, n_hidden):
+    """DecoderFn's parameter tuple -> Wc, bc, Wl, [(W_i, b_i)], Wo, bo, Wf, bf (None where the model has none)."""
+    Wc, bc, Wl = params[:3]
+    Wo, bo, Wf, bf = params[3 + 2 * n_hidden:7 + 2 * n_hidden]
+    return Wc, bc, Wl, [(params[3 + 2 * i], params[4 + 2 * i]) for i in range(n_hidden)], Wo, bo, Wf, bf
+
+
+def _decoder_va(xr, Wc, bc, LB, Nt, Np):
+    """Keyword group of the launches that recompute the coordinate layer's output instead of reading it (virt_act)."""
+    return dict(va_xr=xr.view(Nt, 2), va_wc=Wc.contiguous(), va_bc=bc, va_lb=LB, va_np=Np)
+
+
 class DecoderFn(torch.autograd.Function):
     """SpatialGenerator.forward (src/models.py:95-123): [Fourier] -> coord_linear + latent_linear -> act ->
     (Linear | ResidLinear, act) x (L-1) -> Linear(hid, n_out).  x [B][Np][2], z [B][zd] -> (B, Np, n_out).
@@ -941,10 +1110,7 @@ class DecoderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xr, z, act, resid, sigma, n_hidden, *params):
-        Wc, bc, Wl = params[0], params[1], params[2]
-        hidden = [(params[3 + 2 * i], params[4 + 2 * i]) for i in range(n_hidden)]
-        Wo, bo = params[3 + 2 * n_hidden], params[4 + 2 * n_hidden]
-        Wf, bf = params[5 + 2 * n_hidden], params[6 + 2 * n_hidden]
+        Wc, bc, Wl, hidden, Wo, bo, Wf, bf = _decoder_params(params, n_hidden)
         xr = xr.contiguous()
         _expect(xr.dim() == 3 and xr.shape[2] == 2, f'decoder coordinates {tuple(xr.shape)} are not (B, N, 2)')
         B, Np = xr.shape[0], xr.shape[1]
@@ -956,6 +1122,8 @@ class DecoderFn(torch.autograd.Function):
         _expect(Wl is None or (z is not None and tuple(z.shape) == (B, Wl.shape[1])), 'latent z does not match latent_linear')
         dev = xr.device
         rt = decoder_route(B, Np, F_, n_hidden, n_out, act, resid, Wf.shape[0] if Wf is not None else 0, _INFER)
+        plan = decoder_plan(rt, n_hidden, resid, Wf is not None)
+        bd = _DecoderBounds(plan, n_hidden, dev)
         ldn = rt.ldn
         LB = None
         if ldn != Nt:
@@ -969,11 +1137,10 @@ class DecoderFn(torch.autograd.Function):
             LB = torch.empty(B, F_, dtype=torch.float32, device=dev)
             call('tvae_latent_bias', Wl.contiguous(), z, LB, B, F_, zd)
         feat = None
-        feat_amax = h_bound = h_rows = None       # h3 bounds of operands that are streamed from memory (include/tvae_hip.h: x_amax)
         # without Fourier features the coordinate layer's output is two FMAs and an activation per element: the layers
         # that consume it (first hidden layer: forward, mask of the data gradient, weight gradient) recompute it and the
         # [hid][B*n^2] tensor is never written or read (virt_act)
-        va = dict(va_xr=xr.view(Nt, 2), va_wc=Wc.contiguous(), va_bc=bc, va_lb=LB, va_np=Np) if rt.virt_act else None
+        va = _decoder_va(xr, Wc, bc, LB, Nt, Np) if rt.virt_act else None
         h = None if rt.virt_act else torch.empty(F_, ldn, dtype=torch.float32, device=dev)
         if rt.virt_act:
             _note('dec.virt_act')
@@ -988,141 +1155,90 @@ class DecoderFn(torch.autograd.Function):
                 if zx:
                     feat_all[Ff:, :Nt].view(zx, B, Np).copy_(z.contiguous().t().unsqueeze(2).expand(zx, B, Np))
                 Wfull = torch.cat([Wc, Wl], 1) if zx else Wc
-                # h3 (round 4): the streamed operand is cos(.) <= 1 over the latent rows: its bound max(1, max |z|) is known
-                # without looking at it; the layer's OUTPUT is then bounded by the largest absolute row sum of the weights
-                p_c = parts()
-                if rt.h3:
-                    feat_amax = torch.clamp(_inf_norm(z), min=1.0) if zx else torch.ones(1, dtype=torch.float32, device=dev)
-                    # per-unit bound of this layer's output (the weight gradient of the layer BEHIND it takes one
-                    # scale per row of its X operand = per unit here), and its maximum for the forward of that layer
-                    h_rows = Wfull.detach().abs().sum(1) * feat_amax + bc.detach().abs()
-                    h_bound = h_rows.amax().reshape(1)
+                feat_amax = None
+                if plan.chain:                         # (h3, round 4)
+                    feat_amax = bd.first_fourier(Wfull, bc, z if zx else None)
                     _note('dec.four_h3')
-                w3c = _split_weight(Wfull, F_, Ff + zx, False, 'x6_dense_wc', nparts=p_c)
-                with _timed('tvae_linear_fwd_x6', p_c):
+                w3c = _split_weight(Wfull, F_, Ff + zx, False, 'x6_dense_wc', nparts=plan.first_parts)
+                with _timed('tvae_linear_fwd_x6', plan.first_parts):
                     call('tvae_linear_fwd_x6', w3c, feat_all, bc, None, h, F_, Nt, Ff + zx, ldn, ldn, act, LRELU_SLOPE,
-                         parts=p_c, x_amax=feat_amax)
+                         parts=plan.first_parts, x_amax=feat_amax)
             else:
                 call('tvae_linear_fwd', Wc.contiguous(), feat, bc, LB, Np, None, h, F_, Nt, Ff, ldn, ldn, act, LRELU_SLOPE)
         else:
             call('tvae_dec_l0_fwd', xr, Wc.contiguous(), bc, LB, h, ldn, F_, Nt, Np, act, LRELU_SLOPE)
-            if rt.h3:                                  # the stored coordinate layer: |act(pre)| <= |pre| <= this bound
-                h_rows = _inf_norm(xr) * Wc.detach().abs().sum(1) + \
-                    ((bc.detach()[None, :] + LB).abs().amax(0) if LB is not None else bc.detach().abs())      # per unit
-                h_bound = h_rows.amax().reshape(1)
+            if plan.chain:
+                bd.first_coord(xr, Wc, bc, LB)
         hs = [h]
         yh = torch.empty(B, Np, n_out, dtype=torch.float32, device=dev)
         sbits = None
-        # Round 6: every hidden layer whose input is a STORED activation runs h3 -- the launch that stores hs[l] also leaves
-        # max |hs[l]| in a word (tvae_linear_fwd_x6 y_amax, atomic max from its epilogue), the measured bound of the launch that
-        # streams it next (forward here, weight gradient in the backward).  An analytic row-sum chain would lose ~5 bits of
-        # fp16's exponent headroom per layer; a measured maximum loses none, whatever the depth.
-        meas_words = torch.zeros(max(n_hidden, 1), dtype=torch.float32, device=dev) if (rt.h3 and n_hidden >= 2) else None
-        h_meas = [None] * (n_hidden + 1)          # h_meas[l]: measured max |hs[l]| (one device word) or None
-        rows_l = h_rows                           # per-unit bound of hs[l] by the row-sum chain (None: not available)
-        rows_all = [rows_l]
-        for li, (W, b) in enumerate(hidden):
+        for li, ((W, b), lp) in enumerate(zip(hidden, plan.layers)):
             hn = None
-            last = li == n_hidden - 1
             if rt.split:
-                # h3 instances: the layer whose streamed operand is the recomputed first-layer activation, or (round 4) the
-                # stored output of the first layer under its bound, or (round 6) a deeper layer's stored input under its
-                # measured maximum
-                h3_mem = rt.h3 and not (va and li == 0) and (
-                    (li == 0 and h_bound is not None and not resid) or (li > 0 and h_meas[li] is not None))
-                x_bound = (h_bound if li == 0 else h_meas[li]) if h3_mem else None
-                p_l = 2 if (rt.h3 and ((va and li == 0) or h3_mem)) else _p3()
-                if h3_mem:
-                    _note('dec.hidden_h3_mem' if li == 0 else 'dec.hidden_h3_meas')
-                w3 = _split_weight(W, F_, F_, False, 'x6_dense_w', nparts=p_l)
-                # the last hidden layer also applies the single-output Linear that follows it (one pass less over h)
-                fuse = last and rt.fused_out
+                if lp.x_bound in ('rows', 'meas'):
+                    _note('dec.hidden_h3_mem' if lp.x_bound == 'rows' else 'dec.hidden_h3_meas')
+                w3 = _split_weight(W, F_, F_, False, 'x6_dense_w', nparts=lp.parts)
                 # the backward of the single-output Linear behind the last hidden layer needs only the SIGN of this
                 # layer's LeakyReLU output (two-valued implicit gradient): one bit per element, stored by this launch
-                if last and rt.sign_bits and not rt.infer:
+                if lp.store_bits:
                     sbits = torch.empty(F_, Nt // 32, dtype=torch.int32, device=dev)
                     _note('dec.sign_bits')
                 # Round 4: with the fused output dot AND the sign bits, nothing downstream needs this layer's activation
                 # itself -- the backward takes [H > 0] from the bits and dWo from the identity sum_k W[m][k] G[m][k] +
                 # b[m] g0[m] (include/tvae_hip.h: tvae_linear_dgrad_x6 vg_bits) -- so the 2.1 GB tensor is neither written
                 # here nor read there.  (inference: same launch without the bits -- only the fused output dot leaves it)
-                if last and rt.no_h:
-                    _note('dec.no_h_inference' if rt.infer else 'dec.no_h')
-                else:
+                if lp.store_h:
                     hn = torch.empty(F_, ldn, dtype=torch.float32, device=dev)
-                # this layer's output feeds another hidden layer: leave its maximum for that launch
-                emit = meas_words[li:li + 1] if (meas_words is not None and not last) else None
-                with _timed('tvae_linear_fwd_x6', p_l):
+                else:
+                    _note('dec.no_h_inference' if rt.infer else 'dec.no_h')
+                # the last hidden layer also applies the single-output Linear that follows it (one pass less over h)
+                with _timed('tvae_linear_fwd_x6', lp.parts):
                     call('tvae_linear_fwd_x6', w3, hs[-1], b, hs[-1] if resid else None, hn, F_, Nt, F_, ldn, ldn, act,
-                         LRELU_SLOPE, **(dict(col_w=Wo.contiguous(), col_b=bo, col_y=yh) if fuse else {}),
-                         **(va if va and li == 0 else {}), sign_bits=sbits, parts=p_l, x_amax=x_bound, y_amax=emit)
-                h_meas[li + 1] = emit
-                _note('dec.fused_out' if fuse else 'dec.hidden_x6')
+                         LRELU_SLOPE, **(dict(col_w=Wo.contiguous(), col_b=bo, col_y=yh) if lp.fused_out else {}),
+                         **(va if lp.x_bound == 'virt' else {}), sign_bits=sbits, parts=lp.parts, x_amax=bd.fwd_x(li, lp),
+                         y_amax=bd.fwd_y(li, lp))
+                _note('dec.fused_out' if lp.fused_out else 'dec.hidden_x6')
             else:
                 hn = torch.empty(F_, ldn, dtype=torch.float32, device=dev)
                 call('tvae_linear_fwd', W.contiguous(), hs[-1], b, None, 1, hs[-1] if resid else None, hn, F_, Nt, F_,
                      ldn, ldn, act, LRELU_SLOPE)
-            if rows_l is not None:                     # |act(W h + b [+ h])| <= |W| rows + |b| [+ rows], unit by unit
-                rows_l = torch.addmv(b.detach().abs(), W.detach().abs(), rows_l) + (rows_l if resid else 0.0)
-            rows_all.append(rows_l)
+            bd.next_layer(W, b, resid)
             hs.append(hn)
         if not rt.fused_out:
             call('tvae_coldot', hs[-1], ldn, F_, Nt, Wo.contiguous(), 1, F_, bo, n_out, yh)
         if rt.infer:
             return yh
-        ctx.save_for_backward(xr, z if Wl is not None else None, feat, LB if rt.virt_act else None, *hs,
-                              *[p for p in params if p is not None])
-        ctx.meta = (act, resid, sigma, n_hidden, Wl is not None, Wf is not None, B, Np)
+        ctx.save_for_backward(xr, z if Wl is not None else None, feat, LB if rt.virt_act else None, *hs, *params)
+        ctx.meta = (act, resid, sigma, n_hidden, B, Np)
         ctx.arith = get_gemm_mode()
-        ctx.route, ctx.sbits = rt, sbits
-        ctx.h_meas, ctx.rows_all = h_meas, rows_all
+        ctx.route, ctx.plan, ctx.bounds, ctx.sbits = rt, plan, bd, sbits
         return yh
 
     @staticmethod
     @_in_forward_arithmetic
     def backward(ctx, gy):
-        act, resid, sigma, n_hidden, has_l, has_f, B, Np = ctx.meta
-        rt = ctx.route
-        sv = list(ctx.saved_tensors)
-        xr, z, feat, LB = sv[0], sv[1], sv[2], sv[3]
-        hs = sv[4:4 + n_hidden + 1]
-        ps = sv[4 + n_hidden + 1:]
-        it = iter(ps)
-        Wc, bc = next(it), next(it)
-        Wl = next(it) if has_l else None
-        hidden = [(next(it), next(it)) for _ in range(n_hidden)]
-        Wo, bo = next(it), next(it)
-        Wf, bf = (next(it), next(it)) if has_f else (None, None)
+        act, resid, sigma, n_hidden, B, Np = ctx.meta
+        rt, plan, bd = ctx.route, ctx.plan, ctx.bounds
+        sv = ctx.saved_tensors
+        xr, z, feat, LB = sv[:4]
+        hs = sv[4:5 + n_hidden]
+        Wc, bc, Wl, hidden, Wo, bo, Wf, bf = _decoder_params(sv[5 + n_hidden:], n_hidden)
         Nt = B * Np
         F_, n_out = Wc.shape[0], Wo.shape[0]
         dev = xr.device
         ldn = rt.ldn                                     # (row stride of every stored [features][Nt] tensor)
         gy = gy.contiguous().view(Nt, n_out)
-        gy_max = []                                      # max |gy|, formed once (one reduction over the output gradient) on first use
-
-        def gy_amax():
-            if not gy_max:
-                gy_max.append(_inf_norm(gy))
-            return gy_max[0]
-
-        def in_bound(li):
-            """Bound of hidden layer li's stored input (None: none): the first layer's analytic per-unit bound, or a deeper
-            layer's measured maximum, capped unit by unit by the row-sum chain where the forward formed it (a unit far below
-            the others keeps its own scale)."""
-            if li == 0:
-                return ctx.rows_all[0]
-            m, r = ctx.h_meas[li], ctx.rows_all[li]
-            return m if (m is None or r is None) else torch.minimum(r, m)
+        bd.begin_backward(gy, Wo, n_hidden)
         # last layer: one pass over h gives d (pre-activation gradient), its row sums and dWo
         gyT = gy.t().contiguous()
         dbo = _rowsum(gyT, n_out, Nt)
         # with a single output the gradient of the last hidden activation, Wo[f] gy[n] act'(h[f][n]), is cheap to
         # re-form inside the two GEMMs that consume it: it is then never written (dec_out_bwd only produces row sums)
         d = None if rt.virt_grad else torch.empty(F_, ldn, dtype=torch.float32, device=dev)
-        tot = torch.empty(1 + n_out, F_, dtype=torch.float32, device=dev)
+        tot = torch.empty(1 + n_out, F_, dtype=torch.float32, device=dev)      # tot[0]: bias gradient of the last hidden layer
         # two-valued implicit gradient without the saved activation: the data-gradient launch of the last hidden layer
-        # streams the sign bits anyway and returns the two row sums this layer's backward needs (tot[0] = bias gradient
-        # below, tot[1] = dWo): no pass of its own
+        # streams the sign bits anyway and returns the two row sums this layer's backward needs (tot[0], tot[1] = dWo): no
+        # pass of its own
         if not rt.no_h:
             part = workspace(dev, ((Nt + 1023) // 1024) * F_ * (1 + n_out))
             call('tvae_dec_out_bwd', gy, n_out, Wo.contiguous(), hs[-1], ldn, d, ldn, F_, Nt, act, LRELU_SLOPE, part,
@@ -1132,78 +1248,52 @@ class DecoderFn(torch.autograd.Function):
         vg = dict(vg_wo=Wo.contiguous().view(-1), vg_gy=gy.view(-1), vg_act=act) if rt.virt_grad else None
         if rt.virt_grad:
             _note('dec.virt_grad')
-        dWo, drow = tot[1:], tot[0]
+        va = _decoder_va(xr, Wc, bc, LB, Nt, Np) if rt.virt_act else None
+        dWo = tot[1:]
         grads_hidden = []
-        # Round 6 (h3 for every hidden layer): one bound word per stored gradient tensor -- the top one analytically
-        # (|d[m][n]| <= max_m sum_o |Wo[o][m]| max |gy|: act' <= 1), every later one measured by the data-gradient launch that
-        # stores it (tvae_linear_dgrad_x6 y_amax)
-        # (words for the measured maxima: only where a stored gradient is streamed again -- a second hidden layer, or the Fourier
-        #  first layer behind the first one; the single-hidden-layer configurations need none and launch no fill)
-        dmeas = torch.zeros(n_hidden + 1, dtype=torch.float32, device=dev) if (rt.h3 and (n_hidden >= 2 or has_f)) else None
-        d_bnd = None                                     # bound word of the stored gradient `d` (None: none / not stored)
-        if rt.h3 and not rt.virt_grad:
-            d_bnd = (gy_amax() * Wo.detach().abs().sum(0).amax()).reshape(1)
         for li in range(n_hidden - 1, -1, -1):
-            W, b = hidden[li]
-            hprev = hs[li]
-            use_vg = vg is not None and li == n_hidden - 1
-            dsrc = hs[-1] if use_vg else d             # implicit operand: pass the saved activation instead
-            va = dict(va_xr=xr.view(Nt, 2), va_wc=Wc.contiguous(), va_bc=bc, va_lb=LB, va_np=Np) if hprev is None else None  # recomputed
-            sbits = ctx.sbits if (use_vg and act == ACT_LRELU) else None      # [h > 0] as stored bits (two-valued form)
-            # ... without the stored activation: the weight gradient also returns rowdot[m] = sum_k W[m][k] G[m][k] for dWo,
-            # and the data gradient below the two row sums of the layer behind
-            from_bits = use_vg and rt.no_h
-            # h3 with the layer's input read from memory, under its bound: the two-valued form (round 4; its operand is
-            # gy[n] X[k][n], so times max |gy| -- vg_gy is gy: n_out == 1), or the plain form of two stored tensors (round 6)
-            xb = in_bound(li) if (rt.h3 and va is None and (sbits is not None if use_vg else d_bnd is not None)) else None
-            plain_h3 = not use_vg and xb is not None
-            if plain_h3:
+            (W, b), lp, hprev = hidden[li], plan.layers[li], hs[li]
+            dsrc = hs[-1] if lp.virt_grad else d       # implicit operand: pass the saved activation instead
+            sbits = ctx.sbits if lp.two_val else None  # [h > 0] as stored bits
+            d_bnd = bd.d_word(lp.d_bound, li + 1)
+            if lp.wgrad_bound == 'plain':
                 _note('dec.wgrad_h3_meas')
-            elif xb is not None:
-                xb = xb * gy_amax()
-            wg = _wgrad(dsrc, hprev, F_, Nt, F_, vg if use_vg else None, va, act, sbits, rowdot_w=W if from_bits else None,
-                        a_amax=d_bnd if plain_h3 else None, x_amax=xb, ld=ldn)
-            dW, rowdot = wg if from_bits else (wg, None)
-            db = drow if drow is not None else _rowsum(d, F_, Nt, ld=ldn)
-            drow = None
+            # from_bits: the weight gradient also returns rowdot[m] = sum_k W[m][k] G[m][k] for dWo, and the data gradient
+            # below the two row sums of the layer behind
+            wg = _wgrad(dsrc, hprev, F_, Nt, F_, vg if lp.virt_grad else None, va if lp.x_bound == 'virt' else None, act,
+                        sbits, rowdot_w=W if lp.from_bits else None, a_amax=d_bnd if lp.wgrad_bound == 'plain' else None,
+                        x_amax=bd.wgrad_x(li, lp), ld=ldn, nparts=lp.wgrad_parts, x_amax_rows=lp.wgrad_x_rows,
+                        two_val=lp.two_val)
+            dW, rowdot = wg if lp.from_bits else (wg, None)
+            db = tot[0] if li == n_hidden - 1 else _rowsum(d, F_, Nt, ld=ldn)
             # the data gradient of the FIRST hidden layer behind a recomputed coordinate layer feeds that layer's backward
             # from its epilogue (coordinate gradient + per-panel row sums); its result is then never written
-            fuse_in = li == 0 and rt.virt_act
-            dprev = None if fuse_in else torch.empty(F_, ldn, dtype=torch.float32, device=dev)
+            dprev = None if lp.fuse_in else torch.empty(F_, ldn, dtype=torch.float32, device=dev)
             if rt.split:
-                # LeakyReLU: the implicit gradient in its two-valued form (3 MFMAs per block instead of 6)
-                two_val = use_vg and act == ACT_LRELU
-                # h3 instances: the exact 0 / 1 operand (two products), or (round 6) a stored gradient under its bound word
-                p_d = 2 if (rt.h3 and (two_val or (not use_vg and d_bnd is not None))) else _p3()
-                if p_d == 2 and not two_val:
+                p_d = lp.dgrad_parts
+                if lp.d_bound:
                     _note('dec.dgrad_h3_meas')
-                emit = dmeas[li:li + 1] if (dmeas is not None and not fuse_in) else None      # max |dprev| for its consumers
-                if two_val:
+                if lp.two_val:                         # LeakyReLU: 3 MFMAs per block instead of 6
                     w3t, csum = _split_weight(W, F_, F_, True, 'x6_dense_wt', scale=vg['vg_wo'], nparts=p_d)
                     _note('dec.virt_grad_2val')
                 else:
                     w3t, csum = _split_weight(W, F_, F_, True, 'x6_dense_wt', nparts=p_d), None
                 fin = {}
-                if fuse_in:                            # (hprev is None, so `va` is set, exactly here: hence in_bc / in_lb / in_np)
+                if lp.fuse_in:
                     gxr_f = torch.empty(B, Np, 2, dtype=torch.float32, device=dev)
                     part_f = workspace(dev, (Nt // 128) * F_ * 3)
                     fin = dict(in_xr=xr.view(Nt, 2), in_wc=Wc.contiguous(), in_gxr=gxr_f, in_part=part_f,
                                in_part_floats=part_f.numel(), in_bc=bc, in_lb=LB, in_np=Np)
-                rs_part = _scratch(dev, 'dec_rs_part', (Nt // 128) * F_ * 2) if from_bits else None
+                rs_part = _scratch(dev, 'dec_rs_part', (Nt // 128) * F_ * 2) if lp.from_bits else None
                 rs = dict(rs_part=rs_part, rs_part_floats=rs_part.numel(), rs_wo=vg['vg_wo'], rs_gysum=dbo, rs_db=tot[0],
-                          rs_dwo=tot[1], vg_bits=sbits, rs_rowdot=rowdot, rs_bias=b) if from_bits else {}
-                with _timed('tvae_linear_dgrad_x6', p_d, two_val):
+                          rs_dwo=tot[1], vg_bits=sbits, rs_rowdot=rowdot, rs_bias=b) if lp.from_bits else {}
+                with _timed('tvae_linear_dgrad_x6', p_d, lp.two_val):
                     call('tvae_linear_dgrad_x6', w3t, dsrc, d if resid else None, hprev, dprev, F_, Nt, F_, ldn, ldn, act,
-                         LRELU_SLOPE, **fin, vg_wo=vg['vg_wo'] if (use_vg and not two_val) else None,
-                         vg_gy=vg['vg_gy'] if use_vg else None, vg_csum=csum, **rs, parts=p_d,
-                         x_amax=d_bnd if (p_d == 2 and not two_val) else None, y_amax=emit)
-                if fuse_in:
+                         LRELU_SLOPE, **fin, vg_wo=vg['vg_wo'] if (lp.virt_grad and not lp.two_val) else None,
+                         vg_gy=vg['vg_gy'] if lp.virt_grad else None, vg_csum=csum, **rs, parts=p_d, x_amax=d_bnd,
+                         y_amax=bd.dgrad_y(li, lp))
+                if lp.fuse_in:
                     _note('dec.fuse_in')
-                d_bnd = emit
-                if two_val and li == 0 and has_f and rt.h3:
-                    # the gradient this launch leaves in `dprev` is read again by the Fourier first layer's backward, under
-                    # this analytic bound: |dX[k][n]| <= max |gy| * sum_m |wo[m] W[m][k]|
-                    d_bnd = gy_amax() * (W.detach().abs() * vg['vg_wo'].detach().abs()[:, None]).sum(0).amax().reshape(1)
             else:
                 call('tvae_linear_dgrad', W.contiguous(), d, d if resid else None, hprev, dprev, F_, Nt, F_, ldn, ldn,
                      act, LRELU_SLOPE)
@@ -1217,7 +1307,7 @@ class DecoderFn(torch.autograd.Function):
         if rt.virt_act:
             dWc = torch.empty(F_, 2, dtype=torch.float32, device=dev)
             call('tvae_dec_in_total', part_f, B, Np // 128, F_, Simg, dbc, dWc)
-        elif has_f:
+        elif Wf is not None:
             call('tvae_rowdot_seg', d, ldn, None, 1, F_, Nt, Np, Simg)
             call('tvae_seg_sum', Simg, B, F_, dbc, 1.0, 0)
         else:
@@ -1227,20 +1317,22 @@ class DecoderFn(torch.autograd.Function):
             call('tvae_dec_in_bwd', d, ldn, xr.view(Nt, 2), Wc.contiguous(), F_, B, Np, gxr, Simg, dbc, dWc, part,
                  part.numel())
         dWl = dz = None
-        if has_l:
+        if Wl is not None:
             zd = Wl.shape[1]
             dWl = torch.empty(F_, zd, dtype=torch.float32, device=dev)
             dz = torch.empty(B, zd, dtype=torch.float32, device=dev)
             call('tvae_latent_bwd', Simg, Wl.contiguous(), z, dWl, dz, B, F_, zd)
-        if has_f:
+        if Wf is not None:
             Ff = Wf.shape[0]
             # h3 for the Fourier first layer's backward (round 4): both operands come from memory with known bounds -- the
             # features are cosines (<= 1), d is under its bound word (analytic behind a two-valued data gradient, else measured)
-            one = torch.ones(1, dtype=torch.float32, device=dev) if d_bnd is not None else None
-            dWc = _wgrad(d, feat, F_, Nt, Ff, a_amax=d_bnd, x_amax=one, ld=ldn)
+            d_bnd = bd.behind_two_val(hidden[0][0], vg['vg_wo']) if plan.four_bound == 'two_val' else \
+                bd.d_word(plan.four_bound, 0)
+            one = torch.ones(1, dtype=torch.float32, device=dev) if plan.four_bound else None
+            dWc = _wgrad(d, feat, F_, Nt, Ff, a_amax=d_bnd, x_amax=one, ld=ldn, nparts=plan.four_wgrad_parts)
             dfeat = torch.empty(Ff, ldn, dtype=torch.float32, device=dev)
             if rt.four_dgrad_x6:
-                p_f = 2 if d_bnd is not None else _p3()
+                p_f = plan.four_dgrad_parts
                 w3t = _split_weight(Wc, Ff, F_, True, 'x6_dense_wct', nparts=p_f)
                 with _timed('tvae_linear_dgrad_x6', p_f):
                     call('tvae_linear_dgrad_x6', w3t, d, None, None, dfeat, F_, Nt, Ff, ldn, ldn, ACT_NONE, LRELU_SLOPE,

@@ -466,7 +466,9 @@ def test_shape_validation_happens_before_any_launch():
 # arithmetics (x6 / h3 / bf16; 'h3' in h3 only) and the row padding there; in f32 none holds.  bench.py's decoders at their
 # bench batch, then one each of resid / tanh / 128 / 1024 hidden units.  The GPU tests' path sets follow from these:
 # virt_act -> dec.virt_act + dec.fuse_in, sign_bits -> dec.sign_bits + dec.virt_grad_2val, no_h -> dec.no_h +
-# dec.row_sums_in_dgrad (test_step_hot_widths_golden, test_decoder_kink_free_probe_at_bench_size).
+# dec.row_sums_in_dgrad (test_step_hot_widths_golden, test_decoder_kink_free_probe_at_bench_size).  The same rows name the
+# per-layer plans (DECODER_LAYERS: parts and bound source of every launch, ops.decoder_plan) and, as small stand-ins, the
+# launch sequences (DECODER_LAUNCHES) further down.
 _S64 = {'split', 'virt_act', 'fused_out', 'virt_grad', 'sign_bits', 'no_h'}
 DECODER_ROUTES = {
     'S64': ((256, 4096, 512, 1, 1, True, False, 0), _S64, 0),
@@ -499,6 +501,162 @@ def test_decoder_route_of_named_configurations(name, mode):
             want = {f: split and f in fields for f in ops.DecoderRoute._fields}
             want.update(ldn=B * Np + (pad if split else 0), h3=split and mode == 'h3' and 'split' in fields, infer=infer)
             assert ops.decoder_route(B, Np, F_, nh, n_out, act, resid, Ff, infer)._asdict() == want
+
+
+def _layer(p, x='', y=False, fused=False, h=True, bits=False, vg=False, two=False, fb=False, wp=None, wb='', wr=False,
+           dp=None, db='', dm=False, fi=False):
+    """One ops.DecoderLayer, written short: the defaults are a stored layer in parts `p` with no bound and no fusion."""
+    return dict(parts=p, x_bound=x, y_max=y, fused_out=fused, store_h=h, store_bits=bits, virt_grad=vg, two_val=two,
+                from_bits=fb, wgrad_parts=p if wp is None else wp, wgrad_bound=wb, wgrad_x_rows=wr,
+                dgrad_parts=p if dp is None else dp, d_bound=db, dgrad_max=dm, fuse_in=fi)
+
+
+def _no_bounds(p):
+    """The plan-wide fields where nothing runs h3: (first_parts, four_bound, four_wgrad_parts, four_dgrad_parts, chain,
+    h_words, top_bound, d_words)."""
+    return (p, '', p, p, False, False, False, False)
+
+
+_BITS = dict(vg=True, two=True, fb=True, fused=True, h=False, bits=True)        # last layer of S64 / S28 / S28F (no_h)
+_H3_MID = dict(wb='plain', wr=True, db='meas', dm=True)                         # backward of an h3 layer between stored tensors
+# name of DECODER_ROUTES -> arithmetic -> (hidden layers, plan-wide fields) of ops.decoder_plan in training; 'p': the x6 (p = 3)
+# and bf16 (p = 1) plans, which differ in nothing else; f32 has _layer(3) for every layer and _no_bounds(3).  In inference
+# only store_bits changes (False everywhere).
+DECODER_LAYERS = {
+    'S64': {'p': lambda p: ([_layer(p, 'virt', fi=True, **_BITS)], _no_bounds(p)),
+            'h3': ([_layer(2, 'virt', fi=True, **_BITS)], (2, '', 3, 3, False, False, False, False))},
+    'S28F': {'p': lambda p: ([_layer(p, **_BITS)], _no_bounds(p)),
+             'h3': ([_layer(2, 'rows', wb='two_val', wr=True, dm=True, **_BITS)],
+                    (2, 'two_val', 2, 2, True, False, False, True))},
+    'S128G': {'p': lambda p: ([_layer(p)] * 3, _no_bounds(p)),
+              'h3': ([_layer(2, 'rows', y=True, **_H3_MID), _layer(2, 'meas', y=True, **_H3_MID),
+                      _layer(2, 'meas', wb='plain', wr=True, db='top', dm=True)], (2, 'meas', 2, 2, True, True, True, True))},
+    # a residual first hidden layer runs three-part forward (its stored input has a bound, the launch does not take it)
+    'resid': {'p': lambda p: ([_layer(p), _layer(p), _layer(p, fused=True)], _no_bounds(p)),
+              'h3': ([_layer(3, y=True, wp=2, dp=2, **_H3_MID), _layer(2, 'meas', y=True, **_H3_MID),
+                      _layer(2, 'meas', fused=True, wb='plain', wr=True, db='top', dm=True)],
+                     (2, '', 3, 3, True, True, True, True))},
+    # tanh: implicit gradient in its general form, three-part in h3 too (the activation is stored: no bits)
+    'tanh': {'p': lambda p: ([_layer(p, 'virt', fused=True, vg=True, fi=True)], _no_bounds(p)),
+             'h3': ([_layer(2, 'virt', fused=True, vg=True, fi=True, wp=3, dp=3)], (2, '', 3, 3, False, False, False, False))},
+    'F128': {'p': lambda p: ([_layer(p)], _no_bounds(p)),
+             'h3': ([_layer(3)], (2, '', 3, 3, False, False, False, False))},       # (no split-pipe layer: nothing runs h3)
+    'F1024': {'p': lambda p: ([_layer(p), _layer(p, vg=True, two=True, bits=True)], _no_bounds(p)),
+              'h3': ([_layer(2, 'rows', y=True, **_H3_MID),
+                      _layer(2, 'meas', vg=True, two=True, bits=True, wb='two_val', wr=True, dm=True)],
+                     (2, '', 3, 3, True, True, False, True))},
+}
+DECODER_LAYERS['S28'] = DECODER_LAYERS['S64']            # (padded to 896 pixels: the same plan)
+
+
+@pytest.mark.parametrize('mode', ['f32', 'x6', 'h3', 'bf16'])
+@pytest.mark.parametrize('name', sorted(DECODER_ROUTES))
+def test_decoder_layers_of_named_configurations(name, mode):
+    """ops.decoder_plan -- parts and bound source of every DecoderFn launch, decided once from the route -- for the named
+    configurations in each arithmetic, in training and in inference (host only: no library, no GPU)."""
+    from tvae import ops
+    from tvae._lib import arithmetic
+    (B, Np, F_, nh, n_out, lrelu, resid, Ff), _, _ = DECODER_ROUTES[name]
+    act = ops.ACT_LRELU if lrelu else ops.ACT_TANH
+    if mode == 'f32':
+        layers, wide = [_layer(3)] * nh, _no_bounds(3)
+    elif mode == 'h3':
+        layers, wide = DECODER_LAYERS[name]['h3']
+    else:
+        layers, wide = DECODER_LAYERS[name]['p']({'x6': 3, 'bf16': 1}[mode])
+    with arithmetic(mode):
+        Np = ops.decoder_padded_pixels(Np, B, F_, nh, n_out, resid, Ff > 0, act) or Np
+        for infer in (False, True):
+            plan = ops.decoder_plan(ops.decoder_route(B, Np, F_, nh, n_out, act, resid, Ff, infer), nh, resid, Ff > 0)
+            assert [lp._asdict() for lp in plan.layers] == [dict(lp, store_bits=lp['store_bits'] and not infer) for lp in layers]
+            assert tuple(plan[1:]) == wide
+
+
+# (arithmetic, B, Np, hidden units, hidden layers, outputs, LeakyReLU, resid, Fourier features, zd, inference) -> entry points
+# of DecoderFn's forward + backward in order, `tvae_` dropped, and PARTS_LOG's (parts, MFMAs per block) lists of
+# linear_fwd_x6, linear_dgrad_x6, linear_wgrad_x6; small stand-ins of the DECODER_ROUTES rows with every route predicate on
+# the same side.  Recorded on the tree BEFORE decoder_plan existed (DecoderFn deciding inline from the tensors at hand).
+_S64_LIKE = (2, 128, 512, 1, 1, True, False, 0, 2, False)
+_S64_X6 = 'latent_bias dense_split3 linear_fwd_x6 rowdot_seg seg_sum linear_wgrad_x6 dense_split3 linear_dgrad_x6 ' \
+    'dec_in_total latent_bwd'
+_PLAIN_1 = 'latent_bias dec_l0_fwd linear_fwd coldot rowdot_seg seg_sum dec_out_bwd linear_wgrad linear_dgrad dec_in_bwd ' \
+    'latent_bwd'
+_S28F_X6 = 'fourier_fwd dense_split3 linear_fwd_x6 dense_split3 linear_fwd_x6 rowdot_seg seg_sum linear_wgrad_x6 ' \
+    'dense_split3 linear_dgrad_x6 rowdot_seg seg_sum latent_bwd linear_wgrad_x6 dense_split3 linear_dgrad_x6 fourier_bwd'
+_BWD_STORED = ' linear_wgrad_x6 rowdot_seg seg_sum dense_split2h linear_dgrad_x6'        # a hidden layer below the top one
+DECODER_LAUNCHES = {
+    ('f32',) + _S64_LIKE: (_PLAIN_1, ([], [], [])),
+    ('x6',) + _S64_LIKE: (_S64_X6, ([(3, 6)], [(3, 3)], [(3, 3)])),
+    ('h3',) + _S64_LIKE: (_S64_X6.replace('split3', 'split2h'), ([(2, 3)], [(2, 2)], [(2, 2)])),
+    ('bf16',) + _S64_LIKE: (_S64_X6, ([(1, 1)], [(1, 1)], [(1, 1)])),
+    ('x6', 2, 128, 512, 1, 1, True, False, 256, 2, False):                                        # S28F-like
+        (_S28F_X6, ([(3, 6), (3, 6)], [(3, 3), (3, 6)], [(3, 3), (3, 6)])),
+    ('h3', 2, 128, 512, 1, 1, True, False, 256, 2, False):
+        (_S28F_X6.replace('split3', 'split2h'), ([(2, 3), (2, 3)], [(2, 2), (2, 3)], [(2, 2), (2, 3)])),
+    ('h3', 1, 16384, 256, 3, 3, True, False, 256, 3, False):                                      # S128G-like (dec.ld_pad)
+        ('fourier_fwd' + 4 * ' dense_split2h linear_fwd_x6' + ' coldot rowdot_seg seg_sum dec_out_bwd linear_wgrad_x6 '
+         'dense_split2h linear_dgrad_x6' + 2 * _BWD_STORED + ' rowdot_seg seg_sum latent_bwd linear_wgrad_x6 dense_split2h '
+         'linear_dgrad_x6 fourier_bwd', ([(2, 3)] * 4, [(2, 3)] * 4, [(2, 3)] * 4)),
+    ('h3', 2, 128, 512, 3, 1, True, True, 0, 2, False):                                           # resid
+        ('latent_bias dec_l0_fwd dense_split3 linear_fwd_x6 dense_split2h linear_fwd_x6 dense_split2h linear_fwd_x6 '
+         'rowdot_seg seg_sum dec_out_bwd linear_wgrad_x6 dense_split2h linear_dgrad_x6' + 2 * _BWD_STORED +
+         ' dec_in_bwd latent_bwd', ([(3, 6), (2, 3), (2, 3)], [(2, 3)] * 3, [(2, 3)] * 3)),
+    ('h3', 2, 128, 512, 1, 1, False, False, 0, 2, False):                                         # tanh
+        ('latent_bias dense_split2h linear_fwd_x6 rowdot_seg seg_sum dec_out_bwd linear_wgrad_x6 dense_split3 '
+         'linear_dgrad_x6 dec_in_total latent_bwd', ([(2, 3)], [(3, 6)], [(3, 6)])),
+    ('h3', 2, 128, 1024, 2, 1, True, False, 0, 2, False):                                         # F1024
+        ('latent_bias dec_l0_fwd dense_split2h linear_fwd_x6 dense_split2h linear_fwd_x6 coldot rowdot_seg seg_sum '
+         'dec_out_bwd linear_wgrad_x6 dense_split2h linear_dgrad_x6' + _BWD_STORED + ' dec_in_bwd latent_bwd',
+         ([(2, 3), (2, 3)], [(2, 2), (2, 3)], [(2, 2), (2, 3)])),
+    ('h3', 2, 128, 128, 1, 1, True, False, 256, 2, False):         # F128 with Fourier: split pipe in its data gradient only
+        ('latent_bias fourier_fwd linear_fwd linear_fwd coldot rowdot_seg seg_sum dec_out_bwd linear_wgrad linear_dgrad '
+         'rowdot_seg seg_sum latent_bwd linear_wgrad dense_split3 linear_dgrad_x6 fourier_bwd', ([], [(3, 6)], [])),
+    ('h3', 2, 100, 512, 1, 1, True, False, 0, 2, False): (_PLAIN_1, ([], [], [])),                # Np = 100: plain first layer
+    ('h3',) + _S64_LIKE[:-1] + (True,): ('latent_bias dense_split2h linear_fwd_x6', ([(2, 3)], [], [])),      # inference
+    ('h3', 2, 128, 256, 2, 1, True, False, 0, 3, False):
+        ('latent_bias dense_split2h linear_fwd_x6 dense_split2h linear_fwd_x6 rowdot_seg seg_sum linear_wgrad_x6 '
+         'dense_split2h linear_dgrad_x6' + _BWD_STORED + ' dec_in_total latent_bwd',
+         ([(2, 3), (2, 3)], [(2, 2), (2, 3)], [(2, 2), (3, 6)])),
+}
+
+
+@pytest.mark.parametrize('row', sorted(DECODER_LAUNCHES), ids=lambda r: '-'.join(str(v) for v in r))
+def test_decoder_launches_of_named_configurations(row):
+    """The entry points DecoderFn launches, forward then backward, and the arithmetic of its split-pipe launches, for
+    stand-ins of the route table's rows: run on CPU tensors with `ops.call` recorded and `ops.query` stubbed
+    (profiles/tools/launch_trace.py; host only: no library, no GPU)."""
+    import importlib.util
+    from tvae import ops
+    spec = importlib.util.spec_from_file_location(
+        'launch_trace', os.path.join(ROOT, 'profiles', 'tools', 'launch_trace.py'))
+    lt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(lt)
+    mode, B, Np, F_, nh, n_out, lrelu, resid, Ff, zd, infer = row
+    rec = lt.trace_decoder(mode, B, Np, F_, nh, n_out, ops.ACT_LRELU if lrelu else ops.ACT_TANH, resid, Ff, zd, infer)
+    want, want_parts = DECODER_LAUNCHES[row]
+    assert lt.names(rec) == ['tvae_' + e for e in want.split()]
+    assert tuple(rec.parts.get('tvae_linear_%s_x6' % k, []) for k in ('fwd', 'dgrad', 'wgrad')) == want_parts
+
+
+def test_wgrad_two_parts_need_their_bounds():
+    """ops._wgrad takes its arithmetic from the caller: two parts without the bounds of the streamed operands raise on the
+    host, before any launch (host only: no library, no GPU)."""
+    import importlib.util
+    from tvae import ops
+    from tvae._lib import arithmetic
+    spec = importlib.util.spec_from_file_location(
+        'launch_trace', os.path.join(ROOT, 'profiles', 'tools', 'launch_trace.py'))
+    lt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(lt)
+    d, X, one = torch.zeros(256, 128), torch.zeros(256, 128), torch.ones(1)
+    with arithmetic('h3'), lt.traced() as rec:
+        for bounds in ({}, dict(a_amax=one), dict(x_amax=one)):
+            with pytest.raises(ValueError):
+                ops._wgrad(d, X, 256, 128, 256, nparts=2, **bounds)
+        assert rec.launches == []
+        ops._wgrad(d, X, 256, 128, 256, nparts=2, a_amax=one, x_amax=one)
+        ops._wgrad(d, X, 256, 128, 256)
+    assert lt.names(rec) == ['tvae_linear_wgrad_x6'] * 2 and rec.parts['tvae_linear_wgrad_x6'] == [(2, 3), (3, 6)]
 
 
 # (arithmetic, head rows, LeakyReLU, N % 32 == 0, conv1 left max |A1|) -> (tail, parts, h3, bits, wgrad) of ops.encoder_route
