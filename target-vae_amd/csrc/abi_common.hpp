@@ -72,6 +72,13 @@ static inline int pick_splits(int tiles, long K) {
     if (want < 1) want = 1;
     return (int)want;
 }
+// Mid-size reductions (latent_bwd, dec_in_total_*, part_total_s1, dft_dbias_rows, enc_tail_wgrad_total): their <true>
+// instances issue the loads of several terms of a sum together and then add them in the order of the one-load-at-a-time
+// loops (<false>, the kernels as they were: TVAE_MIDSIZE_ILP=0).  Read at every call, so one process can run both.
+static inline bool midsize_ilp() {
+    const char* e = getenv("TVAE_MIDSIZE_ILP");
+    return !(e && e[0] == '0');
+}
 static inline int panels_of(long N, int width) { return (int)((N + width - 1) / width); }
 
 static inline ConvGeom make_geom(int B, int Cin, int n, int ksz, int pad, int R) {

@@ -612,8 +612,12 @@ int tvae_conv1_wgrad_dft(const float* dpre, const float* at, float* dbank, float
     }
     if (dbias) {
         float* dbpart = ED + ((q.ed_floats + 3) & ~3L);           // M floats behind the transform tables (then the h3 cell tables)
-        hipLaunchKernelGGL(dft_dbias_rows_kernel, dim3(q.M), dim3(256), 0, st, (const float*)Sp, dbpart, q.Lh, q.NB, q.M,
-                           s16 ? 1 : 0);
+        if (midsize_ilp())
+            hipLaunchKernelGGL(dft_dbias_rows_kernel<true>, dim3(q.M), dim3(256), 0, st, (const float*)Sp, dbpart, q.Lh, q.NB, q.M,
+                               s16 ? 1 : 0);
+        else
+            hipLaunchKernelGGL(dft_dbias_rows_kernel<false>, dim3(q.M), dim3(256), 0, st, (const float*)Sp, dbpart, q.Lh, q.NB, q.M,
+                               s16 ? 1 : 0);
         TVAE_CHECK_LAUNCH();
         hipLaunchKernelGGL(dft_dbias_kernel, dim3((C + 63) / 64), dim3(64), 0, st, (const float*)dbpart, dbias, R, C);
         TVAE_CHECK_LAUNCH();

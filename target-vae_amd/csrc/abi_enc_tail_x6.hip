@@ -94,7 +94,12 @@ int tvae_enc_tail_wgrad_x6(const float* A1, long lda, const float* dheads, long 
                       (const uint4*)bits_h, Wh, ws, N, slope, amax_a1, (const float*)slots);
     });
     if (rc) return rc;
-    hipLaunchKernelGGL(enc_tail_wgrad_total_kernel, dim3(ET_C * ET_C / 64), dim3(256), 0, S(stream), (const float*)ws, grid, dW2);
+    if (midsize_ilp())
+        hipLaunchKernelGGL(enc_tail_wgrad_total_kernel<true>, dim3(ET_C * ET_C / 64), dim3(256), 0, S(stream), (const float*)ws, grid,
+                           dW2);
+    else
+        hipLaunchKernelGGL(enc_tail_wgrad_total_kernel<false>, dim3(ET_C * ET_C / 64), dim3(256), 0, S(stream), (const float*)ws, grid,
+                           dW2);
     TVAE_CHECK_LAUNCH();
     return 0;
 }
@@ -113,7 +118,12 @@ int tvae_enc_tail_wgrad_wide(const float* D, long ldd, int rows_d, const float* 
     const int rc = launch(enc_tail_wgrad_plain_kernel, dim3(grid), dim3(ET_THREADS), PW_LDS, S(stream), D, ldd, rows_d, A, lda, ws,
                           N, amax_d, amax_a);
     if (rc) return rc;
-    hipLaunchKernelGGL(enc_tail_wgrad_total_kernel, dim3(ET_C * ET_C / 64), dim3(256), 0, S(stream), (const float*)ws, grid, dW);
+    if (midsize_ilp())
+        hipLaunchKernelGGL(enc_tail_wgrad_total_kernel<true>, dim3(ET_C * ET_C / 64), dim3(256), 0, S(stream), (const float*)ws, grid,
+                           dW);
+    else
+        hipLaunchKernelGGL(enc_tail_wgrad_total_kernel<false>, dim3(ET_C * ET_C / 64), dim3(256), 0, S(stream), (const float*)ws, grid,
+                           dW);
     TVAE_CHECK_LAUNCH();
     return 0;
 }

@@ -210,8 +210,12 @@ int tvae_heads_bwd(const float* W, const float* dY, long ldy, const float* X, lo
     const long used = (long)np * C * (nh + 1), mv = (long)C * (nh + 1);
     if (np >= 4 * PT_GROUPS && mv % 4 == 0 && part_floats >= ((used + 3) & ~3L) + PT_GROUPS * mv && aligned16(part)) {
         float* partial = part + ((used + 3) & ~3L);
-        hipLaunchKernelGGL(part_total_s1_kernel, dim3(PT_GROUPS), dim3(256), 0, S(stream), (const float*)part, np, (int)(mv / 4),
-                           partial);
+        if (midsize_ilp())
+            hipLaunchKernelGGL(part_total_s1_kernel<true>, dim3(PT_GROUPS), dim3(256), 0, S(stream), (const float*)part, np,
+                               (int)(mv / 4), partial);
+        else
+            hipLaunchKernelGGL(part_total_s1_kernel<false>, dim3(PT_GROUPS), dim3(256), 0, S(stream), (const float*)part, np,
+                               (int)(mv / 4), partial);
         TVAE_CHECK_LAUNCH();
         hipLaunchKernelGGL(part_total_s2_kernel, dim3((unsigned)((mv + 255) / 256)), dim3(256), 0, S(stream),
                            (const float*)partial, C, nh + 1, tot);
@@ -252,6 +256,18 @@ static int head_chunks(int B, int RP, int zd, long part_floats, int per_chunk_fl
     return (RP + chunk - 1) / chunk;
 }
 
+// Register-resident route of the one-workgroup-per-image head (small_kernels.hpp: attn_head_*_reg_kernel): the smallest
+// instance with R*P <= NPT * 1024, 0 when there is none.  TVAE_HEAD_REG=0 restores the strided kernels; the switch is read at
+// every call, so one process can run both (tvae/ops.py: head_reg_route mirrors this for PATH_LOG).
+constexpr int HEAD_REG_MAX_NPT = 9;
+static int head_reg_npt(int RP) {
+    const char* e = getenv("TVAE_HEAD_REG");
+    if ((e && e[0] == '0') || RP < 1) return 0;
+    for (int npt : {1, 3, 5, HEAD_REG_MAX_NPT})
+        if (RP <= npt * HEAD_REG_THREADS) return npt;
+    return 0;
+}
+
 int tvae_attn_head_fwd(const float* heads, long ldh, const float* E, const float* eps_z, const float* eps_t,
                        const float* p_r, const float* off, const float* p_tr, const float* grid, int B, int R, int P,
                        int zd, float sigma_p, float theta_off_scale, float* attn, float* q, float* a, float* z,
@@ -271,7 +287,14 @@ int tvae_attn_head_fwd(const float* heads, long ldh, const float* E, const float
         TVAE_CHECK_LAUNCH();
         return 0;
     }
-    hipLaunchKernelGGL(attn_head_fwd_kernel, dim3(B), dim3(1024), 0, S(stream), hp, attn, q, a, z, theta, dx, kl);
+    switch (head_reg_npt(R * P)) {
+#define TVAE_HEAD_FWD_REG(NPT) \
+        case NPT: hipLaunchKernelGGL(attn_head_fwd_reg_kernel<NPT>, dim3(B), dim3(HEAD_REG_THREADS), 0, S(stream), hp, attn, q, a, \
+                                     z, theta, dx, kl); break;
+        TVAE_HEAD_FWD_REG(1) TVAE_HEAD_FWD_REG(3) TVAE_HEAD_FWD_REG(5) TVAE_HEAD_FWD_REG(9)
+#undef TVAE_HEAD_FWD_REG
+        default: hipLaunchKernelGGL(attn_head_fwd_kernel, dim3(B), dim3(1024), 0, S(stream), hp, attn, q, a, z, theta, dx, kl);
+    }
     TVAE_CHECK_LAUNCH();
     return 0;
 }
@@ -295,8 +318,15 @@ int tvae_attn_head_bwd(const float* heads, long ldh, const float* q, const float
         TVAE_CHECK_LAUNCH();
         return 0;
     }
-    hipLaunchKernelGGL(attn_head_bwd_kernel, dim3(B), dim3(1024), 0, S(stream), hp, q, a, gz, gth, gdx, gkl, g_attn,
-                       g_q, g_a, dheads);
+    switch (head_reg_npt(R * P)) {
+#define TVAE_HEAD_BWD_REG(NPT) \
+        case NPT: hipLaunchKernelGGL(attn_head_bwd_reg_kernel<NPT>, dim3(B), dim3(HEAD_REG_THREADS), 0, S(stream), hp, q, a, gz, \
+                                     gth, gdx, gkl, g_attn, g_q, g_a, dheads); break;
+        TVAE_HEAD_BWD_REG(1) TVAE_HEAD_BWD_REG(3) TVAE_HEAD_BWD_REG(5) TVAE_HEAD_BWD_REG(9)
+#undef TVAE_HEAD_BWD_REG
+        default: hipLaunchKernelGGL(attn_head_bwd_kernel, dim3(B), dim3(1024), 0, S(stream), hp, q, a, gz, gth, gdx, gkl,
+                                    g_attn, g_q, g_a, dheads);
+    }
     TVAE_CHECK_LAUNCH();
     return 0;
 }
@@ -368,7 +398,12 @@ int tvae_latent_bwd(const float* S_, const float* Wl, const float* z, float* dWl
                     tvae_stream_t stream) {
     const int tot = (F * zd > B * zd) ? F * zd : B * zd;
     if (tot <= 0) return 0;
-    hipLaunchKernelGGL(latent_bwd_kernel, dim3((tot + 63) / 64), dim3(1024), 0, S(stream), S_, Wl, z, dWl, dz, B, F, zd);
+    if (midsize_ilp())
+        hipLaunchKernelGGL(latent_bwd_kernel<true>, dim3((tot + 63) / 64), dim3(1024), 0, S(stream), S_, Wl, z, dWl, dz, B, F,
+                           zd);
+    else
+        hipLaunchKernelGGL(latent_bwd_kernel<false>, dim3((tot + 63) / 64), dim3(1024), 0, S(stream), S_, Wl, z, dWl, dz, B, F,
+                           zd);
     TVAE_CHECK_LAUNCH();
     return 0;
 }
@@ -444,10 +479,16 @@ int tvae_dec_in_total(float* part, int B, int cpi, int F, float* Simg, float* db
     // second stage of the fused first-layer backward: part[B*cpi panels][F][3] -> per-image sums, bias and weight grads.
     // part is CONSUMED: the first panel of every image is overwritten with the image's sums.
     if (B <= 0 || F <= 0 || cpi <= 0) return 0;
-    hipLaunchKernelGGL(dec_in_total_img_kernel, dim3(B), dim3(256), 0, S(stream), part, cpi, F, Simg);
+    const bool ilp = midsize_ilp();
+    if (ilp) hipLaunchKernelGGL(dec_in_total_img_kernel<true>, dim3(B), dim3(256), 0, S(stream), part, cpi, F, Simg);
+    else hipLaunchKernelGGL(dec_in_total_img_kernel<false>, dim3(B), dim3(256), 0, S(stream), part, cpi, F, Simg);
     TVAE_CHECK_LAUNCH();
-    hipLaunchKernelGGL(dec_in_total_sum_kernel, dim3((3 * F + 63) / 64), dim3(256), 0, S(stream), (const float*)part, B, cpi, F,
-                       dbc, dWc);
+    if (ilp)
+        hipLaunchKernelGGL(dec_in_total_sum_kernel<true>, dim3((3 * F + 63) / 64), dim3(256), 0, S(stream), (const float*)part, B,
+                           cpi, F, dbc, dWc);
+    else
+        hipLaunchKernelGGL(dec_in_total_sum_kernel<false>, dim3((3 * F + 63) / 64), dim3(256), 0, S(stream), (const float*)part, B,
+                           cpi, F, dbc, dWc);
     TVAE_CHECK_LAUNCH();
     return 0;
 }

@@ -169,11 +169,30 @@ static __global__ __launch_bounds__(ET_THREADS, 2) void enc_tail_wgrad_plain_ker
 }
 
 // dW2[e] = sum over workgroups of slabs[g][e], in workgroup order
+// ILP: two rounds of eight slabs in flight per thread; each of the eight sums still takes its slabs in order.
+template <bool ILP>
 static __global__ void enc_tail_wgrad_total_kernel(const float* __restrict__ slabs, int nslab, float* __restrict__ dW2) {
     // thread (element e, slab group q < 4): eight loads in flight per thread, fixed summation order
     __shared__ float sm[4][64];
     const int e = blockIdx.x * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
     float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if constexpr (ILP) {
+        for (int g0 = 8 * q; g0 < nslab; g0 += 64) {
+            float v[2][8];
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int g = g0 + 32 * r + u;
+                    v[r][u] = slabs[(long)(g < nslab ? g : g0) * ET_C * ET_C + e];
+                }
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int u = 0; u < 8; ++u)
+                    if (g0 + 32 * r + u < nslab) s[u] += v[r][u];
+        }
+    } else
     for (int g0 = 8 * q; g0 < nslab; g0 += 32) {
 #pragma unroll
         for (int u = 0; u < 8; ++u)

@@ -62,7 +62,10 @@ static __global__ void part_total_kernel(const float* __restrict__ part, int npa
 // floats: 41 us for 4 356 panels of 128 x 8).  Stage 1: workgroup g adds its contiguous range of panels, every thread a
 // float4 of the [M][NV] block (consecutive threads, consecutive addresses), into partial[g][M NV]; stage 2 adds the
 // PT_GROUPS partials in order and transposes to out[v M + m].  Deterministic (fixed ranges, fixed order).
+// ILP: eight panels in flight instead of two (a group walks 69 panels at the 64x64 shape: 35 dependent round trips, 19 us);
+// a and b still take the even and the odd panels of the range in order.
 constexpr int PT_GROUPS = 64;
+template <bool ILP>
 static __global__ __launch_bounds__(256) void part_total_s1_kernel(const float* __restrict__ part, int npanels, int MV4,
                                                                   float* __restrict__ partial) {
     const float4* p4 = reinterpret_cast<const float4*>(part);
@@ -71,6 +74,18 @@ static __global__ __launch_bounds__(256) void part_total_s1_kernel(const float* 
     for (int idx = threadIdx.x; idx < MV4; idx += 256) {
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = make_float4(0.f, 0.f, 0.f, 0.f);
         int p = pb;
+        if constexpr (ILP) {
+            for (; p + 7 < pe; p += 8) {
+                float4 w[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) w[u] = p4[(long)(p + u) * MV4 + idx];
+#pragma unroll
+                for (int u = 0; u < 8; u += 2) {
+                    a.x += w[u].x; a.y += w[u].y; a.z += w[u].z; a.w += w[u].w;
+                    b.x += w[u + 1].x; b.y += w[u + 1].y; b.z += w[u + 1].z; b.w += w[u + 1].w;
+                }
+            }
+        }
         for (; p + 1 < pe; p += 2) {                     // two loads in flight; (a + b) at the end keeps a fixed order
             const float4 u = p4[(long)p * MV4 + idx], v = p4[(long)(p + 1) * MV4 + idx];
             a.x += u.x; a.y += u.y; a.z += u.z; a.w += u.w;
@@ -231,9 +246,42 @@ static __global__ __launch_bounds__(256) void dec_in_bwd_kernel(const float* __r
 // Two coalesced stages (round 3; the single-stage form -- one workgroup per feature reading 12-byte pieces 6 KB apart -- took
 // 90 us for 50 MB): (1) one workgroup per image adds its cpi panels element-wise, every read a contiguous 3 F floats, leaves
 // the image's sums IN ITS FIRST PANEL (part is consumed) and writes Simg; (2) the sums over the images, 3 F outputs.
+// ILP: a thread's elements six at a time, the loads of all of them ahead of the stores (the store to base[e] kept the next
+// element's loads waiting: one round trip per element, 23 us for 6 MB); every element still adds its panels in panel order.
+template <bool ILP>
 static __global__ void dec_in_total_img_kernel(float* __restrict__ part, int cpi, int F, float* __restrict__ Simg) {
     const int b = blockIdx.x, n3 = 3 * F;
     float* base = part + (long)b * cpi * n3;
+    if constexpr (ILP) {
+        constexpr int EU = 6;
+        for (int e0 = threadIdx.x; e0 < n3; e0 += EU * blockDim.x) {
+            float s[EU];
+            int ec[EU];
+#pragma unroll
+            for (int u = 0; u < EU; ++u) {
+                s[u] = 0.f;
+                ec[u] = e0 + u * (int)blockDim.x < n3 ? e0 + u * (int)blockDim.x : e0;      // (past the end: a copy of e0, dropped)
+            }
+#pragma unroll 4
+            for (int c = 0; c < cpi; ++c) {
+                float v[EU];
+#pragma unroll
+                for (int u = 0; u < EU; ++u) v[u] = base[(long)c * n3 + ec[u]];
+#pragma unroll
+                for (int u = 0; u < EU; ++u) s[u] += v[u];
+            }
+#pragma unroll
+            for (int u = 0; u < EU; ++u) {
+                const int e = e0 + u * (int)blockDim.x;
+                if (e < n3) {
+                    base[e] = s[u];
+                    const int f = e / 3;
+                    if (e - 3 * f == 0) Simg[(long)b * F + f] = s[u];
+                }
+            }
+        }
+        return;
+    }
     for (int e = threadIdx.x; e < n3; e += blockDim.x) {
         float s = 0.f;
 #pragma unroll 4
@@ -243,11 +291,25 @@ static __global__ void dec_in_total_img_kernel(float* __restrict__ part, int cpi
         if (e - 3 * f == 0) Simg[(long)b * F + f] = s;
     }
 }
+// ILP: sixteen images of a thread's 64 in flight, added in image order.
+template <bool ILP>
 static __global__ void dec_in_total_sum_kernel(const float* __restrict__ part, int B, int cpi, int F, float* __restrict__ dbc,
                                                float* __restrict__ dWc) {
     __shared__ float sm[4][64];
     const int n3 = 3 * F, e = blockIdx.x * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
     float s = 0.f;
+    if constexpr (ILP) {
+        constexpr int U = 16;
+        if (e < n3)
+            for (int b0 = q; b0 < B; b0 += 4 * U) {
+                float v[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) v[u] = part[(long)(b0 + 4 * u < B ? b0 + 4 * u : b0) * cpi * n3 + e];
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (b0 + 4 * u < B) s += v[u];
+            }
+    } else
     if (e < n3)
         for (int b = q; b < B; b += 4) s += part[(long)b * cpi * n3 + e];
     sm[q][threadIdx.x & 63] = s;

@@ -255,6 +255,9 @@ static __global__ void latent_bias_kernel(const float* __restrict__ Wl, const fl
 // From S[img][f] = sum_{pix in img} dpre0[f][pix]:  dWl[f][d] = sum_img S*z,  dz[img][d] = sum_f Wl[f][d]*S
 // Block = 64 outputs x 16 reduction slices (the sums run over the batch resp. the features: a thread per output walking
 // all of them was a 128 us latency chain); slice sums are added in slice order.
+// ILP: the loads of 16 terms of a slice in flight, then its fused multiply-adds in the same order (the plain loop compiles to
+// one pair of loads per trip, 48 dependent round trips at B = 256, F = 512: 22 us).
+template <bool ILP>
 static __global__ __launch_bounds__(1024) void latent_bwd_kernel(const float* __restrict__ S, const float* __restrict__ Wl,
                                                                  const float* __restrict__ z, float* __restrict__ dWl,
                                                                  float* __restrict__ dz, int B, int F, int zd) {
@@ -262,13 +265,47 @@ static __global__ __launch_bounds__(1024) void latent_bwd_kernel(const float* __
     const int o = threadIdx.x & 63, sl = threadIdx.x >> 6;
     const int i = blockIdx.x * 64 + o;
     float s0 = 0.f, s1 = 0.f;
-    if (i < F * zd) {
-        const int f = i / zd, d = i - f * zd;
-        for (int b = sl; b < B; b += 16) s0 += S[(long)b * F + f] * z[b * zd + d];
-    }
-    if (i < B * zd) {
-        const int b = i / zd, d = i - b * zd;
-        for (int f = sl; f < F; f += 16) s1 += Wl[f * zd + d] * S[(long)b * F + f];
+    if constexpr (ILP) {
+        constexpr int U = 16;
+        if (i < F * zd) {
+            const int f = i / zd, d = i - f * zd;
+            for (int b0 = sl; b0 < B; b0 += 16 * U) {
+                float sv[U], zv[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int b = b0 + 16 * u < B ? b0 + 16 * u : b0;
+                    sv[u] = S[(long)b * F + f];
+                    zv[u] = z[b * zd + d];
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (b0 + 16 * u < B) s0 = __fmaf_rn(sv[u], zv[u], s0);
+            }
+        }
+        if (i < B * zd) {
+            const int b = i / zd, d = i - b * zd;
+            for (int f0 = sl; f0 < F; f0 += 16 * U) {
+                float wv[U], sv[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int f = f0 + 16 * u < F ? f0 + 16 * u : f0;
+                    wv[u] = Wl[f * zd + d];
+                    sv[u] = S[(long)b * F + f];
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (f0 + 16 * u < F) s1 = __fmaf_rn(wv[u], sv[u], s1);
+            }
+        }
+    } else {
+        if (i < F * zd) {
+            const int f = i / zd, d = i - f * zd;
+            for (int b = sl; b < B; b += 16) s0 += S[(long)b * F + f] * z[b * zd + d];
+        }
+        if (i < B * zd) {
+            const int b = i / zd, d = i - b * zd;
+            for (int f = sl; f < F; f += 16) s1 += Wl[f * zd + d] * S[(long)b * F + f];
+        }
     }
     part[0][sl][o] = s0;
     part[1][sl][o] = s1;
@@ -877,6 +914,354 @@ static __global__ void attn_head_bwd_b_kernel(HeadParams hp, int G, int chunk, c
     for (int gg = 0; gg < G; ++gg) { sa += part[2 * (b * G + gg)]; sq += part[2 * (b * G + gg) + 1]; }
     float dummy[2] = {0.f, 0.f};
     head_bwd_pass<8>(hp, b, (long)b * RP, j0, j1, 1, sa, sq, q, a, gz, gth, gdx, gkl, g_attn, g_q, g_a, dheads, dummy);
+}
+
+// ---- register-resident head: one 1024-thread workgroup per image with R*P <= NPT * 1024 (28x28: 2 312 / 4 624, 64x64: 8 712).
+// A thread owns the positions threadIdx.x + 1024 i, i < NPT -- the assignment of the strided loops above, so every per-thread
+// partial sum adds the same terms in the same order and every expression below is the one of head_p1 .. head_p4g /
+// head_bwd_pass: bitwise the same results.  What those loops wrote to attn / q / a and read back in the next sweep, and what
+// they evaluated again per sweep -- logf(E) three times, the Gumbel expf twice, expf(q) once per pooled quantity, j / P by a
+// run-time division in three sweeps, and the whole backward position twice -- stays in registers and is computed once; the
+// loads of a sweep are issued together ahead of its arithmetic.  Slots past R*P load position 0 and take no part in any sum
+// or store.  TVAE_HEAD_REG=0 restores the kernels above (abi_small.hip).
+constexpr int HEAD_REG_THREADS = 1024;
+// (rotation, grid cell) of the positions threadIdx.x + 1024 i by stepping: one division per sweep instead of one per position
+struct HeadStep {
+    int r, h, dr, dh, P;
+    __device__ __forceinline__ explicit HeadStep(int P_) : P(P_) {
+        dr = HEAD_REG_THREADS / P; dh = HEAD_REG_THREADS - dr * P;
+        r = (int)threadIdx.x / P; h = (int)threadIdx.x - r * P;
+    }
+    __device__ __forceinline__ void next() {
+        r += dr; h += dh;
+        if (h >= P) { h -= P; ++r; }
+    }
+};
+
+template <int NPT>
+static __global__ void __launch_bounds__(HEAD_REG_THREADS)
+attn_head_fwd_reg_kernel(HeadParams hp, float* __restrict__ attn, float* __restrict__ q, float* __restrict__ a,
+                         float* __restrict__ zs, float* __restrict__ th, float* __restrict__ dxo, float* __restrict__ kl) {
+    constexpr int CG = 2;               // latent dimensions per sweep: 4 NPT loads in flight, z_dim is 2 at these shapes
+    __shared__ float sm[3 * CG * 16];
+    const int b = blockIdx.x;
+    const int RP = hp.R * hp.P;
+    const long base = (long)b * RP;
+    const int tid = threadIdx.x;
+    float l[NPT], d[NPT];               // logit + prior, and the same minus logf(E)
+    float m1 = -INFINITY, m2 = -INFINITY;
+    {
+        float lr[NPT], ev[NPT], pr[NPT];
+        HeadStep st(hp.P);
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            const bool ok = tid + HEAD_REG_THREADS * i < RP;
+            const int j = ok ? tid + HEAD_REG_THREADS * i : 0;
+            lr[i] = hp.heads[base + j];
+            ev[i] = hp.E[base + j];
+            pr[i] = hp.p_r[ok ? st.r : 0];
+            st.next();
+        }
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            l[i] = lr[i] + pr[i];
+            d[i] = l[i] - logf(ev[i]);
+            if (tid + HEAD_REG_THREADS * i < RP) {
+                attn[base + tid + HEAD_REG_THREADS * i] = l[i];
+                m1 = fmaxf(m1, l[i]);
+                m2 = fmaxf(m2, d[i]);
+            }
+        }
+    }
+    m1 = block_max(m1, sm);
+    m2 = block_max(m2, sm);
+    float s[2] = {0.f, 0.f};
+    float e2[NPT];                      // the Gumbel-softmax numerator
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+        const float e1 = expf(l[i] - m1);
+        e2[i] = expf(d[i] - m2);
+        if (tid + HEAD_REG_THREADS * i < RP) { s[0] += e1; s[1] += e2[i]; }
+    }
+    block_sum<2>(s, sm);
+    const float lse = m1 + logf(s[0]);
+    const float inv2 = 1.f / s[1];
+    float aa[NPT], eq[NPT];             // a and expf(q)
+    float t[3] = {0.f, 0.f, 0.f};
+    {
+        float g0[NPT], g1[NPT], pt[NPT];
+        HeadStep st(hp.P);
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            const bool ok = tid + HEAD_REG_THREADS * i < RP;
+            const int hw = ok ? st.h : 0;
+            g0[i] = hp.grid[2 * hw];
+            g1[i] = hp.grid[2 * hw + 1];
+            pt[i] = hp.p_tr[ok ? tid + HEAD_REG_THREADS * i : 0];
+            st.next();
+        }
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            const float qq = l[i] - lse;
+            aa[i] = e2[i] * inv2;
+            eq[i] = expf(qq);
+            if (tid + HEAD_REG_THREADS * i < RP) {
+                q[base + tid + HEAD_REG_THREADS * i] = qq;
+                a[base + tid + HEAD_REG_THREADS * i] = aa[i];
+                t[0] += aa[i] * g0[i];
+                t[1] += aa[i] * g1[i];
+                t[2] += eq[i] * (qq - pt[i]);
+            }
+        }
+    }
+    block_sum<3>(t, sm);
+    float klsum = t[2];
+    if (tid == 0) { dxo[2 * b] = t[0]; dxo[2 * b + 1] = t[1]; }
+    {   // theta: head_p4 with c = -1
+        const float* mu_p = hp.heads + 1 * hp.ldh + base;
+        const float* ls_p = hp.heads + 2 * hp.ldh + base;
+        float mus[NPT], lss[NPT], os[NPT];
+        HeadStep st(hp.P);
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            const bool ok = tid + HEAD_REG_THREADS * i < RP;
+            const int j = ok ? tid + HEAD_REG_THREADS * i : 0;
+            mus[i] = mu_p[j];
+            lss[i] = ls_p[j];
+            os[i] = hp.off[ok ? st.r : 0];
+            st.next();
+        }
+        float u[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            if (tid + HEAD_REG_THREADS * i < RP) {
+                float mu = mus[i];
+                float sd = expf(lss[i]) + EPS_STD;
+                const float o = os[i];
+                mu += hp.theta_off_scale * o;
+                u[0] += aa[i] * mu;
+                u[1] += aa[i] * sd;
+                if (eq[i] == 0.f) { mu = 0.f; sd = 1.f; }
+                const float vr = (sd / hp.sigma_p) * (sd / hp.sigma_p);
+                const float t1 = ((mu - o) / hp.sigma_p) * ((mu - o) / hp.sigma_p);
+                const float klv = 0.5f * (vr + t1 - 1.f - logf(vr));
+                u[2] += eq[i] * klv;
+            }
+        }
+        block_sum<3>(u, sm);
+        klsum += u[2];
+        if (tid == 0) th[b] = u[1] * hp.eps_t[b] + u[0];
+    }
+    for (int c0 = 0; c0 < hp.zd; c0 += CG) {            // head_p4g, CG dimensions at a time
+        const float* mu_p[CG];
+        const float* ls_p[CG];
+#pragma unroll
+        for (int k = 0; k < CG; ++k) {
+            const int c = min(c0 + k, hp.zd - 1);
+            mu_p[k] = hp.heads + (long)(3 + c) * hp.ldh + base;
+            ls_p[k] = hp.heads + (long)(3 + hp.zd + c) * hp.ldh + base;
+        }
+        float mus[NPT][CG], lss[NPT][CG];
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            const int j = tid + HEAD_REG_THREADS * i < RP ? tid + HEAD_REG_THREADS * i : 0;
+#pragma unroll
+            for (int k = 0; k < CG; ++k) { mus[i][k] = mu_p[k][j]; lss[i][k] = ls_p[k][j]; }
+        }
+        float u[3 * CG];
+#pragma unroll
+        for (int k = 0; k < 3 * CG; ++k) u[k] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPT; ++i) {
+            if (tid + HEAD_REG_THREADS * i < RP) {
+#pragma unroll
+                for (int k = 0; k < CG; ++k) {
+                    float m = mus[i][k];
+                    float sd = expf(lss[i][k]) + EPS_STD;
+                    u[3 * k] += aa[i] * m;
+                    u[3 * k + 1] += aa[i] * sd;
+                    if (eq[i] == 0.f) { m = 0.f; sd = 1.f; }
+                    u[3 * k + 2] += eq[i] * (0.5f * (sd * sd + m * m - 1.f - logf(sd * sd)));
+                }
+            }
+        }
+        block_sum<3 * CG>(u, sm);
+#pragma unroll
+        for (int k = 0; k < CG; ++k) {
+            const int c = c0 + k;
+            if (c < hp.zd) {                             // (dimension by dimension, in order)
+                klsum += u[3 * k + 2];
+                if (tid == 0) zs[b * hp.zd + c] = u[3 * k + 1] * hp.eps_z[b * hp.zd + c] + u[3 * k];
+            }
+        }
+    }
+    if (tid == 0) kl[b] = klsum;
+}
+
+// x + y that stays an add: never contracted with a product that feeds it (__fadd_rn is a plain, contractable `+` here)
+__device__ __forceinline__ float add_unfused(float x, float y) {
+#pragma clang fp contract(off)
+    return x + y;
+}
+
+// Backward, one evaluation per position: the head-row gradients 1 .. 2 + 2 zd do not depend on (sum a*da, sum dq) and are
+// written at once; (a, da, dq, expf(q)) stay in registers across the one block_sum and give row 0.  Positions are handled
+// PB at a time, all loads of such a group ahead of its stores (`dheads` and `hp.heads` may alias as far as the compiler knows).
+template <int NPT>
+static __global__ void __launch_bounds__(HEAD_REG_THREADS)
+attn_head_bwd_reg_kernel(HeadParams hp, const float* __restrict__ q, const float* __restrict__ a,
+                         const float* __restrict__ gz, const float* __restrict__ gth, const float* __restrict__ gdx,
+                         const float* __restrict__ gkl, const float* __restrict__ g_attn, const float* __restrict__ g_q,
+                         const float* __restrict__ g_a, float* __restrict__ dheads) {
+    // PB = 2: 116 registers at NPT = 9 (3 and 4 spill: a 1024-thread workgroup leaves a wave 128)
+    constexpr int HEAD_BD = 2, PB = 2;
+    __shared__ float sm[2 * 16];
+    const int b = blockIdx.x;
+    const int RP = hp.R * hp.P;
+    const long base = (long)b * RP;
+    const int tid = threadIdx.x;
+    const float w = gkl[b];
+    const float gt = gth[b];
+    const float et = hp.eps_t[b];
+    const float gd0 = gdx[2 * b], gd1 = gdx[2 * b + 1];
+    const float isp2 = 1.f / (hp.sigma_p * hp.sigma_p);
+    // per-image row pointers (uniform) indexed by the 32-bit position: scalar base + one offset register per position
+    const float* ab = a + base;
+    const float* qb = q + base;
+    const float* tmu_p = hp.heads + 1 * hp.ldh + base;
+    const float* tls_p = hp.heads + 2 * hp.ldh + base;
+    float* dl_p = dheads + base;
+    float* dtmu_p = dheads + 1 * hp.ldh + base;
+    float* dtls_p = dheads + 2 * hp.ldh + base;
+    float kaa[NPT], kda[NPT], kdq[NPT], keq[NPT];
+    float acc[2] = {0.f, 0.f};
+    HeadStep st(hp.P);
+#pragma unroll
+    for (int i0 = 0; i0 < NPT; i0 += PB) {
+        float aa[PB], qq[PB], o[PB], tmu_raw[PB], tls[PB], gr0[PB], gr1[PB], ptr[PB], ga[PB], gq[PB];
+        float zmu[PB][HEAD_BD], zls[PB][HEAD_BD];
+#pragma unroll
+        for (int p = 0; p < PB; ++p) {
+            if (i0 + p < NPT) {
+                const bool ok = tid + HEAD_REG_THREADS * (i0 + p) < RP;
+                const int j = ok ? tid + HEAD_REG_THREADS * (i0 + p) : 0;
+                const int hw = ok ? st.h : 0;
+                aa[p] = ab[j];
+                qq[p] = qb[j];
+                o[p] = hp.off[ok ? st.r : 0];
+                tmu_raw[p] = tmu_p[j];
+                tls[p] = tls_p[j];
+                gr0[p] = hp.grid[2 * hw];
+                gr1[p] = hp.grid[2 * hw + 1];
+                ptr[p] = hp.p_tr[j];
+                ga[p] = g_a ? g_a[base + j] : 0.f;
+                gq[p] = g_q ? g_q[base + j] : 0.f;
+                if (hp.zd > 0) {
+#pragma unroll
+                    for (int k = 0; k < HEAD_BD; ++k) {
+                        const int dd = min(k, hp.zd - 1);
+                        zmu[p][k] = (hp.heads + (long)(3 + dd) * hp.ldh + base)[j];
+                        zls[p][k] = (hp.heads + (long)(3 + hp.zd + dd) * hp.ldh + base)[j];
+                    }
+                }
+                st.next();
+            }
+        }
+        float eq[PB], da[PB], klsum[PB];
+        bool dead[PB];
+#pragma unroll
+        for (int p = 0; p < PB; ++p) {
+            if (i0 + p < NPT) {
+                const int j = tid + HEAD_REG_THREADS * (i0 + p);
+                eq[p] = expf(qq[p]);
+                dead[p] = (eq[p] == 0.f);
+                // theta
+                const float tmu = tmu_raw[p] + hp.theta_off_scale * o[p];
+                const float tex = expf(tls[p]);
+                const float tsd = tex + EPS_STD;
+                da[p] = gt * (tmu + et * tsd) + gd0 * gr0[p] + gd1 * gr1[p];
+                {
+                    const float mu = dead[p] ? 0.f : tmu, sd = dead[p] ? 1.f : tsd;
+                    const float vr = (sd / hp.sigma_p) * (sd / hp.sigma_p);
+                    const float t1 = ((mu - o[p]) / hp.sigma_p) * ((mu - o[p]) / hp.sigma_p);
+                    klsum[p] = 0.5f * (vr + t1 - 1.f - logf(vr));
+                }
+                if (j < RP) {
+                    float dmu = aa[p] * gt, dsd = aa[p] * gt * et;
+                    if (!dead[p]) { dmu += w * eq[p] * (tmu - o[p]) * isp2; dsd += w * eq[p] * (tsd * isp2 - 1.f / tsd); }
+                    dtmu_p[j] = dmu;
+                    dtls_p[j] = dsd * tex;
+                }
+            }
+        }
+        for (int d0 = 0; d0 < hp.zd; d0 += HEAD_BD) {
+            if (d0 > 0) {
+#pragma unroll
+                for (int p = 0; p < PB; ++p) {
+                    if (i0 + p < NPT) {
+                        const int j = tid + HEAD_REG_THREADS * (i0 + p) < RP ? tid + HEAD_REG_THREADS * (i0 + p) : 0;
+#pragma unroll
+                        for (int k = 0; k < HEAD_BD; ++k) {
+                            const int dd = min(d0 + k, hp.zd - 1);
+                            zmu[p][k] = (hp.heads + (long)(3 + dd) * hp.ldh + base)[j];
+                            zls[p][k] = (hp.heads + (long)(3 + hp.zd + dd) * hp.ldh + base)[j];
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int p = 0; p < PB; ++p) {
+                if (i0 + p < NPT) {
+                    const int j = tid + HEAD_REG_THREADS * (i0 + p);
+#pragma unroll
+                    for (int k = 0; k < HEAD_BD; ++k) {
+                        const int dd = d0 + k;
+                        if (dd < hp.zd) {
+                            const float zm = zmu[p][k];
+                            const float zex = expf(zls[p][k]);
+                            const float zsd = zex + EPS_STD;
+                            const float g = gz[b * hp.zd + dd], ez = hp.eps_z[b * hp.zd + dd];
+                            da[p] += g * (zm + ez * zsd);
+                            const float mu = dead[p] ? 0.f : zm, sd = dead[p] ? 1.f : zsd;
+                            klsum[p] += 0.5f * (sd * sd + mu * mu - 1.f - logf(sd * sd));
+                            if (j < RP) {
+                                float dmu = aa[p] * g, dsd = aa[p] * g * ez;
+                                if (!dead[p]) { dmu += w * eq[p] * zm; dsd += w * eq[p] * (zsd - 1.f / zsd); }
+                                (dheads + (long)(3 + dd) * hp.ldh + base)[j] = dmu;
+                                (dheads + (long)(3 + hp.zd + dd) * hp.ldh + base)[j] = dsd * zex;
+                            }
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < PB; ++p) {
+            if (i0 + p < NPT) {
+                // (the optional upstream terms as adds of their own, as head_bwd_pass's branches compile: left to the compiler,
+                // dq + g_q contracts into the product before it here)
+                if (g_a) da[p] = add_unfused(da[p], ga[p]);
+                float dq = w * eq[p] * (qq[p] - ptr[p] + 1.f + klsum[p]);
+                if (g_q) dq = add_unfused(dq, gq[p]);
+                if (tid + HEAD_REG_THREADS * (i0 + p) < RP) {
+                    acc[0] += aa[p] * da[p];
+                    acc[1] += dq;
+                }
+                kaa[i0 + p] = aa[p]; kda[i0 + p] = da[p]; kdq[i0 + p] = dq; keq[i0 + p] = eq[p];
+            }
+        }
+    }
+    block_sum<2>(acc, sm);
+    const float sa = acc[0], sq = acc[1];
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+        const int j = tid + HEAD_REG_THREADS * i;
+        if (j < RP) {
+            float dl = kaa[i] * (kda[i] - sa) + kdq[i] - keq[i] * sq;
+            if (g_attn) dl = add_unfused(dl, g_attn[base + j]);
+            dl_p[j] = dl;
+        }
+    }
 }
 
 

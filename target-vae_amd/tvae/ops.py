@@ -803,6 +803,16 @@ class HeadTables:
         self.theta_off_scale = 1.0 if rot_refinement else 0.0
 
 
+HEAD_REG_MAX = 9 * 1024
+
+
+def head_reg_route(RP: int) -> bool:
+    """Whether tvae_attn_head_fwd / _bwd run their register-resident kernels (csrc/abi_small.hip: head_reg_npt, the rule
+    this restates for PATH_LOG): at most 9 positions for each of the 1024 threads of an image, TVAE_HEAD_REG=0 restores the
+    strided kernels.  Read at every call, as the library does."""
+    return 1 <= RP <= HEAD_REG_MAX and not os.environ.get('TVAE_HEAD_REG', '1').startswith('0')
+
+
 class HeadFn(torch.autograd.Function):
     """Prior add + log-softmax + Gumbel-softmax (src/models.py:382-388) fused with expected-value pooling,
     reparameterised sampling, translation expectation and the KL block (train_mnist.py:192-231,242-282).
@@ -825,6 +835,8 @@ class HeadFn(torch.autograd.Function):
         heads = heads.contiguous()
         E, eps_z, eps_t = E.contiguous(), eps_z.contiguous(), eps_t.contiguous()
         part = _scratch(dev, 'head_part', 1024 * (7 + 3 * (zd + 1)))     # chunk partials (few images, many positions)
+        if head_reg_route(RP):
+            _note('head.reg')
         call('tvae_attn_head_fwd', heads, heads.shape[1], E, eps_z, eps_t, tb.p_r, tb.off, tb.p_tr, tb.grid, B, tb.R,
              tb.P, zd, tb.sigma_p, tb.theta_off_scale, attn, q, a, z, th, dx, kl, part, part.numel())
         ctx.save_for_backward(heads, q, a, eps_z, eps_t)
