@@ -1,6 +1,7 @@
 """Register-resident attention head (tvae_attn_head_fwd / _bwd with R*P <= 9 * 1024: csrc/small_kernels.hpp,
 attn_head_*_reg_kernel) against the strided kernels it replaces -- BITWISE, in one process, the route switched through
-TVAE_HEAD_REG -- and against the float64 restatement of tests/test_hip_primitives.py::test_attn_head at that test's tolerances.
+TVAE_HEAD_REG -- and against the fp32 oracle restatement of tests/test_hip_primitives.py::test_attn_head (_head_reference: the
+oracle's posterior_pool_kl casts to float32) and the float64 one of tests/head_ref.py, both at that test's tolerances.
 The calls go through ops.HeadFn (the module API: seven outputs, three of them with optional upstream gradients).
 
 Mid-size reductions with several loads in flight (TVAE_MIDSIZE_ILP: latent_bwd, dec_in_total_img / _sum, part_total_s1,
@@ -135,7 +136,7 @@ def test_attn_head_reg(R, Ho, zd, refine):
     assert RP <= NPT_MAX * 1024
     tb = ops.HeadTables(R, Ho, SPACING, refine, math.pi, False, dev())
     hd, E, eps_z, eps_t, res = _compare_routes(tb, RP, zd, True)
-    # float64, with all seven upstream gradients (tolerances of test_attn_head)
+    # the fp32 oracle, with all seven upstream gradients (tolerances of test_attn_head)
     got, dh, ups = res[True]
     hr = hd.clone().requires_grad_(True)
     ref = _head_reference(hr, E, eps_z, eps_t, R, Ho, zd, refine, math.pi, False, SPACING)
@@ -143,6 +144,13 @@ def test_attn_head_reg(R, Ho, zd, refine):
         assert rel_err(g_.reshape(-1), r_.reshape(-1)) < 5e-5, nm
     sum((r_ * u.to(r_.dtype).view_as(r_)).sum() for r_, u in zip(ref, ups)).backward()
     assert rel_err(dh, hr.grad) < 2e-4
+    # float64 (tests/head_ref.py), at the same tolerances and at head_ref's own per-element / per-block budgets
+    import head_ref
+    f64 = head_ref.head_with_grad(hd.double().view(-1, B, RP), E, eps_z, eps_t, head_ref.tables_f64(tb), ups)
+    for nm, r_, g_ in zip(NAMES, f64[0], got):
+        assert rel_err(g_.reshape(-1), r_.reshape(-1)) < 5e-5, nm
+    assert rel_err(dh, f64[2].reshape(dh.shape)) < 2e-4
+    head_ref.assert_within(head_ref.ratios(got, dh, *f64), (R, Ho, zd, refine))
 
 
 @pytest.mark.parametrize('refine', [False, True])
