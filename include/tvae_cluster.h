@@ -28,8 +28,8 @@ typedef void* tvae_stream_t;
 
 #define TVAE_KMEANS_MAX_RESTARTS 65535
 
-/* Still 1: the Ward, t-SNE, alignment, class-statistics, preprocessing and CTF entry points below were ADDED, no existing
- * prototype or meaning changed. */
+/* Still 1: the Ward, t-SNE, alignment, pose-refinement, class-statistics, preprocessing and CTF entry points below were ADDED,
+ * no existing prototype or meaning changed. */
 int tvae_cluster_abi_version(void);          /* == 1 */
 
 /* floats of workspace for one assign / update pair: per restart G x (k*d sums, k counts, 1 changed count, 1 sum of
@@ -181,6 +181,67 @@ int tvae_align_stack(const float* Y, const float* theta, const float* dx, float*
 /* avg[K][C][n][n]; ws holds tvae_class_average_ws_floats(N, K, C, n) floats. */
 int tvae_class_average(const float* Y, const float* theta, const float* dx, const int* order, const int* seg, float* avg,
                        float* ws, long ws_floats, int N, int C, int n, int K, float t_scale, tvae_stream_t stream);
+
+/* ---- Pose refinement against the class averages --------------------------------------------------------------------------
+ *
+ * The inverse of the map above: instead of resampling the image into the canonical frame, the class average of the image's
+ * class is rendered into the image's frame at NA = 2A + 1 angles, and compared with the image at NS x NS whole-pixel shifts,
+ * NS = 2S + 1.  Y, theta, dx and t_scale (> 0) as in tvae_align_stack; cls[N] (int32) the class of every image;
+ * ref[K][C][n][n] the class averages in the canonical frame; dtheta the angle step in radians (finite); mask_radius and
+ * mask_edge in pixels.
+ *
+ * Template.  For image i with k = cls[i] and the angle index a = -A .. A: theta_a = theta[i] + (float)a * dtheta (the product
+ * and the sum each rounded to fp32), c = cos theta_a, s = sin theta_a (accurate cosf / sinf).  For every pixel (r, q) of the
+ * EXTENDED grid, r and q = -S .. n - 1 + S:
+ *     x0 = 2 q / (n - 1) - 1,  x1 = 1 - 2 r / (n - 1),  v = x - t dx[i],
+ *     u0 = v0 c - v1 s,  u1 = v0 s + v1 c,  col = (u0 + 1) (n - 1) / 2,  row = (1 - u1) (n - 1) / 2,
+ *     T_a[ch][r][q] = m(u) * (the bilinear sample of ref[k][ch] at (row, col)),
+ * with the sampling rules of the section above: taps floor and floor + 1, a tap outside [0, n - 1] is 0, and a position that
+ * is not inside (-1, n) on both axes gives exactly 0, mask or no mask (tested before any float -> int conversion: NaN, +-inf
+ * and huge poses give a template of zeros).  m is the mask of tvae_class_frc (below) at d = sqrt(u0^2 + u1^2) (n - 1) / 2
+ * pixels from the canonical centre, evaluated in fp64 from the fp32 u: 1 for d <= mask_radius, the raised cosine over
+ * mask_edge, 0 beyond; mask_radius <= 0 means no mask; a non-finite radius or edge and a negative edge are rejected.
+ *
+ * Candidates.  The candidate (a, sy, sx), sy and sx = -S .. S, predicts P(r, q) = T_a[r - sy][q - sx] on the frame
+ * r, q = 0 .. n - 1:
+ *     num = sum P Y,  pp = sum P^2  (over channels and pixels),   yy = sum Y^2 over the whole frame,
+ *     score = num / sqrt(pp yy) in fp64 from the three fp32 sums, rounded to fp32 once; exactly 0 where pp or yy is 0:
+ * the cosine between the image and what the model predicts at that pose.  The candidate is the pose
+ *     theta' = theta_a,   dx' = dx + (2 sx / (n - 1), -2 sy / (n - 1)) / t_scale
+ * (fp32: (float)(2 sx) / (float)(n - 1), then / t_scale, then the sum, each correctly rounded).  A part of the pose whose index
+ * (a, sx or sy) is 0 is copied bit for bit.
+ *
+ * Selection.  The best candidate starts as the centre (0, 0, 0); the candidates are visited in ascending (a, sy, sx) and one
+ * replaces the best only if its score is finite and strictly greater.  An image whose pose cannot be improved keeps theta and
+ * dx bit for bit, and the refined score is never below the centre score.  A centre score that is not finite counts as -inf
+ * (and is reported as -inf in score[i][0]); if no candidate is finite the pose is unchanged and both scores are 0.
+ * An image with cls outside [0, K) keeps its pose bit for bit and gets the scores (0, 0), best (0, 0, 0) and zeros in its rows
+ * of the tables; nothing of ref is read for it.
+ *
+ * Arithmetic: fp32 products and sums (FMA chains) in a fixed order, no atomics.  num of a candidate: the rows of the frame are
+ * dealt to G groups by r mod G, where G = ceil(n / ceil(n / (256 div NS))); a group adds channel after channel, within a
+ * channel its rows in ascending r and along a row the pixels in ascending q, one chain; the G sums are then added in ascending
+ * group.  pp: R2[re][sx] = the sum of T^2 over the n columns of the window in row re of the extended template, one chain in
+ * ascending q that runs on through the channels; pp = the sum of R2 over the window's n rows in ascending r.  yy: thread t of
+ * 256 adds the pixels p = t, t + 256, ... of every channel in turn in one chain, then a binary tree over the 256 sums (t and
+ * t + 128, then t and t + 64, ...).  Every output of image i is a pure function of image i, its pose and ref[cls[i]]: not of
+ * N, K or the other images; every output is bitwise reproducible.
+ *
+ * Supported: 1 <= N <= 2^24, 1 <= C <= 16, 2 <= n <= 128 (one image plane and one extended template fit the 160 KB of LDS),
+ * 1 <= K <= 65535, 0 <= A <= 32, 0 <= S <= 8, t_scale finite and > 0, dtheta finite; num and pp both NULL or both not; no
+ * output (the workspace is one) may overlap an input.  Anything else returns hipErrorInvalidValue (1) and writes nothing, and
+ * the query returns 0. */
+
+/* floats of workspace of tvae_pose_refine: the tables num and pp [N][NA][NS][NS] and yy [N] (used where the caller passes
+ * NULL for them).  0 for unsupported arguments. */
+long tvae_pose_refine_ws_floats(int N, int C, int n, int A, int S);
+
+/* theta_out[N], dx_out[N][2], score[N][2] = (centre, best), best[N][3] = (a, sy, sx) (int32); num and pp [N][NA][NS][NS] or
+ * both NULL, yy[N] or NULL: the raw sums, for tests */
+int tvae_pose_refine(const float* Y, const float* theta, const float* dx, const int* cls, const float* ref,
+                     float* theta_out, float* dx_out, float* score, int* best, float* num, float* pp, float* yy, float* ws,
+                     long ws_floats, int N, int C, int n, int K, int A, int S, float t_scale, float dtheta,
+                     float mask_radius, float mask_edge, tvae_stream_t stream);
 
 /* ---- Quality of the class averages: half sets, variance maps and the Fourier ring correlation ---------------------------
  *

@@ -52,22 +52,7 @@ __device__ __forceinline__ float align_sample(const float* __restrict__ img, int
     const float x1 = fmaf(-u0, p.s, fmaf(u1, p.c, p.ty));
     const float col = (x0 + 1.f) * half;
     const float row = (1.f - x1) * half;
-    const float fn = (float)n;
-    // NaN fails every comparison: `in` is false for NaN, +-inf and anything that would not convert to an int
-    const bool in = on && (col > -1.f) && (col < fn) && (row > -1.f) && (row < fn);
-    const float colc = in ? col : 0.f, rowc = in ? row : 0.f;
-    const float fc = floorf(colc), fr = floorf(rowc);
-    const int c0 = (int)fc, r0 = (int)fr;                     // in [-1, n - 1]
-    const float wc = colc - fc, wr = rowc - fr;
-    const bool c0in = c0 >= 0, c1in = c0 + 1 <= n - 1, r0in = r0 >= 0, r1in = r0 + 1 <= n - 1;
-    const int ca = c0in ? c0 : 0, cb = c1in ? c0 + 1 : n - 1;
-    const int ra = r0in ? r0 : 0, rb = r1in ? r0 + 1 : n - 1;
-    const float v00 = img[ra * n + ca], v01 = img[ra * n + cb], v10 = img[rb * n + ca], v11 = img[rb * n + cb];
-    const float a00 = (in && r0in && c0in) ? v00 : 0.f, a01 = (in && r0in && c1in) ? v01 : 0.f;
-    const float a10 = (in && r1in && c0in) ? v10 : 0.f, a11 = (in && r1in && c1in) ? v11 : 0.f;
-    const float top = fmaf(wc, a01 - a00, a00);
-    const float bot = fmaf(wc, a11 - a10, a10);
-    return fmaf(wr, bot - top, top);
+    return bilinear_zero_border(img, n, col, row, on);        // (cluster_common.hpp: shared with the pose refinement)
 }
 
 // grid = N * C * tiles (tile fastest).  out[N][C][n][n]

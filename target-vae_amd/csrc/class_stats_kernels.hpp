@@ -133,10 +133,7 @@ __device__ __forceinline__ float frc_mask(int i, int j, int n, float radius, flo
     if (!(radius > 0.f)) return 1.f;
     const double c = 0.5 * (double)(n - 1);
     const double di = (double)i - c, dj = (double)j - c;
-    const double d = sqrt(di * di + dj * dj), r = (double)radius, e = (double)edge;
-    if (d <= r) return 1.f;
-    if (d >= r + e) return 0.f;                               // (edge = 0: a hard edge, never the division below)
-    return (float)(0.5 * (1.0 + cospi((d - r) / e)));
+    return soft_mask(sqrt(di * di + dj * dj), radius, edge);  // (cluster_common.hpp: shared with the pose refinement)
 }
 
 // grid = (ceil(n / FRC_ROWS), P, 2): z = 0 reads a, z = 1 reads b.  G[P][2][n][H] complex, H = n / 2 + 1:

@@ -36,6 +36,41 @@ constexpr int SIDE_MAX = 1024;           // n: side of an image or plane
 constexpr int PLANES_MAX = 1 << 24;      // images or planes of a stack
 constexpr int CLASSES_MAX = 65535;       // classes
 
+// ---- bilinear sampling with a zero border, and the soft circular mask --------------------------------------------------------
+// The sample of img[n][n] at the position (row, col) in pixels: the taps floor and floor + 1 per axis, a tap outside
+// [0, n - 1] is 0, and a position that is not inside (-1, n) on both axes gives exactly 0 -- the range is tested BEFORE the
+// float -> int conversion and NaN fails it.  `on` = false gives 0 as well; nothing but in-bounds words is ever read.
+__device__ __forceinline__ bool inside_frame(float col, float row, int n) {
+    const float fn = (float)n;
+    // NaN fails every comparison: false for NaN, +-inf and anything that would not convert to an int
+    return (col > -1.f) && (col < fn) && (row > -1.f) && (row < fn);
+}
+
+__device__ __forceinline__ float bilinear_zero_border(const float* __restrict__ img, int n, float col, float row, bool on) {
+    const bool in = on && inside_frame(col, row, n);
+    const float colc = in ? col : 0.f, rowc = in ? row : 0.f;
+    const float fc = floorf(colc), fr = floorf(rowc);
+    const int c0 = (int)fc, r0 = (int)fr;                     // in [-1, n - 1]
+    const float wc = colc - fc, wr = rowc - fr;
+    const bool c0in = c0 >= 0, c1in = c0 + 1 <= n - 1, r0in = r0 >= 0, r1in = r0 + 1 <= n - 1;
+    const int ca = c0in ? c0 : 0, cb = c1in ? c0 + 1 : n - 1;
+    const int ra = r0in ? r0 : 0, rb = r1in ? r0 + 1 : n - 1;
+    const float v00 = img[ra * n + ca], v01 = img[ra * n + cb], v10 = img[rb * n + ca], v11 = img[rb * n + cb];
+    const float a00 = (in && r0in && c0in) ? v00 : 0.f, a01 = (in && r0in && c1in) ? v01 : 0.f;
+    const float a10 = (in && r1in && c0in) ? v10 : 0.f, a11 = (in && r1in && c1in) ? v11 : 0.f;
+    const float top = fmaf(wc, a01 - a00, a00);
+    const float bot = fmaf(wc, a11 - a10, a10);
+    return fmaf(wr, bot - top, top);
+}
+
+// The mask at d pixels from the centre for radius > 0: 1 within `radius`, a raised cosine over `edge`, 0 beyond.
+__device__ __forceinline__ float soft_mask(double d, float radius, float edge) {
+    const double r = (double)radius, e = (double)edge;
+    if (d <= r) return 1.f;
+    if (d >= r + e) return 0.f;                               // (edge = 0: a hard edge, never the division below)
+    return (float)(0.5 * (1.0 + cospi((d - r) / e)));
+}
+
 // ---- direct DFT --------------------------------------------------------------------------------------------------------------
 // kx = 0 .. n / 2 of a half spectrum; also the number of rings
 __host__ __device__ static inline int half_side(int n) { return n / 2 + 1; }

@@ -1,5 +1,5 @@
 """ctypes binding of libtvae_cluster.so (C ABI declared in include/tvae_cluster.h): the batched k-means, Ward
-linkage, t-SNE, alignment and class-statistics kernels.
+linkage, t-SNE, alignment, pose-refinement and class-statistics kernels.
 
 A library of its own beside libtvae_hip.so -- the ABI of the training kernels (tvae._lib.SIGNATURES, version 7) is not
 touched by the clustering half.  Same rules: no CPU fallback, tensors are checked by tvae._lib._ptr (GPU, contiguous,
@@ -47,6 +47,9 @@ SIGNATURES = {
     # X, x_stride, coef (fp64, or None), Hp (or None), h_stride, out, ws, ws_floats, B, n, mode
     'tvae_fourier_filter': 'plpplppliii',
     'tvae_ctf_power': 'pppppiii',             # coef (fp64), order, seg, D (fp64), counts (int32), N, K, n
+    # Y, theta, dx, cls (int32), ref, theta_out, dx_out, score, best (int32), num, pp, yy (or None all three), ws, ws_floats,
+    # N, C, n, K, A, S, t_scale, dtheta, mask_radius, mask_edge
+    'tvae_pose_refine': 'ppppp' 'pppp' 'ppp' 'p' 'l' 'iiiiii' 'ffff',
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
@@ -64,6 +67,7 @@ QUERIES = {
     'tvae_class_frc_ws_floats': ('ii', 'l'),
     'tvae_image_normalize_ws_floats': ('iii', 'l'),
     'tvae_fourier_filter_ws_floats': ('ii', 'l'),
+    'tvae_pose_refine_ws_floats': ('iiiii', 'l'),
 }
 
 # the shape limits every image family shares (SIDE_MAX, PLANES_MAX, CLASSES_MAX of csrc/cluster_common.hpp)

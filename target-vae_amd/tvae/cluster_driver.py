@@ -26,6 +26,11 @@ class_variance.npy, class_frc.npy, class_counts.npy ([K][2], the members of each
 TVAE_CLASS_AVERAGES=1 when both are set), class_resolution.txt and, with matplotlib, class_frc.jpg and class_variance.jpg.
 Both halves share one encoder and one set of poses: not a gold-standard FRC, it reads optimistic.  class_resolution.py
 computes the same from the saved .npy files alone.  Unset, nothing changes.
+
+TVAE_REFINE_POSES=1 refines the run's poses against those averages (tvae.refine: every image scored against the average of
+its class over a small neighbourhood of angles and whole-pixel shifts, three rounds) -- rotations_refined.npy,
+translations_refined.npy, refine_scores.npy and class_averages_refined.npy (.mrcs, .jpg).  refine_poses.py computes the same
+from the saved .npy files alone.  Unset, nothing changes.
 """
 from __future__ import annotations
 
@@ -202,6 +207,24 @@ def _class_frc(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
     resolution.save_outputs(out_dir, res)
 
 
+def _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters):
+    """TVAE_REFINE_POSES=1: the run's poses refined against its class averages (tvae.refine, three rounds with the defaults
+    of refine_poses.py) and the averages of the refined poses, from the same images, poses and clusters as the class averages."""
+    from . import align, refine
+    print('# refining the poses against the class averages ... ', file=sys.stderr)
+    if images.shape[-1] != images.shape[-2]:
+        raise SystemExit('TVAE_REFINE_POSES=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
+    y = images.to(device).float().contiguous()
+    t = align.translation_scale(args.t_inf)
+    th, d, hist = refine.refine_rounds(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(), np.asarray(clusters),
+                                       args.n_clusters, t)
+    avg, counts = align.class_averages(y, th, d, np.asarray(clusters), args.n_clusters, t)
+    np.save(os.path.join(out_dir, 'rotations_refined.npy'), th.cpu().numpy().reshape(tuple(rot_pred.shape)))
+    np.save(os.path.join(out_dir, 'translations_refined.npy'), d.cpu().numpy())
+    np.save(os.path.join(out_dir, 'refine_scores.npy'), hist['scores'])
+    align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), kind == 'particles', 'class_averages_refined')
+
+
 def run(kind: str, argv=None):
     args = build_parser(kind).parse_args(argv)
     from src import models  # noqa: F401     (whole-module checkpoints unpickle as src.models.*)
@@ -266,6 +289,8 @@ def run(kind: str, argv=None):
         _class_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
     if os.environ.get('TVAE_CLASS_FRC', '') == '1':
         _class_frc(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+    if os.environ.get('TVAE_REFINE_POSES', '') == '1':
+        _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
 
     np.save(os.path.join(out_dir, 'latents.npy'), z_values.cpu().numpy())
     np.save(os.path.join(out_dir, 'rotations.npy'), rot_pred.cpu().numpy())

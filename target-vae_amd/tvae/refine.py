@@ -1,0 +1,220 @@
+"""Pose refinement against the class averages on the GPU: the step after class_averages.py.  Every image is scored against
+the average of its class over a small neighbourhood of poses -- the average rendered into the image's frame at 2A + 1 angles
+around the predicted one and compared at (2S + 1)^2 whole-pixel shifts, the score the cosine between the image and the
+prediction -- and keeps the best pose; the averages are then formed again.  include/tvae_cluster.h states the definition
+in full (the inverse of the map of tvae.align: the reference is resampled, not the image).
+
+The kernel is tvae_pose_refine of libtvae_cluster.so: no CPU fallback, no float atomics, bitwise reproducible, and the
+result of an image depends on that image, its pose and its class's reference alone.  n > 128 is out of scope (one image
+plane and one extended template have to fit the LDS): Fourier-downsample the stack with tvae.image first -- poses are in
+coordinate units and carry over unchanged.
+
+`refine_rounds` alternates averaging and refining and halves the angle step after every round.  With cross_halves=True
+every image is scored against the half-set average it is NOT a member of, so that no image is aligned to an average that
+contains it.
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import _cluster_lib as CL
+from . import align
+from ._lib import TvaeHipError
+
+MAX_SIDE, MAX_CHANNELS, MAX_ANGLE_STEPS, MAX_SHIFT = 128, 16, 32, 8
+WS_FLOATS = 1 << 26               # workspace of one tvae_pose_refine call: 256 MB
+
+
+def _check_refs(images, refs, what):
+    CL.require_f32(refs, what, 'refs')
+    N, C, n, _ = images.shape
+    if refs.dim() != 4 or tuple(refs.shape[1:]) != (C, n, n) or refs.device != images.device:
+        raise TvaeHipError(f'{what}: refs must be [K][C][n][n] = [K][{C}][{n}][{n}] on the device of the images, got '
+                           f'{tuple(refs.shape)}')
+    K = refs.shape[0]
+    if not 1 <= K <= align.MAX_CLUSTERS:
+        raise TvaeHipError(f'{what}: {K} references outside [1, {align.MAX_CLUSTERS}]')
+    return K
+
+
+def refine_poses(images, theta, dx, labels, refs, t_scale=1.0, angle_steps=8, angle_step=None, shift=2, mask_radius=None,
+                 mask_edge=0.0, tables=False):
+    """images [N][C][n][n], theta [N] or [N][1], dx [N][2], refs [K][C][n][n] (CUDA fp32), labels [N] integers (any device or
+    numpy; a label outside [0, K) leaves its image alone) -> (theta' [N], dx' [N][2], scores [N][2] = (centre, best),
+    best int32 [N][3] = (a, sy, sx)) and with tables=True also (num, pp [N][NA][NS][NS], yy [N]), the raw sums.
+    angle_steps = A steps of angle_step radians to each side (None: pi / 8 divided by max(A, 1)); shift = S pixels."""
+    what = 'refine_poses'
+    N, C, n, _, lab = align._check_labels(images, theta, dx, labels, 1, what)
+    K = _check_refs(images, refs, what)
+    A, S = int(angle_steps), int(shift)
+    if n > MAX_SIDE:
+        raise TvaeHipError(f'{what}: n = {n} is above {MAX_SIDE} (one image plane and one extended template must fit the LDS): '
+                           'Fourier-downsample the stack with tvae.image first; poses are in coordinate units and carry '
+                           'over unchanged')
+    if not (C <= MAX_CHANNELS and 0 <= A <= MAX_ANGLE_STEPS and 0 <= S <= MAX_SHIFT):
+        raise TvaeHipError(f'{what}: C={C}, angle_steps={A}, shift={S} outside the supported range (C <= {MAX_CHANNELS}, '
+                           f'0 <= angle_steps <= {MAX_ANGLE_STEPS}, 0 <= shift <= {MAX_SHIFT})')
+    step = math.pi / 8 / max(A, 1) if angle_step is None else float(angle_step)
+    t = float(t_scale)
+    radius = 0.0 if mask_radius is None else float(mask_radius)
+    edge = float(mask_edge)
+    if not (np.isfinite(t) and t > 0 and np.isfinite(step)):
+        raise TvaeHipError(f'{what}: t_scale = {t_scale} must be finite and positive and angle_step = {angle_step} finite')
+    if not (np.isfinite(radius) and np.isfinite(edge) and edge >= 0):
+        raise TvaeHipError(f'{what}: mask_radius = {mask_radius} and mask_edge = {mask_edge} must be finite, the edge not negative')
+    if lab.dtype.is_floating_point or lab.dtype == torch.bool:
+        raise TvaeHipError(f'{what}: labels must be a one-dimensional integer array')
+    lim = torch.iinfo(torch.int32)
+    cls = lab.to(torch.int64).clamp(-1, lim.max).to(torch.int32).contiguous()      # (anything negative is outside [0, K) as -1 is)
+    dev = images.device
+    NA, NS = 2 * A + 1, 2 * S + 1
+    th_in = theta.reshape(N)
+    th_out = torch.empty(N, dtype=torch.float32, device=dev)
+    dx_out = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    score = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    best = torch.empty(N, 3, dtype=torch.int32, device=dev)
+    num = pp = yy = None
+    if tables:
+        num = torch.empty(N, NA, NS, NS, dtype=torch.float32, device=dev)
+        pp = torch.empty(N, NA, NS, NS, dtype=torch.float32, device=dev)
+        yy = torch.empty(N, dtype=torch.float32, device=dev)
+    # Images are independent and an image's workgroups and addition order depend on (n, C, A, S) alone, so a call on a slice
+    # of the stack cannot change a bit of any image's result: the slices only bound the workspace.
+    per = CL.query('tvae_pose_refine_ws_floats', 1, C, n, A, S)
+    if per <= 0:
+        raise TvaeHipError(f'{what}: N={N}, C={C}, n={n}, angle_steps={A}, shift={S} outside the supported range')
+    stepN = CL.slice_step(N, CL.MAX_PLANES, WS_FLOATS // per)
+    wsf = CL.query('tvae_pose_refine_ws_floats', stepN, C, n, A, S)
+    ws = torch.empty(wsf, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        for i0 in range(0, N, stepN):
+            i1 = min(i0 + stepN, N)
+            sl = slice(i0, i1)
+            CL.call('tvae_pose_refine', images[sl], th_in[sl], dx[sl], cls[sl], refs, th_out[sl], dx_out[sl], score[sl],
+                    best[sl], None if num is None else num[sl], None if pp is None else pp[sl],
+                    None if yy is None else yy[sl], ws, wsf, i1 - i0, C, n, K, A, S, t, step, radius, edge)
+    if tables:
+        return th_out, dx_out, score, best, num, pp, yy
+    return th_out, dx_out, score, best
+
+
+def cross_half_labels(labels, n_clusters):
+    """labels [N] (integers, any device) -> int64 [N] on the same device: the index among the 2K references
+    [half 0 of class 0 .. K - 1, half 1 of class 0 .. K - 1] of the half-set average that does NOT contain the image.  Half
+    membership is the rule of tvae_class_halves: the position of the image within its class in `segments` order, even =
+    half 0, odd = half 1.  So an image of half 0 gets K + k and one of half 1 gets k; a label outside [0, K) gets -1."""
+    lab = torch.as_tensor(labels)
+    K = int(n_clusters)
+    order, seg, _ = align.segments(lab, K)
+    order, seg = order.to(torch.int64), seg.to(torch.int64)
+    N = order.numel()
+    pos = torch.arange(N, device=order.device)
+    key = torch.where((lab.to(torch.int64) >= 0) & (lab.to(torch.int64) < K), lab.to(torch.int64),
+                      torch.full_like(lab.to(torch.int64), K))[order]      # class of every position (K: none)
+    valid = key < K
+    first = seg[key.clamp(max=K - 1)]
+    odd = ((pos - first) % 2) == 1
+    ref = torch.where(odd, key, key + K)
+    out = torch.full((N,), -1, dtype=torch.int64, device=order.device)
+    out[order] = torch.where(valid, ref, torch.full_like(ref, -1))
+    return out
+
+
+def refine_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3, angle_range=math.pi / 8, angle_steps=8,
+                  shift=2, mask_radius=None, mask_edge=0.0, cross_halves=False):
+    """`rounds` times: the class averages of the current poses (tvae.align.class_averages; with cross_halves=True the two
+    half-set averages of tvae.align.class_halves as 2K references, every image scored against the half it is not in), then
+    refine_poses, then half the angle step: round j searches angle_range / 2^j to each side in angle_steps steps, inside the
+    cell that the previous round chose.  -> (theta' [N], dx' [N][2], history): history['steps'] the angle step of every round
+    and history['scores'] fp64 [rounds][2], the mean centre and best score over the images of a class in each round."""
+    what = 'refine_rounds'
+    N, C, n, K, lab = align._check_labels(images, theta, dx, labels, n_clusters, what)
+    A = int(angle_steps)
+    if int(rounds) < 1:
+        raise TvaeHipError(f'{what}: rounds = {rounds} must be positive')
+    th, d = theta.reshape(N).contiguous(), dx
+    lab64 = lab.to(torch.int64)
+    member = (lab64 >= 0) & (lab64 < K)
+    cls = cross_half_labels(lab64, K) if cross_halves else lab64
+    steps, scores = [], []
+    for j in range(int(rounds)):
+        step = float(angle_range) / max(A, 1) / 2 ** j
+        if cross_halves:
+            refs = align.class_halves(images, th, d, lab64, K, t_scale)[1].reshape(2 * K, C, n, n)
+        else:
+            refs = align.class_averages(images, th, d, lab64, K, t_scale)[0]
+        th, d, sc, _ = refine_poses(images, th, d, cls, refs, t_scale, A, step, shift, mask_radius, mask_edge)
+        steps.append(step)
+        m = sc[member].double()
+        scores.append(m.mean(0).cpu().numpy() if m.numel() else np.zeros(2))
+    return th, d, dict(steps=steps, scores=np.stack(scores))
+
+
+# ---- refine_poses.py: refined poses and averages from the files a clustering run wrote ---------------------------------------
+def build_parser() -> argparse.ArgumentParser:
+    base = align.build_parser()
+    p = argparse.ArgumentParser('Refine the poses of a clustered stack against its aligned 2-D class averages')
+    keep = {'stack', 'rotations', 'translations', 'clusters', 't_inf', 'crop', 'n_clusters', 'out_dir', 'device'}
+    for a in base._actions:                                  # the flags of class_averages.py, as it declares them
+        if a.dest in keep:
+            p._add_action(a)
+    p.add_argument('--rounds', default=3, type=int, help='rounds of averaging and refining; the angle step halves every round')
+    p.add_argument('--angle-range', default=22.5, type=float, help='degrees searched to each side in the first round')
+    p.add_argument('--angle-steps', default=8, type=int, help='angle steps to each side (at most 32)')
+    p.add_argument('--shift', default=2, type=int, help='shift radius in whole pixels (at most 8)')
+    p.add_argument('--mask-radius', default=None, type=float, help='soft mask radius in pixels; default: no mask')
+    p.add_argument('--mask-edge', default=0.0, type=float, help='width of the raised-cosine edge in pixels')
+    p.add_argument('--cross-halves', action='store_true',
+                   help='score every image against the half-set average it is not a member of')
+    return p
+
+
+def _resolutions(images, theta, dx, clusters, K, t):
+    from . import resolution
+    res = resolution.class_resolution(images, theta, dx, clusters, K, t)
+    curve = resolution.combined(res['sums'].cpu().numpy())
+    n = images.shape[-1]
+    return np.stack([resolution.resolution(curve, n, thr) for thr in resolution.THRESHOLDS], 1)
+
+
+def run(argv=None):
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available() or args.device == -1:
+        raise SystemExit('the MI355X build has no CPU compute path')
+    torch.cuda.set_device(args.device)
+    device = torch.device('cuda', args.device)
+    stack = align.load_stack(args.stack, args.crop)
+    particles = args.stack.endswith('mrc') or args.stack.endswith('mrcs')
+    images = torch.from_numpy(stack).to(device)
+    theta = torch.from_numpy(np.asarray(np.load(args.rotations), dtype=np.float32).reshape(-1)).to(device)
+    dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
+    clusters = np.asarray(np.load(args.clusters)).reshape(-1)
+    t = align.translation_scale(args.t_inf)
+    try:
+        K = align._check_labels(images, theta, dx, clusters, args.n_clusters, 'refine_poses')[3]
+        before = _resolutions(images, theta, dx, clusters, K, t)
+        th, d, hist = refine_rounds(images, theta, dx, clusters, K, t, args.rounds, math.radians(args.angle_range),
+                                    args.angle_steps, args.shift, args.mask_radius, args.mask_edge, args.cross_halves)
+        avg, counts = align.class_averages(images, th, d, clusters, K, t)
+        after = _resolutions(images, th, d, clusters, K, t)
+    except TvaeHipError as e:
+        raise SystemExit(str(e)) from e
+    os.makedirs(args.out_dir, exist_ok=True)
+    np.save(os.path.join(args.out_dir, 'rotations_refined.npy'), th.cpu().numpy().reshape(np.load(args.rotations).shape))
+    np.save(os.path.join(args.out_dir, 'translations_refined.npy'), d.cpu().numpy())
+    np.save(os.path.join(args.out_dir, 'refine_scores.npy'), hist['scores'])
+    align.save_outputs(args.out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles, 'class_averages_refined')
+    print('# class  members  resolution[px]@0.143 before -> after  resolution[px]@0.5 before -> after')
+    cnt = counts.cpu().numpy()
+    for k in range(K):
+        print('{} {} {:.4f} -> {:.4f} {:.4f} -> {:.4f}'.format(k, int(cnt[k]), before[k, 0], after[k, 0], before[k, 1],
+                                                               after[k, 1]))
+    print('# refined the poses of {} images in {} classes, {} rounds, mean score {:.6f} -> {:.6f}: {}'.format(
+        images.shape[0], K, args.rounds, hist['scores'][0, 0], hist['scores'][-1, 1], args.out_dir), file=sys.stderr)
+    return th, d, hist
