@@ -28,8 +28,8 @@ typedef void* tvae_stream_t;
 
 #define TVAE_KMEANS_MAX_RESTARTS 65535
 
-/* Still 1: the Ward, t-SNE, alignment, pose-refinement, class-statistics, preprocessing and CTF entry points below were ADDED,
- * no existing prototype or meaning changed. */
+/* Still 1: the Ward, t-SNE, alignment, pose-refinement, reassignment, class-statistics, preprocessing and CTF entry points below were
+ * ADDED, no existing prototype or meaning changed. */
 int tvae_cluster_abi_version(void);          /* == 1 */
 
 /* floats of workspace for one assign / update pair: per restart G x (k*d sums, k counts, 1 changed count, 1 sum of
@@ -242,6 +242,49 @@ int tvae_pose_refine(const float* Y, const float* theta, const float* dx, const 
                      float* theta_out, float* dx_out, float* score, int* best, float* num, float* pp, float* yy, float* ws,
                      long ws_floats, int N, int C, int n, int K, int A, int S, float t_scale, float dtheta,
                      float mask_radius, float mask_edge, tvae_stream_t stream);
+
+/* ---- Reassignment against the class averages -----------------------------------------------------------------------------
+ *
+ * The other half of the averaging loop: the pose search of the section above against M candidate classes per image instead
+ * of one, and the choice among them (multi-reference alignment).  All classes share the decoder's canonical frame, so the
+ * predicted pose of an image is close to right for every class and the small neighbourhood of tvae_pose_refine is enough.
+ * Y, theta, dx, ref[K][C][n][n], t_scale, A, S, dtheta, mask_radius and mask_edge as for tvae_pose_refine;
+ * cand[N][M] (int32), 1 <= M <= TVAE_CLASSIFY_MAX_CANDIDATES: the candidate classes of every image, slot 0 by convention
+ * its current class.  A slot whose value is outside [0, K) is skipped: nothing of ref is read for it, its rows of the tables
+ * are zeros and its scores are (0, 0).  Duplicates are allowed and computed as given.
+ *
+ * Per slot.  For slot m with k = cand[i][m] the sums num, pp [N][M][NA][NS][NS] and yy [N] are bit for bit what
+ * tvae_pose_refine produces for that image with cls[i] = k: the templates, the chains and their order, the score in fp64
+ * from the three fp32 sums and the selection rule with its centre priority are those of the section above, and so are the
+ * slot's score[i][m] = (centre, best) and its best candidate (a, sy, sx).  yy is formed once per image; it is 0 for an
+ * image with no valid slot.
+ *
+ * Across slots.  The valid slots compete with the best score they report.  They are visited in ascending m: the first valid
+ * slot is the start, and a later slot replaces it only if its best score is strictly greater.  Ties therefore stay with the
+ * lowest slot -- the incumbent when slot 0 is valid.  A slot with no finite candidate reports 0 and competes with that 0.
+ *
+ * Outputs.  With m* the winning slot: cls_out[i] = cand[i][m*], best[i] = (m*, a, sy, sx) of that slot's best candidate, and
+ * theta_out, dx_out by the pose update of tvae_pose_refine applied to it (an index that is 0 copies its part of the pose bit
+ * for bit).  An image with no valid slot keeps its pose bit for bit and gets cls_out = cand[i][0] unchanged, best = 0 and
+ * zero scores.  Every output of image i is a pure function of image i, its pose, its row of candidates and the references
+ * that row names: not of N, K or the other images.  No atomics; every output is bitwise reproducible.
+ *
+ * Supported: the range of tvae_pose_refine and 1 <= M <= 64; num and pp both NULL or both not, yy may be NULL (the workspace
+ * holds what is not given); no output (the workspace is one) may overlap an input.  Anything else returns
+ * hipErrorInvalidValue (1) and writes nothing, and the query returns 0. */
+
+#define TVAE_CLASSIFY_MAX_CANDIDATES 64
+
+/* floats of workspace of tvae_pose_classify: N (2 M NA NS^2 + 1), the tables num and pp [N][M][NA][NS][NS] and yy [N] (used
+ * where the caller passes NULL for them).  0 for unsupported arguments. */
+long tvae_pose_classify_ws_floats(int N, int M, int C, int n, int A, int S);
+
+/* cls_out[N] (int32), best[N][4] = (m*, a, sy, sx) (int32), theta_out[N], dx_out[N][2], score[N][M][2] = (centre, best) of
+ * every slot; num and pp [N][M][NA][NS][NS] or both NULL, yy[N] or NULL: the raw sums, for tests */
+int tvae_pose_classify(const float* Y, const float* theta, const float* dx, const int* cand, const float* ref, int* cls_out,
+                       int* best, float* theta_out, float* dx_out, float* score, float* num, float* pp, float* yy, float* ws,
+                       long ws_floats, int N, int C, int n, int K, int M, int A, int S, float t_scale, float dtheta,
+                       float mask_radius, float mask_edge, tvae_stream_t stream);
 
 /* ---- Quality of the class averages: half sets, variance maps and the Fourier ring correlation ---------------------------
  *

@@ -1,5 +1,5 @@
 """ctypes binding of libtvae_cluster.so (C ABI declared in include/tvae_cluster.h): the batched k-means, Ward
-linkage, t-SNE, alignment, pose-refinement and class-statistics kernels.
+linkage, t-SNE, alignment, pose-refinement, reassignment and class-statistics kernels.
 
 A library of its own beside libtvae_hip.so -- the ABI of the training kernels (tvae._lib.SIGNATURES, version 7) is not
 touched by the clustering half.  Same rules: no CPU fallback, tensors are checked by tvae._lib._ptr (GPU, contiguous,
@@ -50,6 +50,9 @@ SIGNATURES = {
     # Y, theta, dx, cls (int32), ref, theta_out, dx_out, score, best (int32), num, pp, yy (or None all three), ws, ws_floats,
     # N, C, n, K, A, S, t_scale, dtheta, mask_radius, mask_edge
     'tvae_pose_refine': 'ppppp' 'pppp' 'ppp' 'p' 'l' 'iiiiii' 'ffff',
+    # Y, theta, dx, cand (int32), ref, cls_out (int32), best (int32), theta_out, dx_out, score, num, pp, yy (or None all three),
+    # ws, ws_floats, N, C, n, K, M, A, S, t_scale, dtheta, mask_radius, mask_edge
+    'tvae_pose_classify': 'ppppp' 'ppppp' 'ppp' 'p' 'l' 'iiiiiii' 'ffff',
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
@@ -68,6 +71,7 @@ QUERIES = {
     'tvae_image_normalize_ws_floats': ('iii', 'l'),
     'tvae_fourier_filter_ws_floats': ('ii', 'l'),
     'tvae_pose_refine_ws_floats': ('iiiii', 'l'),
+    'tvae_pose_classify_ws_floats': ('iiiiii', 'l'),
 }
 
 # the shape limits every image family shares (SIDE_MAX, PLANES_MAX, CLASSES_MAX of csrc/cluster_common.hpp)

@@ -1,0 +1,284 @@
+"""Reassignment against the class averages on the GPU: the other half of the averaging loop (multi-reference alignment).
+tvae.refine scores an image against the average of ITS class and never moves it to another; here every image is scored
+against M candidate classes over the same small neighbourhood of poses (2A + 1 angles, (2S + 1)^2 whole-pixel shifts, the
+cosine between the image and the prediction) and goes to the class whose best pose scores highest.  All classes share the
+decoder's canonical frame, so the predicted pose is close to right for every class and no global angular search is needed.
+include/tvae_cluster.h states the definition in full: a slot is tvae_pose_refine bit for bit, the slots are visited in
+ascending order and a later one wins only with a strictly greater score, so ties stay with slot 0, the incumbent.
+
+The kernel is tvae_pose_classify of libtvae_cluster.so: no CPU fallback, no float atomics, bitwise reproducible, and the
+result of an image depends on that image, its pose, its row of candidates and the references that row names alone.  n > 128
+is out of scope as it is for tvae.refine.
+
+`classify_rounds` alternates averaging and reassigning -- averages -> score against every candidate class -> move ->
+averages -- a reference-based 2-D classification seeded by the VAE's k-means labels.
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+from . import _cluster_lib as CL
+from . import align, refine
+from ._lib import TvaeHipError
+
+MAX_CANDIDATES = 64               # TVAE_CLASSIFY_MAX_CANDIDATES
+
+
+def _as_table(candidates, N, device, what):
+    cand = torch.as_tensor(candidates)
+    if cand.dim() != 2 or cand.shape[0] != N or cand.dtype.is_floating_point or cand.dtype == torch.bool:
+        raise TvaeHipError(f'{what}: candidates must be an [N][M] = [{N}][M] integer array, got {tuple(cand.shape)} '
+                           f'of {cand.dtype}')
+    M = cand.shape[1]
+    if not 1 <= M <= MAX_CANDIDATES:
+        raise TvaeHipError(f'{what}: {M} candidates per image outside [1, {MAX_CANDIDATES}]')
+    lim = torch.iinfo(torch.int32)
+    # (anything negative is outside [0, K) as -1 is)
+    return cand.to(device).to(torch.int64).clamp(-1, lim.max).to(torch.int32).contiguous(), M
+
+
+def classify_poses(images, theta, dx, candidates, refs, t_scale=1.0, angle_steps=8, angle_step=None, shift=2, mask_radius=None,
+                   mask_edge=0.0, tables=False):
+    """images [N][C][n][n], theta [N] or [N][1], dx [N][2], refs [K][C][n][n] (CUDA fp32), candidates [N][M] integers (any
+    device or numpy; slot 0 by convention the image's current class, a value outside [0, K) is skipped) -> (labels' int64 [N],
+    theta' [N], dx' [N][2], scores [N][M][2] = (centre, best) of every slot, best int32 [N][4] = (m*, a, sy, sx)) and with
+    tables=True also (num, pp [N][M][NA][NS][NS], yy [N]), the raw sums.  An image with no valid slot keeps its pose and its
+    slot-0 value.  angle_steps, angle_step, shift and the mask as in tvae.refine.refine_poses."""
+    what = 'classify_poses'
+    N, C, n = align._check_stack(images, theta, dx, what)
+    K = refine._check_refs(images, refs, what)
+    cand, M = _as_table(candidates, N, images.device, what)
+    A, S = int(angle_steps), int(shift)
+    if n > refine.MAX_SIDE:
+        raise TvaeHipError(f'{what}: n = {n} is above {refine.MAX_SIDE} (one image plane and one extended template must fit the '
+                           'LDS): Fourier-downsample the stack with tvae.image first; poses are in coordinate units and carry '
+                           'over unchanged')
+    if not (C <= refine.MAX_CHANNELS and 0 <= A <= refine.MAX_ANGLE_STEPS and 0 <= S <= refine.MAX_SHIFT):
+        raise TvaeHipError(f'{what}: C={C}, angle_steps={A}, shift={S} outside the supported range (C <= {refine.MAX_CHANNELS}, '
+                           f'0 <= angle_steps <= {refine.MAX_ANGLE_STEPS}, 0 <= shift <= {refine.MAX_SHIFT})')
+    step = math.pi / 8 / max(A, 1) if angle_step is None else float(angle_step)
+    t = float(t_scale)
+    radius = 0.0 if mask_radius is None else float(mask_radius)
+    edge = float(mask_edge)
+    if not (np.isfinite(t) and t > 0 and np.isfinite(step)):
+        raise TvaeHipError(f'{what}: t_scale = {t_scale} must be finite and positive and angle_step = {angle_step} finite')
+    if not (np.isfinite(radius) and np.isfinite(edge) and edge >= 0):
+        raise TvaeHipError(f'{what}: mask_radius = {mask_radius} and mask_edge = {mask_edge} must be finite, the edge not negative')
+    dev = images.device
+    NA, NS = 2 * A + 1, 2 * S + 1
+    th_in = theta.reshape(N)
+    cls_out = torch.empty(N, dtype=torch.int32, device=dev)
+    best = torch.empty(N, 4, dtype=torch.int32, device=dev)
+    th_out = torch.empty(N, dtype=torch.float32, device=dev)
+    dx_out = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    score = torch.empty(N, M, 2, dtype=torch.float32, device=dev)
+    num = pp = yy = None
+    if tables:
+        num = torch.empty(N, M, NA, NS, NS, dtype=torch.float32, device=dev)
+        pp = torch.empty(N, M, NA, NS, NS, dtype=torch.float32, device=dev)
+        yy = torch.empty(N, dtype=torch.float32, device=dev)
+    # Images are independent and an image's workgroups and addition order depend on (n, C, A, S) and its own row of
+    # candidates alone, so a call on a slice of the stack cannot change a bit of any image's result: the slices only bound
+    # the workspace (to the bound of tvae.refine, read when the call is made).
+    per = CL.query('tvae_pose_classify_ws_floats', 1, M, C, n, A, S)
+    if per <= 0:
+        raise TvaeHipError(f'{what}: N={N}, M={M}, C={C}, n={n}, angle_steps={A}, shift={S} outside the supported range')
+    stepN = CL.slice_step(N, CL.MAX_PLANES, refine.WS_FLOATS // per)
+    wsf = CL.query('tvae_pose_classify_ws_floats', stepN, M, C, n, A, S)
+    ws = torch.empty(wsf, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        for i0 in range(0, N, stepN):
+            i1 = min(i0 + stepN, N)
+            sl = slice(i0, i1)
+            CL.call('tvae_pose_classify', images[sl], th_in[sl], dx[sl], cand[sl], refs, cls_out[sl], best[sl], th_out[sl],
+                    dx_out[sl], score[sl], None if num is None else num[sl], None if pp is None else pp[sl],
+                    None if yy is None else yy[sl], ws, wsf, i1 - i0, C, n, K, M, A, S, t, step, radius, edge)
+    out = (cls_out.to(torch.int64), th_out, dx_out, score, best)
+    return out + (num, pp, yy) if tables else out
+
+
+def candidate_lists(labels, n_clusters, latents=None, m=None):
+    """labels [N] (integers, any device or numpy) -> int64 [N][M] on the labels' device: the candidate classes of every image.
+    Slot 0 is the current label, or -1 where the label is outside [0, K).  Without `latents` the other classes follow in
+    ascending order (M = K unless `m` is given; K > 64 without `m` raises).  With `latents` [N][d] the m - 1 other classes
+    follow whose centroid -- the mean latent of the class's current members, in fp64 -- is nearest to the image: ascending
+    distance, ties to the lower class, empty classes last.  An image outside every class has no class of its own to leave
+    out: its slots 1 .. m - 1 are the first m - 1 of all K classes in that order."""
+    what = 'candidate_lists'
+    lab = torch.as_tensor(labels)
+    if lab.dim() != 1 or lab.dtype.is_floating_point or lab.dtype == torch.bool:
+        raise TvaeHipError(f'{what}: labels must be a one-dimensional integer array')
+    K = int(n_clusters)
+    if K < 1:
+        raise TvaeHipError(f'{what}: n_clusters = {K} must be positive')
+    if m is None:
+        if K > MAX_CANDIDATES:
+            raise TvaeHipError(f'{what}: {K} classes are more than the {MAX_CANDIDATES} candidates an image may have: give m '
+                               '(and latents, so that the nearest classes are the candidates)')
+        m = K
+    m = int(m)
+    if not 1 <= m <= min(K, MAX_CANDIDATES):
+        raise TvaeHipError(f'{what}: m = {m} outside [1, min(n_clusters, {MAX_CANDIDATES})] = [1, {min(K, MAX_CANDIDATES)}]')
+    lab = lab.to(torch.int64)
+    dev = lab.device
+    N = lab.numel()
+    member = (lab >= 0) & (lab < K)
+    own = torch.where(member, lab, torch.full_like(lab, -1))
+    if latents is None:
+        d2 = torch.arange(K, dtype=torch.float64, device=dev).expand(N, K).clone()
+    else:
+        z = torch.as_tensor(latents).to(dev).to(torch.float64)
+        if z.dim() != 2 or z.shape[0] != N:
+            raise TvaeHipError(f'{what}: latents must be [N][d] = [{N}][d], got {tuple(z.shape)}')
+        onehot = torch.zeros(N, K, dtype=torch.float64, device=dev)
+        onehot[member, lab[member]] = 1.0
+        counts = onehot.sum(0)
+        cen = (onehot.t() @ z) / counts.clamp(min=1.0)[:, None]
+        d2 = ((z[:, None, :] - cen[None, :, :]) ** 2).sum(-1)
+        d2[:, counts == 0] = math.inf
+    rows = torch.arange(N, device=dev)
+    d2[rows[member], lab[member]] = -1.0                      # the own class sorts first: slot 0
+    order = torch.sort(d2, dim=1, stable=True).indices        # (stable: ties to the lower class)
+    out = torch.where(member[:, None], order[:, :m], torch.cat([own[:, None], order[:, :m - 1]], 1))
+    return out.contiguous()
+
+
+def cross_half_candidates(labels, candidates, n_clusters):
+    """The reference index of every slot when the 2K references are [half 0 of class 0 .. K - 1, half 1 of class 0 .. K - 1]
+    (tvae.align.class_halves): the slot for class k, own class or not, is K + k for an image at an even position of its own
+    class and k at an odd one.  For the own class that is the half that does not contain the image
+    (tvae.refine.cross_half_labels); neither half of another class contains it.  An image outside every class counts as
+    even; a slot outside [0, K) stays -1.  Map a result back with % K."""
+    K = int(n_clusters)
+    cand = torch.as_tensor(candidates).to(torch.int64)
+    own = refine.cross_half_labels(torch.as_tensor(labels).to(cand.device), K)
+    odd = (own >= 0) & (own < K)
+    valid = (cand >= 0) & (cand < K)
+    return torch.where(valid, torch.where(odd[:, None], cand, cand + K), torch.full_like(cand, -1))
+
+
+def classify_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3, angle_range=math.pi / 8, angle_steps=8,
+                    shift=2, mask_radius=None, mask_edge=0.0, cross_halves=False, latents=None, candidates=None):
+    """`rounds` times: the class averages of the current labels and poses (tvae.align.class_averages; with cross_halves=True
+    the two half-set averages of tvae.align.class_halves as 2K references, see cross_half_candidates), the candidate lists
+    of the current labels (candidate_lists with `latents` and m = `candidates`), classify_poses, the labels and poses set to
+    its results, then half the angle step.
+    An empty class has a zero reference, scores exactly 0 against every image and so stays empty unless 0 is the best
+    score an image reaches (every other candidate's cosine negative or undefined): reassignment does not revive a class.
+    -> (labels' int64 [N], theta' [N], dx' [N][2], history): history['steps'] the angle step of every round,
+    history['scores'] fp64 [rounds][2] the mean incumbent-centre score (slot 0) and the mean winning score over the images
+    that were members of a class when the round began, history['moved'] int [rounds] the images whose label changed,
+    history['counts'] int [rounds + 1][K] the class sizes before the first round and after each, and the last round's
+    history['candidates'] int64 [N][M] (classes) with their history['slot_scores'] fp32 [N][M][2]."""
+    what = 'classify_rounds'
+    N, C, n, K, lab = align._check_labels(images, theta, dx, labels, n_clusters, what)
+    A = int(angle_steps)
+    if int(rounds) < 1:
+        raise TvaeHipError(f'{what}: rounds = {rounds} must be positive')
+    th, d = theta.reshape(N).contiguous(), dx
+    lab64 = lab.to(torch.int64)
+    if latents is not None:
+        latents = torch.as_tensor(latents).to(images.device)
+    count = lambda l: torch.bincount(l[(l >= 0) & (l < K)], minlength=K).cpu().numpy()
+    steps, scores, moved, counts = [], [], [], [count(lab64)]
+    cand = sc = None
+    for j in range(int(rounds)):
+        step = float(angle_range) / max(A, 1) / 2 ** j
+        cand = candidate_lists(lab64, K, latents, candidates)
+        if cross_halves:
+            refs = align.class_halves(images, th, d, lab64, K, t_scale)[1].reshape(2 * K, C, n, n)
+            slots = cross_half_candidates(lab64, cand, K)
+        else:
+            refs = align.class_averages(images, th, d, lab64, K, t_scale)[0]
+            slots = cand
+        new, th, d, sc, best = classify_poses(images, th, d, slots, refs, t_scale, A, step, shift, mask_radius, mask_edge)
+        if cross_halves:
+            new = torch.where(new >= 0, new % K, new)
+        member = (lab64 >= 0) & (lab64 < K)
+        win = sc[torch.arange(N, device=sc.device), best[:, 0].to(torch.int64), 1]
+        pair = torch.stack([sc[:, 0, 0], win], 1)[member].double()
+        scores.append(pair.mean(0).cpu().numpy() if pair.numel() else np.zeros(2))
+        moved.append(int((new != lab64).sum()))
+        lab64 = new
+        steps.append(step)
+        counts.append(count(lab64))
+    hist = dict(steps=steps, scores=np.stack(scores), moved=np.asarray(moved, dtype=np.int64), counts=np.stack(counts),
+                candidates=cand, slot_scores=sc)
+    return lab64, th, d, hist
+
+
+def class_scores(candidates, slot_scores, n_clusters):
+    """candidates int64 [N][M] (classes), slot_scores [N][M][2] -> fp32 [N][K] numpy: the best score of every image against
+    every class, NaN where a class was not among its candidates."""
+    cand = torch.as_tensor(candidates).cpu().to(torch.int64)
+    sc = torch.as_tensor(slot_scores).cpu()[:, :, 1]
+    K = int(n_clusters)
+    out = torch.full((cand.shape[0], K), float('nan'), dtype=torch.float32)
+    valid = (cand >= 0) & (cand < K)
+    rows = torch.arange(cand.shape[0])[:, None].expand_as(cand)
+    out[rows[valid], cand[valid]] = sc[valid]
+    return out.numpy()
+
+
+# ---- reclassify_particles.py: new labels, poses and averages from the files a clustering run wrote ----------------------------
+def build_parser() -> argparse.ArgumentParser:
+    base = refine.build_parser()
+    p = argparse.ArgumentParser('Reassign the images of a clustered stack to their best-matching aligned 2-D class average')
+    for a in base._actions:                                  # the flags of refine_poses.py, as it declares them
+        if a.dest != 'help':
+            p._add_action(a)
+    p.add_argument('--latents', default=None, help='latents.npy of the run: the candidates of an image are the classes '
+                                                    'whose centroid is nearest to it')
+    p.add_argument('--candidates', default=None, type=int, help='candidate classes per image, the current one among them '
+                                                                '(at most 64); default: all classes')
+    return p
+
+
+def run(argv=None):
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available() or args.device == -1:
+        raise SystemExit('the MI355X build has no CPU compute path')
+    torch.cuda.set_device(args.device)
+    device = torch.device('cuda', args.device)
+    stack = align.load_stack(args.stack, args.crop)
+    particles = args.stack.endswith('mrc') or args.stack.endswith('mrcs')
+    images = torch.from_numpy(stack).to(device)
+    theta = torch.from_numpy(np.asarray(np.load(args.rotations), dtype=np.float32).reshape(-1)).to(device)
+    dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
+    clusters = np.asarray(np.load(args.clusters)).reshape(-1)
+    latents = None if args.latents is None else np.asarray(np.load(args.latents), dtype=np.float64)
+    t = align.translation_scale(args.t_inf)
+    try:
+        K = align._check_labels(images, theta, dx, clusters, args.n_clusters, 'classify_rounds')[3]
+        before = refine._resolutions(images, theta, dx, clusters, K, t)
+        lab, th, d, hist = classify_rounds(images, theta, dx, clusters, K, t, args.rounds, math.radians(args.angle_range),
+                                           args.angle_steps, args.shift, args.mask_radius, args.mask_edge, args.cross_halves,
+                                           latents, args.candidates)
+        new = lab.cpu().numpy()
+        avg, counts = align.class_averages(images, th, d, new, K, t)
+        after = refine._resolutions(images, th, d, new, K, t)
+    except TvaeHipError as e:
+        raise SystemExit(str(e)) from e
+    os.makedirs(args.out_dir, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(args.out_dir, name), a)
+    save('clusters_reclassified.npy', new)
+    save('rotations_reclassified.npy', th.cpu().numpy().reshape(np.load(args.rotations).shape))
+    save('translations_reclassified.npy', d.cpu().numpy())
+    save('classify_scores.npy', hist['scores'])
+    save('classify_moved.npy', hist['moved'])
+    save('class_scores.npy', class_scores(hist['candidates'], hist['slot_scores'], K))
+    align.save_outputs(args.out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles, 'class_averages_reclassified')
+    print('# class  members before -> after  resolution[px]@0.143 before -> after  resolution[px]@0.5 before -> after')
+    for k in range(K):
+        print('{} {} -> {} {:.4f} -> {:.4f} {:.4f} -> {:.4f}'.format(k, int(hist['counts'][0, k]), int(hist['counts'][-1, k]),
+                                                                    before[k, 0], after[k, 0], before[k, 1], after[k, 1]))
+    print('# reassigned {} images among {} classes, {} rounds, moved {}, mean score {:.6f} -> {:.6f}: {}'.format(
+        images.shape[0], K, args.rounds, hist['moved'].tolist(), hist['scores'][0, 0], hist['scores'][-1, 1], args.out_dir),
+        file=sys.stderr)
+    return lab, th, d, hist

@@ -31,6 +31,12 @@ TVAE_REFINE_POSES=1 refines the run's poses against those averages (tvae.refine:
 its class over a small neighbourhood of angles and whole-pixel shifts, three rounds) -- rotations_refined.npy,
 translations_refined.npy, refine_scores.npy and class_averages_refined.npy (.mrcs, .jpg).  refine_poses.py computes the same
 from the saved .npy files alone.  Unset, nothing changes.
+
+TVAE_RECLASSIFY=1 reassigns the run's images to their best-matching class average (tvae.classify: every image scored against
+its own class and the classes whose latent centroid is nearest, min(K, 8) candidates in all, three rounds of averaging and
+reassigning) -- clusters_reclassified.npy, rotations_reclassified.npy, translations_reclassified.npy, classify_scores.npy,
+classify_moved.npy, class_scores.npy and class_averages_reclassified.npy (.mrcs, .jpg).  reclassify_particles.py computes
+the same from the saved .npy files alone.  Unset, nothing changes.
 """
 from __future__ import annotations
 
@@ -225,6 +231,30 @@ def _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, cluste
     align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), kind == 'particles', 'class_averages_refined')
 
 
+def _reclassify(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values):
+    """TVAE_RECLASSIFY=1: the run's images reassigned to their best-matching class average (tvae.classify, three rounds with
+    the defaults of reclassify_particles.py, the candidates from the run's latents with m = min(K, 8)) and the averages of the
+    new labels and poses."""
+    from . import align, classify
+    print('# reassigning the images to their best-matching class averages ... ', file=sys.stderr)
+    if images.shape[-1] != images.shape[-2]:
+        raise SystemExit('TVAE_RECLASSIFY=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
+    y = images.to(device).float().contiguous()
+    t = align.translation_scale(args.t_inf)
+    K = args.n_clusters
+    lab, th, d, hist = classify.classify_rounds(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(),
+                                                np.asarray(clusters), K, t, latents=z_values, candidates=min(K, 8))
+    new = lab.cpu().numpy()
+    avg, counts = align.class_averages(y, th, d, new, K, t)
+    np.save(os.path.join(out_dir, 'clusters_reclassified.npy'), new)
+    np.save(os.path.join(out_dir, 'rotations_reclassified.npy'), th.cpu().numpy().reshape(tuple(rot_pred.shape)))
+    np.save(os.path.join(out_dir, 'translations_reclassified.npy'), d.cpu().numpy())
+    np.save(os.path.join(out_dir, 'classify_scores.npy'), hist['scores'])
+    np.save(os.path.join(out_dir, 'classify_moved.npy'), hist['moved'])
+    np.save(os.path.join(out_dir, 'class_scores.npy'), classify.class_scores(hist['candidates'], hist['slot_scores'], K))
+    align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), kind == 'particles', 'class_averages_reclassified')
+
+
 def run(kind: str, argv=None):
     args = build_parser(kind).parse_args(argv)
     from src import models  # noqa: F401     (whole-module checkpoints unpickle as src.models.*)
@@ -291,6 +321,8 @@ def run(kind: str, argv=None):
         _class_frc(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
     if os.environ.get('TVAE_REFINE_POSES', '') == '1':
         _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+    if os.environ.get('TVAE_RECLASSIFY', '') == '1':
+        _reclassify(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values)
 
     np.save(os.path.join(out_dir, 'latents.npy'), z_values.cpu().numpy())
     np.save(os.path.join(out_dir, 'rotations.npy'), rot_pred.cpu().numpy())
