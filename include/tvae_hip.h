@@ -341,7 +341,8 @@ int tvae_enc_tail_dgrad_x6(const void* w3p, const void* wh3, const float* dheads
 /* tvae_enc_tail_wgrad_x6 (ABI 3): weight gradient of conv2 in ONE pass, dH never stored (autograd of nn.Conv3d(C, C, 1)
  * behind the 1x1x1 heads, src/models.py:347-358,390-392):  dW2[c2][c] = sum_n dH[c2][n] A1[c][n] with
  * dH[c2][n] = act'(H[c2][n]) sum_h Wh[h][c2] dheads[h][n] formed on the fly from the head gradients and the sign words
- * of H (bits_h, as stored by tvae_enc_tail_fwd_x6; LeakyReLU).  C = 128, nh <= 7, N % 32 == 0, 16-byte aligned rows;
+ * of H (bits_h, as stored by tvae_enc_tail_fwd_x6; LeakyReLU).  C = 128, nh <= 7, N % 32 == 0, 16-byte aligned rows
+ * (lda, ldd: multiples of 4, at least N);
  * ws: tvae_enc_tail_wgrad_x6_ws_floats(N) floats of per-workgroup slabs, added in a fixed order.  (dWh and db2 come from
  * tvae_heads_bwd with dX = NULL.) */
 long tvae_enc_tail_wgrad_x6_ws_floats(long N);

@@ -34,7 +34,7 @@ int tvae_enc_tail_fwd_x6(const void* w3, const float* A1, long lda, const float*
     if (N <= 0) return 0;
     if (parts == 2 && !amax_a1) return (int)hipErrorInvalidValue;        // h3 needs the per-channel maxima of A1 (C words) from A1's producer
     if (C != ET_C || nh < 1 || nh > ET_MAXH || !aligned16(w3) || (parts != 1 && parts != 2 && parts != 3) || !A1 || !heads || !Wh ||       // (H == NULL: inference-mode forward, heads only)
-        !bh || ((bits_h || bits_a) && (act != ACT_LRELU || !aligned16(bits_h) || !aligned16(bits_a))) ||
+        !bh || (!bits_h != !bits_a) || (bits_h && (act != ACT_LRELU || !aligned16(bits_h) || !aligned16(bits_a))) ||      // sign words: both or neither
         !et_ld_ok(N, lda, ldh, ldo))
         return (int)hipErrorInvalidValue;
     const int Rpad = x6_round_up(ET_C, DX6_ROWS);
@@ -76,8 +76,8 @@ int tvae_enc_tail_wgrad_x6(const float* A1, long lda, const float* dheads, long 
                            const float* amax_a1, tvae_stream_t stream) {
     if (N <= 0) return 0;
     if (C != ET_C || nh < 1 || nh > ET_MAXH || N % EW_NC != 0 || !aligned16(A1) || !aligned16(dheads) || !aligned16(bits_h) ||
-        lda % 4 != 0 || ldd % 4 != 0 || (parts != 1 && parts != 2 && parts != 3) || !A1 || !dheads || !bits_h || !Wh || !dW2 ||
-        !ws || ws_floats < tvae_enc_tail_wgrad_x6_ws_floats(N) || (parts == 2 && !amax_a1))
+        lda % 4 != 0 || ldd % 4 != 0 || lda < N || ldd < N || (parts != 1 && parts != 2 && parts != 3) || !A1 || !dheads || !bits_h ||
+        !Wh || !dW2 || !ws || ws_floats < tvae_enc_tail_wgrad_x6_ws_floats(N) || (parts == 2 && !amax_a1))
         return (int)hipErrorInvalidValue;
     const long nchunks = N / EW_NC;
     const int grid = (int)(nchunks < cu_count() ? nchunks : cu_count());
