@@ -28,7 +28,8 @@ typedef void* tvae_stream_t;
 
 #define TVAE_KMEANS_MAX_RESTARTS 65535
 
-/* Still 1: the Ward, t-SNE, alignment, pose-refinement, reassignment, class-statistics, preprocessing and CTF entry points below were
+/* Still 1: the Ward, t-SNE, alignment, pose-refinement, reassignment, class-statistics, preprocessing, CTF and eigenimage entry points below
+ * were
  * ADDED, no existing prototype or meaning changed. */
 int tvae_cluster_abi_version(void);          /* == 1 */
 
@@ -455,6 +456,67 @@ int tvae_fourier_filter(const float* X, long x_stride, const double* coef, const
 /* D[K][n][R] fp64 = sum over the valid members of class k of H_i^2, counts[K] (int32) their number */
 int tvae_ctf_power(const double* coef, const int* order, const int* seg, double* D, int* counts, int N, int K, int n,
                    tvae_stream_t stream);
+
+/* ---- Eigenimages of the aligned classes: the class covariance applied to a block of vectors, no aligned copy --------------
+ *
+ * Shared definitions.  Y[N][C][n][n], theta[N], dx[N][2], t_scale, order[N] and seg[K + 1] exactly as for tvae_class_average
+ * (the section above): the same sampling and zero border, the same out-of-frame rule (exact 0), `order` entries outside
+ * [0, N) are skipped, and seg is replaced on the device by min(max(0, seg[0], ..., seg[k]), N).
+ * mean[K][C][n][n] is the caller's class averages (of tvae_class_average, the avg of tvae_class_halves, or CTF-corrected ones).
+ * V[K][J][C][n][n] is a block of J vectors per class, 1 <= J <= TVAE_EIGEN_MAX_COMPONENTS.
+ * Mask: that of tvae_class_frc at the canonical pixel p = (i, j): the distance from ((n - 1) / 2, (n - 1) / 2) and the mask in
+ * fp64, rounded to fp32 once; mask_radius <= 0 means no mask (m = 1), mask_edge = 0 a hard edge; a non-finite radius or edge
+ * and a negative edge are rejected.  It is built once per call into the workspace.
+ * Residual of position q of `order`, a valid member of class k, at (ch, p):
+ *     a = the bilinear sample of image order[q] (A of the section above),   r = a - mean[k][ch][p]   (an fp32 subtraction),
+ *     d_q(ch, p) = m(p) * r                                                                            (an fp32 product).
+ * An image wholly out of frame has a = 0 exactly, so d = -m * mean rounded once: NaN, +-inf and huge poses included.
+ *
+ * tvae_class_project: coef[q][j] = sum_{ch,p} d_q(ch, p) V[k][j][ch][p] and norm2[q] = sum d_q^2, rows indexed by the POSITION
+ * q in `order`, not by image.  Each is one fp32 FMA chain per thread followed by a fixed tree, the order of yy of
+ * tvae_pose_refine: thread t of 256 takes the pixels t, t + 256, ... of channel 0, then of channel 1, ... in one chain
+ * acc = fma(d, V, acc) (acc = fma(d, d, acc) for norm2) from 0; the 256 partial sums are then added as
+ * s[t] += s[t + w] for w = 128, 64, ..., 1.  The longest chain of additions an output passes through is
+ * C ceil(n n / 256) + 8.  A skipped entry and a position outside the cleaned [seg[0], seg[K]) get a row of exact zeros.  Row q
+ * is a pure function of its image, its pose, mean[k], V[k] and the mask: not of N, K, the other rows or the launch (a workgroup
+ * takes four consecutive positions and reuses V between those of one class; no chain changes with it).
+ *
+ * tvae_class_backproject: W[k][j][ch][p] = sum over the valid positions q of class k of coef[q][j] d_q(ch, p), and counts[k] the
+ * number of valid members.  A class is cut into chunks of tvae_class_eigen_chunk members counted from the class's own first
+ * position (a build constant, 128: four times the chunk of the averages, because a slot holds J planes).  Per chunk and
+ * (j, ch, p) one fp32 chain acc = fma(coef[q][j], d_q, acc) in ascending position from 0, the sample d_q taken once for all
+ * J; a second launch adds the chunks of a class in fp64 in ascending order and rounds to fp32 once.  Chunk c of class k owns
+ * the slot floor(s_k / chunk) + k + c.  An empty class gives zeros.  Every output of class k depends only on class k's ordered
+ * member list, those members' images, poses and coefficients and mean[k]: not on the other classes, not on K.
+ * The workspace holds J C n n floats per slot, N / chunk + K slots: at N = 100 000, K = 10, C = 1, n = 128 and J = 8 that is
+ * 791 slots of 512 KB, 415 MB (the chunk of the averages would take 1.6 GB).
+ *
+ * Both: no atomics, bitwise reproducible; no allocation, no synchronisation.  Supported: the range of tvae_class_average,
+ * 1 <= J <= 16, K J C ceil(n n / 256) < 2^31, the mask rules above, ws 8-byte aligned and at least the queried size, and no
+ * output (coef, norm2, W, counts, the used part of ws) overlapping an input or another output.  Anything else returns
+ * hipErrorInvalidValue (1) and writes nothing, and the queries return 0. */
+
+#define TVAE_EIGEN_MAX_COMPONENTS 16
+
+/* floats of workspace of tvae_class_project: the cleaned seg (K + 1 int32 words, padded to a multiple of 4) and the mask
+ * (n n).  0 for unsupported arguments. */
+long tvae_class_project_ws_floats(int N, int K, int C, int n, int J);
+/* floats of workspace of tvae_class_backproject: the cleaned seg and one member count per slot (int32 words, padded to a
+ * multiple of 4), the mask (n n) and J C n n partial sums for each of N / chunk + K slots.  0 for unsupported arguments. */
+long tvae_class_backproject_ws_floats(int N, int K, int C, int n, int J);
+/* members per chunk of tvae_class_backproject (a constant of the build, 128).  0 for unsupported arguments. */
+int tvae_class_eigen_chunk(int N, int K, int C, int n, int J);
+
+/* coef[N][J], norm2[N] (may be NULL): rows by position in `order` */
+int tvae_class_project(const float* Y, const float* theta, const float* dx, const int* order, const int* seg,
+                       const float* mean, const float* V, float* coef, float* norm2, float* ws, long ws_floats, int N, int C,
+                       int n, int K, int J, float t_scale, float mask_radius, float mask_edge, tvae_stream_t stream);
+
+/* W[K][J][C][n][n], counts[K] (int32); coef[N][J] by position in `order`, as tvae_class_project writes it */
+int tvae_class_backproject(const float* Y, const float* theta, const float* dx, const int* order, const int* seg,
+                           const float* mean, const float* coef, float* W, int* counts, float* ws, long ws_floats, int N,
+                           int C, int n, int K, int J, float t_scale, float mask_radius, float mask_edge,
+                           tvae_stream_t stream);
 
 #ifdef __cplusplus
 }

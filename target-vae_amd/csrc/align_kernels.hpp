@@ -27,7 +27,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "cluster_common.hpp"
+#include "cluster_common.hpp"         // AlignPose and align_sample: shared with the eigenimage kernels
 
 namespace tvae_cluster {
 
@@ -35,25 +35,8 @@ constexpr int ALIGN_TILE = 256;          // pixels per workgroup = threads per w
 constexpr int AVG_CHUNK = 32;            // members of a class per partial sum
 constexpr int ALIGN_C_MAX = 1024;        // channels
 
-struct AlignPose {
-    float c, s, tx, ty;                  // cos, sin, t * dx0, t * dx1
-};
-
 static inline int align_tiles(int n) { return (n * n + ALIGN_TILE - 1) / ALIGN_TILE; }
 static inline long avg_slots(int N, int K) { return (long)N / AVG_CHUNK + K; }
-
-// Bilinear sample of img[n][n] at the canonical pixel (i, j) under `p`; `on` = false gives 0 without reading anything else
-// than in-bounds words.
-__device__ __forceinline__ float align_sample(const float* __restrict__ img, int n, int i, int j, float step, float half,
-                                              const AlignPose p, bool on) {
-    const float u0 = fmaf((float)j, step, -1.f);
-    const float u1 = fmaf(-(float)i, step, 1.f);
-    const float x0 = fmaf(u0, p.c, fmaf(u1, p.s, p.tx));
-    const float x1 = fmaf(-u0, p.s, fmaf(u1, p.c, p.ty));
-    const float col = (x0 + 1.f) * half;
-    const float row = (1.f - x1) * half;
-    return bilinear_zero_border(img, n, col, row, on);        // (cluster_common.hpp: shared with the pose refinement)
-}
 
 // grid = N * C * tiles (tile fastest).  out[N][C][n][n]
 __global__ __launch_bounds__(ALIGN_TILE) void align_stack_kernel(const float* __restrict__ Y,

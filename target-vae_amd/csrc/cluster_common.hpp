@@ -63,6 +63,23 @@ __device__ __forceinline__ float bilinear_zero_border(const float* __restrict__ 
     return fmaf(wr, bot - top, top);
 }
 
+// The pose of an image in the convention of align_kernels.hpp, and the bilinear sample of img[n][n] at the canonical pixel
+// (i, j) under it; `on` = false gives 0 without reading anything else than in-bounds words.
+struct AlignPose {
+    float c, s, tx, ty;                  // cos, sin, t * dx0, t * dx1
+};
+
+__device__ __forceinline__ float align_sample(const float* __restrict__ img, int n, int i, int j, float step, float half,
+                                              const AlignPose p, bool on) {
+    const float u0 = fmaf((float)j, step, -1.f);
+    const float u1 = fmaf(-(float)i, step, 1.f);
+    const float x0 = fmaf(u0, p.c, fmaf(u1, p.s, p.tx));
+    const float x1 = fmaf(-u0, p.s, fmaf(u1, p.c, p.ty));
+    const float col = (x0 + 1.f) * half;
+    const float row = (1.f - x1) * half;
+    return bilinear_zero_border(img, n, col, row, on);
+}
+
 // The mask at d pixels from the centre for radius > 0: 1 within `radius`, a raised cosine over `edge`, 0 beyond.
 __device__ __forceinline__ float soft_mask(double d, float radius, float edge) {
     const double r = (double)radius, e = (double)edge;

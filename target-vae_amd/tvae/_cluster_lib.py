@@ -1,5 +1,5 @@
 """ctypes binding of libtvae_cluster.so (C ABI declared in include/tvae_cluster.h): the batched k-means, Ward
-linkage, t-SNE, alignment, pose-refinement, reassignment and class-statistics kernels.
+linkage, t-SNE, alignment, pose-refinement, reassignment, class-statistics and eigenimage kernels.
 
 A library of its own beside libtvae_hip.so -- the ABI of the training kernels (tvae._lib.SIGNATURES, version 7) is not
 touched by the clustering half.  Same rules: no CPU fallback, tensors are checked by tvae._lib._ptr (GPU, contiguous,
@@ -53,6 +53,12 @@ SIGNATURES = {
     # Y, theta, dx, cand (int32), ref, cls_out (int32), best (int32), theta_out, dx_out, score, num, pp, yy (or None all three),
     # ws, ws_floats, N, C, n, K, M, A, S, t_scale, dtheta, mask_radius, mask_edge
     'tvae_pose_classify': 'ppppp' 'ppppp' 'ppp' 'p' 'l' 'iiiiiii' 'ffff',
+    # Y, theta, dx, order (int32), seg (int32), mean, V, coef, norm2 (or None), ws, ws_floats, N, C, n, K, J, t_scale,
+    # mask_radius, mask_edge
+    'tvae_class_project': 'ppppp' 'pp' 'pp' 'p' 'l' 'iiiii' 'fff',
+    # Y, theta, dx, order (int32), seg (int32), mean, coef, W, counts (int32), ws, ws_floats, N, C, n, K, J, t_scale,
+    # mask_radius, mask_edge
+    'tvae_class_backproject': 'ppppp' 'pp' 'pp' 'p' 'l' 'iiiii' 'fff',
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
@@ -72,6 +78,9 @@ QUERIES = {
     'tvae_fourier_filter_ws_floats': ('ii', 'l'),
     'tvae_pose_refine_ws_floats': ('iiiii', 'l'),
     'tvae_pose_classify_ws_floats': ('iiiiii', 'l'),
+    'tvae_class_project_ws_floats': ('iiiii', 'l'),
+    'tvae_class_backproject_ws_floats': ('iiiii', 'l'),
+    'tvae_class_eigen_chunk': ('iiiii', 'i'),
 }
 
 # the shape limits every image family shares (SIDE_MAX, PLANES_MAX, CLASSES_MAX of csrc/cluster_common.hpp)

@@ -37,6 +37,12 @@ its own class and the classes whose latent centroid is nearest, min(K, 8) candid
 reassigning) -- clusters_reclassified.npy, rotations_reclassified.npy, translations_reclassified.npy, classify_scores.npy,
 classify_moved.npy, class_scores.npy and class_averages_reclassified.npy (.mrcs, .jpg).  reclassify_particles.py computes
 the same from the saved .npy files alone.  Unset, nothing changes.
+
+TVAE_CLASS_EIGEN=1 describes how the members of a class differ from their average (tvae.eigen: the leading eigenimages of
+every class under the default soft mask, the coordinates of every image along them and its residual norm) --
+class_eigenimages.npy (.mrcs for particles, .jpg with matplotlib), class_eigenvalues.npy, eigen_coordinates.npy,
+eigen_residual.npy and class_eigen.txt.  class_eigenimages.py computes the same from the saved .npy files alone.  Unset,
+nothing changes.
 """
 from __future__ import annotations
 
@@ -213,6 +219,19 @@ def _class_frc(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
     resolution.save_outputs(out_dir, res)
 
 
+def _class_eigen(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters):
+    """TVAE_CLASS_EIGEN=1: eigenimages, coordinates and residual norms of the run's classes (tvae.eigen with the defaults of
+    class_eigenimages.py), from the same images, poses and clusters as the class averages."""
+    from . import align, eigen
+    print('# saving class eigenimages, coordinates and residual norms ... ', file=sys.stderr)
+    if images.shape[-1] != images.shape[-2]:
+        raise SystemExit('TVAE_CLASS_EIGEN=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
+    y = images.to(device).float().contiguous()
+    res = eigen.class_eigenimages(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(), np.asarray(clusters),
+                                  args.n_clusters, t_scale=align.translation_scale(args.t_inf))
+    eigen.save_outputs(out_dir, res, particles=kind == 'particles')
+
+
 def _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters):
     """TVAE_REFINE_POSES=1: the run's poses refined against its class averages (tvae.refine, three rounds with the defaults
     of refine_poses.py) and the averages of the refined poses, from the same images, poses and clusters as the class averages."""
@@ -319,6 +338,8 @@ def run(kind: str, argv=None):
         _class_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
     if os.environ.get('TVAE_CLASS_FRC', '') == '1':
         _class_frc(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+    if os.environ.get('TVAE_CLASS_EIGEN', '') == '1':
+        _class_eigen(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
     if os.environ.get('TVAE_REFINE_POSES', '') == '1':
         _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
     if os.environ.get('TVAE_RECLASSIFY', '') == '1':

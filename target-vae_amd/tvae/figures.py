@@ -187,3 +187,25 @@ def save_class_variance(out_dir, variance, counts):
     plt.savefig(path, bbox_inches='tight')
     plt.close(fig)
     return path
+
+
+def save_class_eigenimages(out_dir, eigenimages, eigenvalues, counts):
+    """Montage of the eigenimages [K][J][C][n][n] (averaged over the channels): one row per class, one panel per component on
+    a scale symmetric about 0, titled with the class, the component and its eigenvalue."""
+    plt = _plt()
+    eig, lam = np.asarray(eigenimages, dtype=np.float64), np.asarray(eigenvalues, dtype=np.float64)
+    counts = np.asarray(counts).reshape(-1)
+    K, J = eig.shape[:2]
+    fig, axes = plt.subplots(K, J, figsize=(2 * J, 2.3 * K), squeeze=False)
+    for k in range(K):
+        for j in range(J):
+            ax = axes[k][j]
+            ax.axis('off')
+            a = eig[k, j].mean(0)
+            top = np.abs(a).max() or 1.0                          # (a zero eigenimage: rank below J)
+            ax.imshow(a, cmap='gray', vmin=-top, vmax=top)
+            ax.set_title('{} ({}) / {}: {:.3g}'.format(k, int(counts[k]), j, lam[k, j]), fontsize=8)
+    path = os.path.join(out_dir, 'class_eigenimages.jpg')
+    plt.savefig(path, bbox_inches='tight')
+    plt.close(fig)
+    return path
