@@ -28,8 +28,8 @@ typedef void* tvae_stream_t;
 
 #define TVAE_KMEANS_MAX_RESTARTS 65535
 
-/* Still 1: the Ward, t-SNE, alignment, pose-refinement, reassignment, class-statistics, preprocessing, CTF and eigenimage entry points below
- * were
+/* Still 1: the Ward, t-SNE, alignment, pose-refinement, reassignment, class-statistics, preprocessing, CTF, eigenimage and
+ * maximum-likelihood entry points below were
  * ADDED, no existing prototype or meaning changed. */
 int tvae_cluster_abi_version(void);          /* == 1 */
 
@@ -517,6 +517,81 @@ int tvae_class_backproject(const float* Y, const float* theta, const float* dx, 
                            const float* mean, const float* coef, float* W, int* counts, float* ws, long ws_floats, int N,
                            int C, int n, int K, int J, float t_scale, float mask_radius, float mask_edge,
                            tvae_stream_t stream);
+
+/* ---- Maximum-likelihood class averages: the posterior over the candidates and the weighted aligned average -------------------
+ *
+ * The soft form of the averaging loop.  tvae_pose_classify gives every image one class and one pose, the arg-max; here every
+ * image contributes to every (class, pose) it is compatible with, with its posterior weight under white Gaussian noise of
+ * variance sigma2 per pixel.  The tables num, pp [N][M][NA][NS][NS], yy [N] and cand [N][M] are those of tvae_pose_classify
+ * (NA = 2A + 1, NS = 2S + 1), theta, dx, n, t_scale and dtheta its poses and grid; logprior[K] (fp64) the log prior of every
+ * class, NULL meaning 0 for all of them.
+ *
+ * tvae_pose_posterior.  Candidates: j = ((m NA + a') NS + sy') NS + sx' with a' = a + A, sy' = sy + S, sx' = sx + S, J = M NA NS^2
+ * of them per image.  In fp64, every operation rounded on its own,
+ *     r_j = ((double)yy - 2 (double)num_j) + (double)pp_j        (the squared residual |Y - P_j|^2),
+ *     h = 0.5 / (double)sigma2,      l_j = logprior[cand[i][m]] - r_j h.
+ * A candidate is LIVE if cand[i][m] is inside [0, K) and l_j is finite: a -inf prior, a NaN table entry and an invalid slot take
+ * it out.  With L the maximum of the live l_j and e_j = exp(l_j - L) (0 for a candidate that is not live):
+ *     E_m = sum of e_j over slot m,   R_m = sum of e_j r_j over slot m,   Z = sum_m E_m,   w_j = e_j / Z,
+ *     lse[i] = L + log Z,    r2[i] = (sum_m R_m) / Z  (= sum_j w_j r_j),    resp[i][m] = (float)(E_m / Z).
+ * Order of addition, a function of (M, A, S) only: within slot m thread t of 256 adds the candidates c = t, t + 256, ... of the
+ * slot (c = j - m NA NS^2) in one chain from 0, the 256 sums are then added by a binary tree (t and t + 128, then t and t + 64,
+ * ...), the order of yy of tvae_pose_refine; Z and sum R_m add the slots in ascending m.  Everything is fp64; resp is rounded
+ * to fp32 once.
+ * Selection: the live candidates ranked by l descending, then j ascending; the first P' = min(P, live) are kept, W = the sum of
+ * their w_j in rank order.  For the kept rank p: ent_idx[i][p] = j, ent_cls[i][p] = cand[i][m], ent_w[i][p] = (float)(w_j / W),
+ * and ent_theta[i][p], ent_dx[i][p] the pose of the candidate (a, sy, sx) by the pose update of tvae_pose_refine, bit for bit
+ * what tvae_pose_classify writes for that candidate (an index that is 0 copies its part of the pose bit for bit);
+ * kept[i] = (float)W.  For the ranks p >= P': ent_idx = ent_cls = -1, ent_w = 0 and the pose is the image's own, bit for bit.
+ * An image with no live candidate gets lse = r2 = kept = 0, zeros in resp and empty entries only.
+ * One workgroup per image; l_j stays in LDS for J <= 4096 and is formed again by the same operations otherwise: the same bits.
+ * No atomics; every output is bitwise reproducible, and the outputs of image i depend on its own rows only.
+ *
+ * Supported: 1 <= N <= 2^24, 2 <= n <= 128, 1 <= K <= 65535, 1 <= M <= 64, 0 <= A <= 32, 0 <= S <= 8 (the range of
+ * tvae_pose_classify), 1 <= P <= TVAE_POSTERIOR_MAX_KEEP, t_scale and sigma2 finite and > 0, dtheta finite, logprior (where
+ * given), lse and r2 8-byte aligned, and no output overlapping an input or another output.  Anything else returns
+ * hipErrorInvalidValue (1) and writes nothing.
+ *
+ * tvae_class_average_weighted.  E entries, already grouped by class: class k is the entries [seg[k], seg[k + 1]), seg[K + 1]
+ * cleaned on the device as for tvae_class_average with E as the upper bound, min(max(0, seg[0], ..., seg[k]), E).  Entry e
+ * resamples image img[e] of Y[N][C][n][n] at the pose (theta_e[e], dx_e[e][2]) with the sampling, the zero border and the
+ * out-of-frame rule of tvae_class_average (a_e, exact zeros out of frame), and carries the weight w[e].  An entry is LIVE if
+ * img[e] is inside [0, N) and w[e] is finite and > 0; an entry that is not contributes to nothing and nothing of Y is read for
+ * it.  A live entry whose pose is out of frame (NaN, +-inf and huge poses among them) contributes exact zeros to the sum and
+ * its weight to the denominator, as an out-of-frame member counts in tvae_class_average.
+ * A class is cut into chunks of tvae_class_average_weighted_chunk entries (a build constant, 128: E is several times N and a
+ * slot is one C n n plane) counted from the class's own first entry; chunk c of class k owns the slot
+ * floor(s_k / chunk) + k + c.  Per chunk and (ch, pixel) one fp32 chain acc = fma(w_e, a_e, acc) in ascending e from 0; per
+ * chunk the fp64 sum of the live weights in ascending e, and the live count.  A second launch adds a class's chunks in ascending
+ * order in fp64, S over the chains and W_k over the weights, and writes
+ *     avg[k] = (float)(S / W_k) (zeros where W_k = 0),    wsum[k] = W_k (fp64),    counts[k] = the live entries.
+ * No atomics; every output is bitwise reproducible, and the outputs of class k depend on class k's own entry list and the
+ * images it names only: not on K, not on the other classes.
+ *
+ * Supported: 1 <= E <= 2^30, N, C, n and K as for tvae_class_average (1 <= N <= 2^24, 1 <= C <= 1024, 2 <= n <= 1024,
+ * 1 <= K <= 65535, N C ceil(n n / 256) < 2^31), (E / chunk + K) C ceil(n n / 256) < 2^31, ws at least the queried size, ws and
+ * wsum 8-byte aligned, no output (the used part of ws is one) overlapping an input or another output.  Anything else returns
+ * hipErrorInvalidValue (1) and writes nothing, and the queries return 0. */
+
+#define TVAE_POSTERIOR_MAX_KEEP 64
+
+/* ent_idx, ent_cls [N][P] (int32), ent_theta [N][P], ent_dx [N][P][2], ent_w [N][P], resp [N][M], lse [N] and r2 [N] (fp64),
+ * kept [N] */
+int tvae_pose_posterior(const float* num, const float* pp, const float* yy, const int* cand, const double* logprior,
+                        const float* theta, const float* dx, int* ent_idx, int* ent_cls, float* ent_theta, float* ent_dx,
+                        float* ent_w, float* resp, double* lse, double* r2, float* kept, int N, int n, int K, int M, int A,
+                        int S, int P, float t_scale, float dtheta, float sigma2, tvae_stream_t stream);
+
+/* floats of workspace of tvae_class_average_weighted: the cleaned seg and one live count per chunk slot (int32 words, padded to
+ * a multiple of 4), one fp64 weight sum per slot and the partial sums of E / chunk + K slots.  0 for unsupported arguments. */
+long tvae_class_average_weighted_ws_floats(int E, int K, int C, int n);
+/* entries per chunk (a constant of the build, 128).  0 for unsupported arguments. */
+int tvae_class_average_weighted_chunk(int E, int K, int C, int n);
+
+/* avg[K][C][n][n], wsum[K] (fp64), counts[K] (int32); ws holds tvae_class_average_weighted_ws_floats(E, K, C, n) floats */
+int tvae_class_average_weighted(const float* Y, const int* img, const float* theta_e, const float* dx_e, const float* w,
+                                const int* seg, float* avg, double* wsum, int* counts, float* ws, long ws_floats, int N, int E,
+                                int C, int n, int K, float t_scale, tvae_stream_t stream);
 
 #ifdef __cplusplus
 }

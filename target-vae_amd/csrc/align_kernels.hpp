@@ -95,18 +95,10 @@ struct AvgChunk {
         const long rest = block / tiles;
         ch = (int)(rest % C);
         slot = (int)(rest / C);
-        // the class whose slots contain `slot`: the largest k with clean[k] / AVG_CHUNK + k <= slot (strictly increasing in k)
-        int lo = 0, hi = K - 1;
-        if (clean[0] / AVG_CHUNK > slot) return false;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (clean[mid] / AVG_CHUNK + mid <= slot) lo = mid; else hi = mid - 1;
-        }
-        const int k = lo;
-        const int sk = clean[k], ek = clean[k + 1];
-        const int first = sk + (slot - (sk / AVG_CHUNK + k)) * AVG_CHUNK;
-        if (first >= ek) return false;                        // a slot that no chunk owns: nobody reads it either
-        members = min(AVG_CHUNK, ek - first);
+        ChunkSpan span;
+        if (!chunk_of_slot(clean, K, slot, AVG_CHUNK, span)) return false;   // a slot that no chunk owns
+        const int first = span.first;
+        members = span.members;
         if (threadIdx.x < AVG_CHUNK) {
             int id = -1;
             AlignPose q = {0.f, 0.f, 0.f, 0.f};

@@ -80,6 +80,34 @@ __device__ __forceinline__ float align_sample(const float* __restrict__ img, int
     return bilinear_zero_border(img, n, col, row, on);
 }
 
+// ---- the chunks of a class and their workspace slots --------------------------------------------------------------------------
+// THE statement of the slot numbering of the class averages, the eigenimages and the weighted averages.  `clean` is a monotone
+// seg[K + 1]; class k = the positions [s_k, e_k) is cut into chunks of `chunk` positions counted from s_k, and chunk c owns the
+// slot floor(s_k / chunk) + k + c: slots of different classes never collide, and there are at most total / chunk + K of them.
+// chunk_of_slot finds the chunk that owns `slot`: its class, its first position and its length.  false for a slot that no
+// chunk owns (nobody reads such a slot either); the answer depends on `slot` and `clean` alone, so it is uniform over a
+// workgroup whose slot comes from blockIdx.  `chunk` is a constant at every call site: the divisions are by a constant.
+struct ChunkSpan {
+    int k, first, members;
+};
+
+__device__ __forceinline__ bool chunk_of_slot(const int* __restrict__ clean, int K, int slot, int chunk, ChunkSpan& out) {
+    // the class whose slots contain `slot`: the largest k with clean[k] / chunk + k <= slot (strictly increasing in k)
+    int lo = 0, hi = K - 1;
+    if (clean[0] / chunk > slot) return false;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (clean[mid] / chunk + mid <= slot) lo = mid; else hi = mid - 1;
+    }
+    const int sk = clean[lo], ek = clean[lo + 1];
+    const int first = sk + (slot - (sk / chunk + lo)) * chunk;
+    if (first >= ek) return false;
+    out.k = lo;
+    out.first = first;
+    out.members = min(chunk, ek - first);
+    return true;
+}
+
 // The mask at d pixels from the centre for radius > 0: 1 within `radius`, a raised cosine over `edge`, 0 beyond.
 __device__ __forceinline__ float soft_mask(double d, float radius, float edge) {
     const double r = (double)radius, e = (double)edge;

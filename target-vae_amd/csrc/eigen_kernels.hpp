@@ -195,19 +195,10 @@ __global__ __launch_bounds__(EIGEN_TILE) void eigen_accum_kernel(
     const long rest = blockIdx.x / tiles;
     const int ch = (int)(rest % C);
     const int slot = (int)(rest / C);
-    // the class whose slots contain `slot`: the largest k with clean[k] / EIGEN_CHUNK + k <= slot (strictly increasing in k).
-    // Both returns depend on blockIdx and `clean` alone: uniform, and in front of every barrier.
-    int lo = 0, hi = K - 1;
-    if (clean[0] / EIGEN_CHUNK > slot) return;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (clean[mid] / EIGEN_CHUNK + mid <= slot) lo = mid; else hi = mid - 1;
-    }
-    const int k = lo;
-    const int sk = clean[k], ek = clean[k + 1];
-    const int first = sk + (slot - (sk / EIGEN_CHUNK + k)) * EIGEN_CHUNK;
-    if (first >= ek) return;                                  // a slot that no chunk owns: nobody reads it either
-    const int members = min(EIGEN_CHUNK, ek - first);
+    // The return depends on blockIdx and `clean` alone: uniform, and in front of every barrier.
+    ChunkSpan span;
+    if (!chunk_of_slot(clean, K, slot, EIGEN_CHUNK, span)) return;       // a slot that no chunk owns
+    const int k = span.k, first = span.first, members = span.members;
     if (tid < EIGEN_CHUNK) {
         int id = -1;
         if (tid < members) {

@@ -1,5 +1,5 @@
 """ctypes binding of libtvae_cluster.so (C ABI declared in include/tvae_cluster.h): the batched k-means, Ward
-linkage, t-SNE, alignment, pose-refinement, reassignment, class-statistics and eigenimage kernels.
+linkage, t-SNE, alignment, pose-refinement, reassignment, class-statistics, eigenimage and maximum-likelihood kernels.
 
 A library of its own beside libtvae_hip.so -- the ABI of the training kernels (tvae._lib.SIGNATURES, version 7) is not
 touched by the clustering half.  Same rules: no CPU fallback, tensors are checked by tvae._lib._ptr (GPU, contiguous,
@@ -59,6 +59,11 @@ SIGNATURES = {
     # Y, theta, dx, order (int32), seg (int32), mean, coef, W, counts (int32), ws, ws_floats, N, C, n, K, J, t_scale,
     # mask_radius, mask_edge
     'tvae_class_backproject': 'ppppp' 'pp' 'pp' 'p' 'l' 'iiiii' 'fff',
+    # num, pp, yy, cand (int32), logprior (fp64, or None), theta, dx, ent_idx, ent_cls (int32 both), ent_theta, ent_dx, ent_w, resp,
+    # lse, r2 (fp64 both), kept, N, n, K, M, A, S, P, t_scale, dtheta, sigma2
+    'tvae_pose_posterior': 'ppppp' 'pp' 'ppppp' 'pppp' 'iiiiiii' 'fff',
+    # Y, img (int32), theta_e, dx_e, w, seg (int32), avg, wsum (fp64), counts (int32), ws, ws_floats, N, E, C, n, K, t_scale
+    'tvae_class_average_weighted': 'pppppp' 'pppp' 'l' 'iiiii' 'f',
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
@@ -81,6 +86,8 @@ QUERIES = {
     'tvae_class_project_ws_floats': ('iiiii', 'l'),
     'tvae_class_backproject_ws_floats': ('iiiii', 'l'),
     'tvae_class_eigen_chunk': ('iiiii', 'i'),
+    'tvae_class_average_weighted_ws_floats': ('iiii', 'l'),
+    'tvae_class_average_weighted_chunk': ('iiii', 'i'),
 }
 
 # the shape limits every image family shares (SIDE_MAX, PLANES_MAX, CLASSES_MAX of csrc/cluster_common.hpp)

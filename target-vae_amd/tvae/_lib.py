@@ -305,6 +305,8 @@ _F64_OK |= {('tvae_class_frc', 3)}
 _F64_OK |= {('tvae_image_normalize', 2)}
 # ... and the coefficient rows of the CTF entry points and the power sums of tvae_ctf_power
 _F64_OK |= {('tvae_ctf_eval', 0), ('tvae_fourier_filter', 2), ('tvae_ctf_power', 0), ('tvae_ctf_power', 3)}
+# ... and the log priors, log-likelihoods and mean residuals of tvae_pose_posterior and the weight sums of the weighted average
+_F64_OK |= {('tvae_pose_posterior', 4), ('tvae_pose_posterior', 13), ('tvae_pose_posterior', 14), ('tvae_class_average_weighted', 7)}
 
 
 def _ptr(t, name, pos):

@@ -38,6 +38,12 @@ reassigning) -- clusters_reclassified.npy, rotations_reclassified.npy, translati
 classify_moved.npy, class_scores.npy and class_averages_reclassified.npy (.mrcs, .jpg).  reclassify_particles.py computes
 the same from the saved .npy files alone.  Unset, nothing changes.
 
+TVAE_ML_AVERAGES=1 replaces the arg-max of that loop by its maximum-likelihood form (tvae.ml2d: every image contributes to
+every class and pose it is compatible with, with its posterior weight; the same min(K, 8) candidates, three rounds, eight
+entries per image, the noise variance and the class priors re-estimated every round) -- class_averages_ml.npy (.mrcs, .jpg),
+class_weights.npy, clusters_ml.npy, rotations_ml.npy, translations_ml.npy, ml_log_likelihood.npy, ml_sigma2.npy and
+ml_entropy.npy.  ml_class_averages.py computes the same from the saved .npy files alone.  Unset, nothing changes.
+
 TVAE_CLASS_EIGEN=1 describes how the members of a class differ from their average (tvae.eigen: the leading eigenimages of
 every class under the default soft mask, the coordinates of every image along them and its residual norm) --
 class_eigenimages.npy (.mrcs for particles, .jpg with matplotlib), class_eigenvalues.npy, eigen_coordinates.npy,
@@ -274,6 +280,30 @@ def _reclassify(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters
     align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), kind == 'particles', 'class_averages_reclassified')
 
 
+def _ml_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values):
+    """TVAE_ML_AVERAGES=1: the maximum-likelihood class averages of the run (tvae.ml2d, three rounds with the defaults of
+    ml_class_averages.py, the candidates from the run's latents with m = min(K, 8)), the labels and top-1 poses they imply."""
+    from . import align, ml2d
+    print('# maximum-likelihood class averages: soft assignment over classes and poses ... ', file=sys.stderr)
+    if images.shape[-1] != images.shape[-2]:
+        raise SystemExit('TVAE_ML_AVERAGES=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
+    y = images.to(device).float().contiguous()
+    t = align.translation_scale(args.t_inf)
+    K = args.n_clusters
+    avg, wsum, lab, th, d, hist = ml2d.ml_rounds(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(),
+                                                 np.asarray(clusters), K, t, latents=z_values, candidates=min(K, 8))
+    new = lab.cpu().numpy()
+    np.save(os.path.join(out_dir, 'class_weights.npy'), wsum.cpu().numpy())
+    np.save(os.path.join(out_dir, 'clusters_ml.npy'), new)
+    np.save(os.path.join(out_dir, 'rotations_ml.npy'), th.cpu().numpy().reshape(tuple(rot_pred.shape)))
+    np.save(os.path.join(out_dir, 'translations_ml.npy'), d.cpu().numpy())
+    np.save(os.path.join(out_dir, 'ml_log_likelihood.npy'), hist['log_likelihood'])
+    np.save(os.path.join(out_dir, 'ml_sigma2.npy'), hist['sigma2'])
+    np.save(os.path.join(out_dir, 'ml_entropy.npy'), hist['entropy'].cpu().numpy())
+    counts = np.bincount(new[(new >= 0) & (new < K)], minlength=K)
+    align.save_outputs(out_dir, avg.cpu().numpy(), counts, kind == 'particles', 'class_averages_ml')
+
+
 def run(kind: str, argv=None):
     args = build_parser(kind).parse_args(argv)
     from src import models  # noqa: F401     (whole-module checkpoints unpickle as src.models.*)
@@ -344,6 +374,8 @@ def run(kind: str, argv=None):
         _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
     if os.environ.get('TVAE_RECLASSIFY', '') == '1':
         _reclassify(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values)
+    if os.environ.get('TVAE_ML_AVERAGES', '') == '1':
+        _ml_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values)
 
     np.save(os.path.join(out_dir, 'latents.npy'), z_values.cpu().numpy())
     np.save(os.path.join(out_dir, 'rotations.npy'), rot_pred.cpu().numpy())
