@@ -28,8 +28,8 @@ typedef void* tvae_stream_t;
 
 #define TVAE_KMEANS_MAX_RESTARTS 65535
 
-/* Still 1: the Ward, t-SNE, alignment, pose-refinement, reassignment, class-statistics, preprocessing, CTF, eigenimage and
- * maximum-likelihood entry points below were
+/* Still 1: the Ward, t-SNE, alignment, pose-refinement, reassignment, pose-polish, class-statistics, preprocessing, CTF,
+ * eigenimage and maximum-likelihood entry points below were
  * ADDED, no existing prototype or meaning changed. */
 int tvae_cluster_abi_version(void);          /* == 1 */
 
@@ -286,6 +286,84 @@ int tvae_pose_classify(const float* Y, const float* theta, const float* dx, cons
                        int* best, float* theta_out, float* dx_out, float* score, float* num, float* pp, float* yy, float* ws,
                        long ws_floats, int N, int C, int n, int K, int M, int A, int S, float t_scale, float dtheta,
                        float mask_radius, float mask_edge, tvae_stream_t stream);
+
+/* ---- Sub-pixel pose polish against the class averages: Gauss-Newton on the cosine score ---------------------------------
+ *
+ * The grid searches above leave a translation error of up to half a pixel per axis.  The polish is the continuous local
+ * step after them: Levenberg-Marquardt on || Y - alpha P(theta, t dx) ||^2, whose minimum over alpha is the maximum of the
+ * cosine score.  One evaluation (tvae_pose_moments) renders ONE template per image with its derivatives and reduces them
+ * to 15 sums; the bookkeeping (tvae_pose_polish_step) is a thread per image in fp64 on those sums, so the host loop is
+ * launches only:  moments(start) -> step(first = 1) -> [moments(trial) -> step(first = 0)] x iterations.
+ * Y, theta, dx, cls, ref, t_scale, mask_radius and mask_edge as for tvae_pose_refine.
+ *
+ * tvae_pose_moments.  For image i with k = cls[i], at every pixel (r, q) of the frame: the position (u0, u1), (col, row) of
+ * tvae_pose_refine's template at A = 0, S = 0 -- the same fp32 arithmetic, operation for operation -- and with it the same
+ * bilinear sample B of ref[k][ch] (zero border; exact 0 out of frame) and the same mask m(u).  With the taps a00, a01 (row
+ * floor), a10, a11 (row floor + 1) of that sample, already zeroed by the border rule, and its weights wc, wr:
+ *     top = a00 + wc (a01 - a00),  bot = a10 + wc (a11 - a10),  B = top + wr (bot - top),
+ *     Bc = (1 - wr) (a01 - a00) + wr (a11 - a10),   Br = bot - top:
+ * the derivatives of the SAME cell that produced the sample, exact 0 where the sample is the out-of-frame 0.  With
+ * h = (n - 1) / 2 the basis functions on the frame are
+ *     P = m B,   G0 = m h Bc  (dP / du0),   G1 = -m h Br  (dP / du1),   Dtheta = -u1 G0 + u0 G1   (0 out of frame).
+ * The mask is held CONSTANT under the derivative, deliberately: the direction is quasi-Newton, acceptance uses the exact
+ * score, and a hard edge has no derivative anyway.
+ * mom[i][0 .. 14], sums over channels and pixels:  PP, P Dtheta, P G0, P G1, Dtheta Dtheta, Dtheta G0, Dtheta G1, G0 G0, G0 G1,
+ * G1 G1;  P Y, Dtheta Y, G0 Y, G1 Y;  Y Y.  mom[i][0] and mom[i][10] are pp and num of the centre candidate of tvae_pose_refine
+ * (A = 0, S = 0) up to the order of addition, and mom[i][14] is its yy bit for bit.
+ * Order of addition, that of yy in tvae_pose_refine: thread t of 256 takes the pixels t, t + 256, ... of channel 0, then of
+ * channel 1, ..., one fmaf chain per sum; then a binary tree over the 256 sums (t and t + 128, then t and t + 64, ...).  No
+ * atomics, bitwise reproducible; row i is a function of image i, its pose and ref[cls[i]] only, not of N or K.
+ * An image with cls outside [0, K) gets 15 exact zeros and nothing of ref is read for it; a pose that puts every sample out
+ * of frame (NaN, +-inf, huge) gives zeros in the first 14 sums and the true yy.
+ * Supported: 1 <= N <= 2^24, 1 <= C <= 16, 2 <= n <= 128, 1 <= K <= 65535, t_scale finite and > 0, the mask rules of
+ * tvae_pose_refine; mom may not overlap an input.  Anything else returns hipErrorInvalidValue (1) and writes nothing.
+ *
+ * tvae_pose_polish_step.  State per image, all in the caller's arrays: the start pose theta0, dx0 (input: the centre of the
+ * trust region), the current pose theta_out, dx_out with its moments mom_cur and score[i] = (start, current), the damping
+ * lambda (fp64), the trial pose theta_try, dx_try, whose moments the caller puts into mom_try before every call, the number
+ * of accepted steps and the flag `ended`.  Every operation below is fp64, rounded on its own, in the order written.
+ *   first != 0 (mom_try holds the moments of the start pose): current <- start, mom_cur <- mom_try, both scores <- its score,
+ *     lambda <- 1e-3, steps <- 0.  An image with cls outside [0, K) or a start score that is not finite gets the scores
+ *     (0, 0), trial = current = start bit for bit and ended = 1.
+ *   first == 0: an ended image is left alone entirely.  Otherwise the trial is accepted iff its score is finite and
+ *     STRICTLY greater than the current one: trial -> current (pose, moments, score[i][1]), lambda <- lambda / 4, steps + 1;
+ *     if not, lambda <- 8 lambda.
+ *   Score: PY / sqrt(PP YY) in fp64 from the fp32 sums, exactly 0 where PP or YY is 0 (tvae_pose_refine's rule), compared
+ *     in fp64 -- near the optimum two poses differ by less than an fp32 step of the cosine -- and rounded to fp32 only
+ *     where it is stored in `score`.  The current score is formed again from mom_cur at every call.
+ *   Next trial, from the moments of the current pose.  c and s: the cosine and sine of the fp32 theta evaluated in fp64 and
+ *     rounded to fp32 once (the correctly rounded cosf / sinf, so that a host restatement has the same bits), as doubles;
+ *     (Dtx, Dty) = (-c G0 - s G1, s G0 - c G1), the derivatives along t dx; their sums:
+ *       P Dtx = -(c PG0) - s PG1,  P Dty = s PG0 - c PG1,  and the same for Dtheta and for Y in the place of P;
+ *       DtxDtx = (c c) G0G0 + (2 (c s)) G0G1 + (s s) G1G1,   DtyDty = (s s) G0G0 - (2 (c s)) G0G1 + (c c) G1G1,
+ *       DtxDty = ((c c - s s) G0G1 - (c s) G0G0) + (c s) G1G1      (sums left to right).
+ *     alpha = PY / PP.  Unknowns x = (dtheta, dtx, dty, dalpha) of || Y - alpha P ||^2, J = [alpha Dtheta, alpha Dtx,
+ *     alpha Dty, P]:  M = J^T J with M[a][b] = (alpha alpha) <Da Db> for a, b < 3, M[a][3] = alpha <P Da>, M[3][3] = PP;
+ *     rhs[a] = alpha (<Da Y> - alpha <P Da>), rhs[3] = PY - alpha PP; then M[a][a] <- M[a][a] + lambda M[a][a].
+ *     Gaussian elimination with partial pivoting: for column k = 0 .. 3 the pivot is the first row r >= k of the largest
+ *     |M[r][k]| (rows swapped); for r > k: f = M[r][k] / M[k][k], M[r][j] <- M[r][j] - f M[k][j] for j > k,
+ *     rhs[r] <- rhs[r] - f rhs[k]; back substitution x[i] = (rhs[i] - M[i][i+1] x[i+1] - ... ) / M[i][i], subtracted in
+ *     ascending j.  PP = 0, YY = 0, a zero or non-finite pivot or a non-finite solution mean "no step".
+ *     New pose: theta + dtheta, dx + (dtx, dty) / t_scale in fp64, clamped per component to the trust region
+ *     [centre - radius, centre + radius] (centre the start pose; radius max_angle for theta and
+ *     ((max_shift * 2) / (n - 1)) / t_scale for dx), rounded to fp32 once; a rounded value outside the region is moved one
+ *     fp32 step towards the centre.  A trial that is not finite is "no step".
+ *   A trial equal to the current pose bit for bit ("no step" among it) ends the image: ended = 1.
+ * After the last call theta_out, dx_out, score and steps are the result; score[i][1] >= score[i][0] always.
+ * Supported: 1 <= N <= 2^24, 2 <= n <= 128, 1 <= K <= 65535, t_scale finite and > 0, max_shift (pixels) and max_angle
+ * (radians) finite and >= 0; lambda 8-byte aligned; none of the nine state arrays (theta_try .. ended) may overlap another or
+ * an input.  Anything else returns hipErrorInvalidValue (1) and writes nothing. */
+
+/* mom[N][15] */
+int tvae_pose_moments(const float* Y, const float* theta, const float* dx, const int* cls, const float* ref, float* mom, int N,
+                      int C, int n, int K, float t_scale, float mask_radius, float mask_edge, tvae_stream_t stream);
+
+/* cls[N] (int32), theta0[N], dx0[N][2], mom_try[N][15]: inputs.  theta_try[N], dx_try[N][2], theta_out[N], dx_out[N][2],
+ * mom_cur[N][15], score[N][2], lambda[N] (fp64), steps[N], ended[N] (int32): the state, written by the first call */
+int tvae_pose_polish_step(const int* cls, const float* theta0, const float* dx0, const float* mom_try, float* theta_try,
+                          float* dx_try, float* theta_out, float* dx_out, float* mom_cur, float* score, double* lambda,
+                          int* steps, int* ended, int N, int n, int K, int first, float t_scale, float max_shift,
+                          float max_angle, tvae_stream_t stream);
 
 /* ---- Quality of the class averages: half sets, variance maps and the Fourier ring correlation ---------------------------
  *

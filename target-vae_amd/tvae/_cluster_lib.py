@@ -1,5 +1,5 @@
 """ctypes binding of libtvae_cluster.so (C ABI declared in include/tvae_cluster.h): the batched k-means, Ward
-linkage, t-SNE, alignment, pose-refinement, reassignment, class-statistics, eigenimage and maximum-likelihood kernels.
+linkage, t-SNE, alignment, pose-refinement, reassignment, pose-polish, class-statistics, eigenimage and maximum-likelihood kernels.
 
 A library of its own beside libtvae_hip.so -- the ABI of the training kernels (tvae._lib.SIGNATURES, version 7) is not
 touched by the clustering half.  Same rules: no CPU fallback, tensors are checked by tvae._lib._ptr (GPU, contiguous,
@@ -53,6 +53,11 @@ SIGNATURES = {
     # Y, theta, dx, cand (int32), ref, cls_out (int32), best (int32), theta_out, dx_out, score, num, pp, yy (or None all three),
     # ws, ws_floats, N, C, n, K, M, A, S, t_scale, dtheta, mask_radius, mask_edge
     'tvae_pose_classify': 'ppppp' 'ppppp' 'ppp' 'p' 'l' 'iiiiiii' 'ffff',
+    # Y, theta, dx, cls (int32), ref, mom, N, C, n, K, t_scale, mask_radius, mask_edge
+    'tvae_pose_moments': 'pppppp' 'iiii' 'fff',
+    # cls (int32), theta0, dx0, mom_try, theta_try, dx_try, theta_out, dx_out, mom_cur, score, lambda (fp64), steps, ended (int32
+    # both), N, n, K, first, t_scale, max_shift, max_angle
+    'tvae_pose_polish_step': 'pppp' 'pp' 'ppppppp' 'iiii' 'fff',
     # Y, theta, dx, order (int32), seg (int32), mean, V, coef, norm2 (or None), ws, ws_floats, N, C, n, K, J, t_scale,
     # mask_radius, mask_edge
     'tvae_class_project': 'ppppp' 'pp' 'pp' 'p' 'l' 'iiiii' 'fff',

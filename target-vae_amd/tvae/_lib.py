@@ -307,6 +307,8 @@ _F64_OK |= {('tvae_image_normalize', 2)}
 _F64_OK |= {('tvae_ctf_eval', 0), ('tvae_fourier_filter', 2), ('tvae_ctf_power', 0), ('tvae_ctf_power', 3)}
 # ... and the log priors, log-likelihoods and mean residuals of tvae_pose_posterior and the weight sums of the weighted average
 _F64_OK |= {('tvae_pose_posterior', 4), ('tvae_pose_posterior', 13), ('tvae_pose_posterior', 14), ('tvae_class_average_weighted', 7)}
+# ... and the damping factors of tvae_pose_polish_step
+_F64_OK |= {('tvae_pose_polish_step', 10)}
 
 
 def _ptr(t, name, pos):

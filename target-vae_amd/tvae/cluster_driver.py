@@ -32,6 +32,12 @@ its class over a small neighbourhood of angles and whole-pixel shifts, three rou
 translations_refined.npy, refine_scores.npy and class_averages_refined.npy (.mrcs, .jpg).  refine_poses.py computes the same
 from the saved .npy files alone.  Unset, nothing changes.
 
+TVAE_POLISH_POSES=1 polishes the poses to sub-pixel accuracy against the class averages (tvae.polish: a few Levenberg-Marquardt
+steps per image on the cosine score, inside a trust region of one pixel and 0.05 rad; it starts from the refined poses when
+TVAE_REFINE_POSES=1 is set as well, else from the run's own) -- rotations_polished.npy, translations_polished.npy,
+polish_scores.npy, polish_steps.npy and class_averages_polished.npy (.mrcs, .jpg).  polish_poses.py computes the same from the
+saved .npy files alone.  Unset, nothing changes.
+
 TVAE_RECLASSIFY=1 reassigns the run's images to their best-matching class average (tvae.classify: every image scored against
 its own class and the classes whose latent centroid is nearest, min(K, 8) candidates in all, three rounds of averaging and
 reassigning) -- clusters_reclassified.npy, rotations_reclassified.npy, translations_reclassified.npy, classify_scores.npy,
@@ -254,6 +260,27 @@ def _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, cluste
     np.save(os.path.join(out_dir, 'translations_refined.npy'), d.cpu().numpy())
     np.save(os.path.join(out_dir, 'refine_scores.npy'), hist['scores'])
     align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), kind == 'particles', 'class_averages_refined')
+    return th, d
+
+
+def _polish_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, start=None):
+    """TVAE_POLISH_POSES=1: the poses polished to sub-pixel accuracy against the class averages (tvae.polish, one round with the
+    defaults of polish_poses.py) and the averages of the polished poses.  `start`: the refined poses (theta, dx) where
+    TVAE_REFINE_POSES=1 ran before, else the run's own."""
+    from . import align, polish
+    print('# polishing the poses against the class averages ... ', file=sys.stderr)
+    if images.shape[-1] != images.shape[-2]:
+        raise SystemExit('TVAE_POLISH_POSES=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
+    y = images.to(device).float().contiguous()
+    t = align.translation_scale(args.t_inf)
+    th0, d0 = start if start is not None else (rot_pred.float().contiguous(), tr_pred.float().contiguous())
+    th, d, hist = polish.polish_rounds(y, th0, d0, np.asarray(clusters), args.n_clusters, t)
+    avg, counts = align.class_averages(y, th, d, np.asarray(clusters), args.n_clusters, t)
+    np.save(os.path.join(out_dir, 'rotations_polished.npy'), th.cpu().numpy().reshape(tuple(rot_pred.shape)))
+    np.save(os.path.join(out_dir, 'translations_polished.npy'), d.cpu().numpy())
+    np.save(os.path.join(out_dir, 'polish_scores.npy'), hist['image_scores'])
+    np.save(os.path.join(out_dir, 'polish_steps.npy'), hist['image_steps'])
+    align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), kind == 'particles', 'class_averages_polished')
 
 
 def _reclassify(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values):
@@ -370,8 +397,11 @@ def run(kind: str, argv=None):
         _class_frc(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
     if os.environ.get('TVAE_CLASS_EIGEN', '') == '1':
         _class_eigen(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+    refined = None
     if os.environ.get('TVAE_REFINE_POSES', '') == '1':
-        _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+        refined = _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+    if os.environ.get('TVAE_POLISH_POSES', '') == '1':
+        _polish_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, refined)
     if os.environ.get('TVAE_RECLASSIFY', '') == '1':
         _reclassify(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values)
     if os.environ.get('TVAE_ML_AVERAGES', '') == '1':
