@@ -110,8 +110,7 @@ long tvae_class_frc_ws_floats(int P, int n) { return frc_shape_ok(P, n) ? P * fr
 int tvae_class_frc(const float* a, const float* b, float* frc, double* sums, float* ws, long ws_floats, int P, int n,
                    float mask_radius, float mask_edge, tvae_stream_t stream) {
     if (!frc_shape_ok(P, n) || !a || !b || !frc || !sums || !ws) return (int)hipErrorInvalidValue;
-    if (!finite(mask_radius) || !finite(mask_edge) || mask_edge < 0.f)
-        return (int)hipErrorInvalidValue;
+    if (!mask_ok(mask_radius, mask_edge)) return (int)hipErrorInvalidValue;
     if (ws_floats < P * frc_plane_floats(n) || !aligned8(ws)) return (int)hipErrorInvalidValue;
     const int H = half_side(n);
     float2* G = reinterpret_cast<float2*>(ws);                // [P][2][n][H] complex

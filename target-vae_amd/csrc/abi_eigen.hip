@@ -17,30 +17,6 @@ static bool eigen_shape_ok(long N, long K, long C, long n, long J) {
     return K * J * C * tiles <= GRID_MAX;                  // eigen_reduce_kernel; eigen_accum_kernel has fewer than the line above
 }
 
-static bool mask_ok(float radius, float edge) { return finite(radius) && finite(edge) && edge >= 0.f; }
-
-// [a, a + an) and [b, b + bn) in bytes share a byte
-static bool overlap(const void* a, size_t an, const void* b, size_t bn) {
-    const size_t x = reinterpret_cast<size_t>(a), y = reinterpret_cast<size_t>(b);
-    return a && b && x < y + bn && y < x + an;
-}
-
-struct Span {
-    const void* p;
-    size_t bytes;
-};
-
-template <int NO, int NI>
-static bool outputs_clear(const Span (&out)[NO], const Span (&in)[NI]) {
-    for (int o = 0; o < NO; ++o) {
-        for (int i = 0; i < NI; ++i)
-            if (overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes)) return false;
-        for (int o2 = o + 1; o2 < NO; ++o2)
-            if (overlap(out[o].p, out[o].bytes, out[o2].p, out[o2].bytes)) return false;
-    }
-    return true;
-}
-
 // workspace of tvae_class_project: (K + 1) cleaned boundaries (int32, padded to a multiple of 4 words), then the mask [n][n]
 static long project_ws_ints(int K) { return ((long)K + 1 + 3) / 4 * 4; }
 // workspace of tvae_class_backproject: (K + 1) cleaned boundaries and one member count per slot (int32, padded to a multiple

@@ -10,8 +10,8 @@ using namespace tvae_cluster;
 
 // the range of tvae_pose_classify (abi_classify.hip) without its channels, and P
 static bool posterior_shape_ok(long N, long n, long K, long M, long A, long S, long P) {
-    return N >= 1 && N <= PLANES_MAX && M >= 1 && M <= POST_M_MAX && n >= 2 && n <= REFINE_SIDE_MAX && A >= 0 &&
-           A <= REFINE_A_MAX && S >= 0 && S <= REFINE_S_MAX && K >= 1 && K <= CLASSES_MAX && P >= 1 && P <= POST_KEEP_MAX;
+    return refine_shape_ok(N, 1, n, A, S) && M >= 1 && M <= POST_M_MAX && K >= 1 && K <= CLASSES_MAX && P >= 1 &&
+           P <= POST_KEEP_MAX;
 }
 
 // the range of tvae_class_average (abi_align.hip) with E entries in the place of its N members
@@ -29,28 +29,6 @@ static long wavg_ws_need(long E, int K, int C, int n) {
     return wavg_ws_ints(E, K) + 2 * slots + slots * C * n * n;
 }
 
-// [a, a + an) and [b, b + bn) in bytes share a byte
-static bool overlap(const void* a, size_t an, const void* b, size_t bn) {
-    const size_t x = reinterpret_cast<size_t>(a), y = reinterpret_cast<size_t>(b);
-    return a && b && x < y + bn && y < x + an;
-}
-
-struct Span {
-    const void* p;
-    size_t bytes;
-};
-
-template <int NO, int NI>
-static bool outputs_clear(const Span (&out)[NO], const Span (&in)[NI]) {
-    for (int o = 0; o < NO; ++o) {
-        for (int i = 0; i < NI; ++i)
-            if (overlap(out[o].p, out[o].bytes, in[i].p, in[i].bytes)) return false;
-        for (int o2 = o + 1; o2 < NO; ++o2)
-            if (overlap(out[o].p, out[o].bytes, out[o2].p, out[o2].bytes)) return false;
-    }
-    return true;
-}
-
 extern "C" {
 
 int tvae_pose_posterior(const float* num, const float* pp, const float* yy, const int* cand, const double* logprior,
@@ -65,7 +43,7 @@ int tvae_pose_posterior(const float* num, const float* pp, const float* yy, cons
         return (int)hipErrorInvalidValue;
     if (!aligned8(lse) || !aligned8(r2) || !aligned8(logprior)) return (int)hipErrorInvalidValue;
     const size_t f = sizeof(float), d = sizeof(double), Ns = (size_t)N;
-    const size_t table = Ns * M * (2 * A + 1) * (2 * S + 1) * (2 * S + 1) * f, ent = Ns * P * f;
+    const size_t table = Ns * M * refine_cand(A, S) * f, ent = Ns * P * f;
     const Span in[] = {{num, table}, {pp, table}, {yy, Ns * f}, {cand, Ns * M * f}, {logprior, (size_t)K * d},
                        {theta, Ns * f}, {dx, 2 * Ns * f}};
     const Span out[] = {{ent_idx, ent}, {ent_cls, ent}, {ent_theta, ent}, {ent_dx, 2 * ent}, {ent_w, ent},

@@ -7,24 +7,6 @@
 
 using namespace tvae_cluster;
 
-static bool refine_shape_ok(long N, long C, long n, long A, long S) {
-    return N >= 1 && N <= PLANES_MAX && C >= 1 && C <= REFINE_C_MAX && n >= 2 && n <= REFINE_SIDE_MAX && A >= 0 &&
-           A <= REFINE_A_MAX && S >= 0 && S <= REFINE_S_MAX;      // (N NA workgroups: at most 2^24 * 65 < 2^31)
-}
-
-// candidates of an image
-static long refine_cand(int A, int S) { return (2L * A + 1) * (2 * S + 1) * (2 * S + 1); }
-
-// [lo, hi) of `count` four-byte words
-struct RefineRange {
-    size_t lo, hi;
-};
-static RefineRange range_of(const void* p, long count) {
-    const size_t lo = reinterpret_cast<size_t>(p);
-    return {lo, lo + (p ? 4 * (size_t)count : 0)};
-}
-static bool overlap(RefineRange a, RefineRange b) { return a.lo < b.hi && b.lo < a.hi; }
-
 template <int S>
 static int refine_launch(const float* Y, const float* theta, const float* dx, const int* cls, const float* ref, float* num,
                          float* pp, float* yy, int N, int C, int n, int K, int A, float t_scale, float dtheta,
@@ -54,40 +36,23 @@ int tvae_pose_refine(const float* Y, const float* theta, const float* dx, const 
         return (int)hipErrorInvalidValue;
     if ((num == nullptr) != (pp == nullptr)) return (int)hipErrorInvalidValue;
     if (!finite(t_scale) || !(t_scale > 0.f) || !finite(dtheta)) return (int)hipErrorInvalidValue;
-    if (!finite(mask_radius) || !finite(mask_edge) || mask_edge < 0.f) return (int)hipErrorInvalidValue;
+    if (!mask_ok(mask_radius, mask_edge)) return (int)hipErrorInvalidValue;
     const long cand = refine_cand(A, S), plane = (long)C * n * n;
     if (ws_floats < (long)N * (2 * cand + 1)) return (int)hipErrorInvalidValue;
-    const RefineRange in[5] = {range_of(Y, N * plane), range_of(theta, N), range_of(dx, 2L * N), range_of(cls, N),
-                               range_of(ref, K * plane)};
-    const RefineRange out[8] = {range_of(theta_out, N), range_of(dx_out, 2L * N), range_of(score, 2L * N),
-                                range_of(best, 3L * N), range_of(num, N * cand), range_of(pp, N * cand),
-                                range_of(yy, N),         range_of(ws, (long)N * (2 * cand + 1))};
-    for (const RefineRange& o : out)
-        for (const RefineRange& i : in)
-            if (overlap(o, i)) return (int)hipErrorInvalidValue;
+    const size_t f = sizeof(float), Ns = (size_t)N, table = Ns * cand * f;
+    const Span in[] = {{Y, Ns * plane * f}, {theta, Ns * f}, {dx, 2 * Ns * f}, {cls, Ns * f}, {ref, (size_t)K * plane * f}};
+    const Span out[] = {{theta_out, Ns * f}, {dx_out, 2 * Ns * f}, {score, 2 * Ns * f}, {best, 3 * Ns * f}, {num, table},
+                        {pp, table}, {yy, Ns * f}, {ws, 2 * table + Ns * f}};
+    if (!outputs_off_inputs(out, in)) return (int)hipErrorInvalidValue;
     // the tables are the caller's where it asks for them, the workspace's [num | pp | yy] otherwise
     float* numt = num ? num : ws;
     float* ppt = pp ? pp : ws + (long)N * cand;
     float* yyt = yy ? yy : ws + 2L * N * cand;
     hipStream_t s = tvae_cluster::S(stream);                  // (the shift radius hides the helper's name here)
-    int rc = (int)hipErrorInvalidValue;
-    switch (S) {
-#define TVAE_REFINE_CASE(SV)                                                                                            \
-    case SV:                                                                                                            \
-        rc = refine_launch<SV>(Y, theta, dx, cls, ref, numt, ppt, yyt, N, C, n, K, A, t_scale, dtheta, mask_radius,     \
-                               mask_edge, s);                                                                           \
-        break;
-        TVAE_REFINE_CASE(0)
-        TVAE_REFINE_CASE(1)
-        TVAE_REFINE_CASE(2)
-        TVAE_REFINE_CASE(3)
-        TVAE_REFINE_CASE(4)
-        TVAE_REFINE_CASE(5)
-        TVAE_REFINE_CASE(6)
-        TVAE_REFINE_CASE(7)
-        TVAE_REFINE_CASE(8)
-#undef TVAE_REFINE_CASE
-    }
+    const int rc = refine_by_shift(S, [&](auto sv) {
+        return refine_launch<decltype(sv)::value>(Y, theta, dx, cls, ref, numt, ppt, yyt, N, C, n, K, A, t_scale, dtheta,
+                                                  mask_radius, mask_edge, s);
+    });
     if (rc != 0) return rc;
     refine_select_kernel<<<(unsigned)((N + REFINE_TILE - 1) / REFINE_TILE), REFINE_TILE, 0, s>>>(
         theta, dx, cls, numt, ppt, yyt, theta_out, dx_out, score, best, N, n, K, A, S, t_scale, dtheta);

@@ -1,5 +1,6 @@
-// What the kernel families of libtvae_cluster.so share: the launch check, the host-side argument tests, the shape limits,
-// the DFT twiddle table and the fragment conventions of the fp32 MFMA.  Host and device code, and NO __global__ function:
+// What the kernel families of libtvae_cluster.so share: the launch check, the host-side argument tests that do not belong
+// to one family (finite, the mask, the byte spans of the pointer arguments and their overlap rules; the shape range of the
+// pose searches is refine_device.hpp's), the shape limits, the DFT twiddle table and the fragment conventions of the fp32 MFMA.  Host and device code, and NO __global__ function:
 // a non-template kernel is emitted by every unit that sees its definition (abi_common.hpp), so a header that any unit of the
 // library may include -- this one -- must not define one.  That is the difference from align_kernels.hpp and the other
 // *_kernels.hpp, each of which exactly one unit may see.  It does not include abi_common.hpp either: that header carries the
@@ -23,6 +24,34 @@ constexpr long GRID_MAX = 0x7fffffffL;   // workgroups along x of one launch
 static inline hipStream_t S(tvae_stream_t s) { return (hipStream_t)s; }
 static inline bool aligned8(const void* p) { return (reinterpret_cast<size_t>(p) & 7) == 0; }
 static inline bool finite(float x) { return x - x == 0.f; }            // false for NaN and +-inf
+static inline bool mask_ok(float radius, float edge) { return finite(radius) && finite(edge) && edge >= 0.f; }
+
+// A pointer argument and the bytes the call reads or writes behind it.  A null pointer -- an optional argument that was left
+// away; the required ones are tested before -- overlaps nothing.
+struct Span {
+    const void* p;
+    size_t bytes;
+};
+static inline bool overlap(Span a, Span b) {
+    const size_t x = reinterpret_cast<size_t>(a.p), y = reinterpret_cast<size_t>(b.p);
+    return a.p && b.p && x < y + b.bytes && y < x + a.bytes;
+}
+// no output shares a byte with an input
+template <int NO, int NI>
+static inline bool outputs_off_inputs(const Span (&out)[NO], const Span (&in)[NI]) {
+    for (const Span& o : out)
+        for (const Span& i : in)
+            if (overlap(o, i)) return false;
+    return true;
+}
+// ... and no two outputs share one either
+template <int NO, int NI>
+static inline bool outputs_clear(const Span (&out)[NO], const Span (&in)[NI]) {
+    for (int a = 0; a < NO; ++a)
+        for (int b = a + 1; b < NO; ++b)
+            if (overlap(out[a], out[b])) return false;
+    return outputs_off_inputs(out, in);
+}
 // (allow_big_lds of abi_common.hpp)
 template <class KernelT>
 static hipError_t allow_big_lds(KernelT kernel, size_t bytes) {

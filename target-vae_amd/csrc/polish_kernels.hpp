@@ -109,14 +109,8 @@ __global__ __launch_bounds__(REFINE_TILE) void polish_moments_kernel(
         for (int e = tid; e < n * n; e += REFINE_TILE) {
             const int r = e / n, q = e - r * n;
             const float y = Yp[e];
-            // the position arithmetic of refine_build_template<0>
-            const float x0 = fmaf((float)q, step, -1.f);
-            const float x1 = fmaf(-(float)r, step, 1.f);
-            const float v0 = x0 - p.tx, v1 = x1 - p.ty;
-            const float u0 = fmaf(v0, p.c, -mul_rn(v1, p.s));
-            const float u1 = fmaf(v0, p.s, mul_rn(v1, p.c));
-            const float col = mul_rn(u0 + 1.f, half);
-            const float row = mul_rn(1.f - u1, half);
+            const RefinePosition at = refine_position(q, r, step, half, p);
+            const float u0 = at.u0, u1 = at.u1, col = at.col, row = at.row;
             const bool in = inside_frame(col, row, n);
             const BilinearJet b = bilinear_zero_border_jet(plane, n, rstride, col, row, in);
             float P = b.v, hc = mul_rn(half, b.bc), hr = mul_rn(half, b.br);

@@ -2,9 +2,14 @@
 // (image, angle, reference) -- the extended template, the sliding-ring correlation, the separable sum of T^2 -- and what one
 // thread does to pick an image's candidate.  refine_kernels.hpp (one reference per image) and classify_kernels.hpp (M
 // candidate references per image) call them, so a slot of tvae_pose_classify is tvae_pose_refine bit for bit by construction.
-// Host and device code and NO __global__ function (cluster_common.hpp says why): both kernel headers include this one.
+// The host part states the shape range of a pose search once, for abi_refine.hip, abi_classify.hip, abi_ml2d.hip and
+// abi_polish.hip, and dispatches over the shift radius.
+// Host and device code and NO __global__ function (cluster_common.hpp says why): the kernel headers of the pose searches
+// include this one.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "cluster_common.hpp"
 
@@ -26,6 +31,32 @@ constexpr int REFINE_C_MAX = 16;
 constexpr int REFINE_A_MAX = 32;
 constexpr int REFINE_S_MAX = 8;
 
+// ---- host: the range of a pose search, its candidates per (image, reference), the dispatch over the shift radius ------------
+static inline bool refine_shape_ok(long N, long C, long n, long A, long S) {
+    return N >= 1 && N <= PLANES_MAX && C >= 1 && C <= REFINE_C_MAX && n >= 2 && n <= REFINE_SIDE_MAX && A >= 0 &&
+           A <= REFINE_A_MAX && S >= 0 && S <= REFINE_S_MAX;      // (N NA workgroups: at most 2^24 * 65 < 2^31)
+}
+static inline long refine_cand(int A, int S) { return (2L * A + 1) * (2 * S + 1) * (2 * S + 1); }
+
+// launch(std::integral_constant<int, S>) for the S in 0 .. REFINE_S_MAX that was asked for: the kernels take S as a template
+// argument.  -> what `launch` returns, or hipErrorInvalidValue for another S.
+template <class Launch>
+static inline int refine_by_shift(int S, Launch&& launch) {
+    switch (S) {
+        case 0: return launch(std::integral_constant<int, 0>{});
+        case 1: return launch(std::integral_constant<int, 1>{});
+        case 2: return launch(std::integral_constant<int, 2>{});
+        case 3: return launch(std::integral_constant<int, 3>{});
+        case 4: return launch(std::integral_constant<int, 4>{});
+        case 5: return launch(std::integral_constant<int, 5>{});
+        case 6: return launch(std::integral_constant<int, 6>{});
+        case 7: return launch(std::integral_constant<int, 7>{});
+        case 8: return launch(std::integral_constant<int, 8>{});
+    }
+    return (int)hipErrorInvalidValue;
+}
+
+// ---- device -----------------------------------------------------------------------------------------------------------------
 // row stride of a plane of `side` columns in LDS: odd
 __host__ __device__ static inline int refine_stride(int side) { return side | 1; }
 
@@ -52,6 +83,25 @@ __device__ __forceinline__ RefinePose refine_angle_pose(const float* __restrict_
     return p;
 }
 
+// Where the pixel at column q and row r of the image frame (q, r may lie outside it: the extended template) reads the
+// reference under the pose p: (u0, u1) in coordinate units and (col, row) in pixels of the reference.  THE position arithmetic
+// of the pose searches: refine_build_template and polish_moments_kernel both call it, so the template of the polish is that of
+// refinement at A = 0, S = 0 bit for bit by construction.
+struct RefinePosition {
+    float u0, u1, col, row;
+};
+__device__ __forceinline__ RefinePosition refine_position(int q, int r, float step, float half, RefinePose p) {
+    const float x0 = fmaf((float)q, step, -1.f);
+    const float x1 = fmaf(-(float)r, step, 1.f);
+    const float v0 = x0 - p.tx, v1 = x1 - p.ty;
+    RefinePosition at;
+    at.u0 = fmaf(v0, p.c, -mul_rn(v1, p.s));
+    at.u1 = fmaf(v0, p.s, mul_rn(v1, p.c));
+    at.col = mul_rn(at.u0 + 1.f, half);
+    at.row = mul_rn(1.f - at.u1, half);
+    return at;
+}
+
 // ys [n][ystride] = the plane Yp [n][n]
 __device__ __forceinline__ void refine_load_plane(float* __restrict__ ys, const float* __restrict__ Yp, int n, int ystride,
                                                   int tid) {
@@ -70,18 +120,12 @@ __device__ __forceinline__ void refine_build_template(float* __restrict__ ts, co
     const bool masked = mask_radius > 0.f;
     for (int e = tid; e < ne * ne; e += REFINE_TILE) {
         const int re = e / ne, qe = e - re * ne;
-        const float x0 = fmaf((float)(qe - S), step, -1.f);
-        const float x1 = fmaf(-(float)(re - S), step, 1.f);
-        const float v0 = x0 - p.tx, v1 = x1 - p.ty;
-        const float u0 = fmaf(v0, p.c, -mul_rn(v1, p.s));
-        const float u1 = fmaf(v0, p.s, mul_rn(v1, p.c));
-        const float col = mul_rn(u0 + 1.f, half);
-        const float row = mul_rn(1.f - u1, half);
-        float v = bilinear_zero_border(Rp, n, col, row, true);
+        const RefinePosition at = refine_position(qe - S, re - S, step, half, p);
+        float v = bilinear_zero_border(Rp, n, at.col, at.row, true);
         if (masked) {
             // out of frame (NaN and +-inf among it) stays an exact 0 whatever the mask would be there
-            const bool in = inside_frame(col, row, n);
-            const double d = sqrt((double)u0 * (double)u0 + (double)u1 * (double)u1) * (0.5 * (double)(n - 1));
+            const bool in = inside_frame(at.col, at.row, n);
+            const double d = sqrt((double)at.u0 * (double)at.u0 + (double)at.u1 * (double)at.u1) * (0.5 * (double)(n - 1));
             v = in ? mul_rn(soft_mask(d, mask_radius, mask_edge), v) : 0.f;
         }
         ts[re * tstride + qe] = v;

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _cluster_lib as CL
+from . import stack_cli
 from ._lib import TvaeHipError
 
 MAX_IMAGES = CL.MAX_PLANES
@@ -226,17 +227,8 @@ def load_ctf_coefficients(path, n_images, scale=1):
 def build_parser(ctf=False) -> argparse.ArgumentParser:
     """ctf=True adds the CTF flags (what class_averages.py parses); the default is the parser without them."""
     p = argparse.ArgumentParser('Aligned 2-D class averages of a clustered stack')
-    p.add_argument('--stack', required=True, help='the images (.npy, .mrc or .mrcs): [N][n][n] or [N][C][n][n]')
-    p.add_argument('--rotations', required=True, help='rotations.npy of the clustering run')
-    p.add_argument('--translations', required=True, help='translations.npy of the clustering run')
-    p.add_argument('--clusters', required=True, help='clusters.npy of the clustering run')
-    p.add_argument('--t-inf', default='attention', choices=['unimodal', 'attention'],
-                   help='translation inference of the run: chooses the scale of the translations (1 or 0.1)')
-    p.add_argument('--crop', default=0, type=int, help='central crop, as the clustering run applied it')
-    p.add_argument('--n-clusters', default=None, type=int, help='default: the largest label + 1')
-    p.add_argument('--out-dir', default='.', help='where class_averages.npy, class_counts.npy and the figure go')
-    p.add_argument('--write-aligned', action='store_true', help='also write the aligned images, aligned.npy')
-    p.add_argument('-d', '--device', type=int, default=0)
+    stack_cli.add_stack_flags(p, own=lambda q: q.add_argument('--write-aligned', action='store_true',
+                                                              help='also write the aligned images, aligned.npy'))
     if ctf:
         add_ctf_flags(p, ('wiener', 'flip'))
     return p
@@ -261,18 +253,9 @@ def load_stack(path, crop=0):
 
 def run(argv=None):
     args = build_parser(ctf=True).parse_args(argv)
-    if not torch.cuda.is_available() or args.device == -1:
-        raise SystemExit('the MI355X build has no CPU compute path')
-    torch.cuda.set_device(args.device)
-    device = torch.device('cuda', args.device)
-    stack = load_stack(args.stack, args.crop)
-    particles = args.stack.endswith('mrc') or args.stack.endswith('mrcs')
-    images = torch.from_numpy(stack).to(device)
-    theta = torch.from_numpy(np.asarray(np.load(args.rotations), dtype=np.float32).reshape(-1)).to(device)
-    dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
-    clusters = np.asarray(np.load(args.clusters)).reshape(-1)
-    t = translation_scale(args.t_inf)
-    try:
+    inp = stack_cli.open_inputs(args, stack_cli.make_device(args))
+    images, theta, dx, clusters, particles, t = inp.images, inp.theta, inp.dx, inp.clusters, inp.particles, inp.t_scale
+    with stack_cli.hip_errors():
         avg, counts = class_averages(images, theta, dx, clusters, args.n_clusters, t)
         aligned = align_stack(images, theta, dx, t) if args.write_aligned else None
         corrected = None
@@ -281,8 +264,6 @@ def run(argv=None):
             coef = load_ctf_coefficients(args.ctf, images.shape[0], args.scale)
             corrected = ctf.class_averages_ctf(images, theta, dx, clusters, coef, args.n_clusters, t, args.ctf_correct,
                                                args.wiener_tau)
-    except TvaeHipError as e:
-        raise SystemExit(str(e)) from e
     os.makedirs(args.out_dir, exist_ok=True)
     save_outputs(args.out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles)
     if corrected is not None:

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _cluster_lib as CL
-from . import align, refine
+from . import align, refine, stack_cli
 from ._lib import TvaeHipError
 
 MAX_CANDIDATES = 64               # TVAE_CLASSIFY_MAX_CANDIDATES
@@ -32,15 +32,14 @@ MAX_CANDIDATES = 64               # TVAE_CLASSIFY_MAX_CANDIDATES
 
 def _as_table(candidates, N, device, what):
     cand = torch.as_tensor(candidates)
-    if cand.dim() != 2 or cand.shape[0] != N or cand.dtype.is_floating_point or cand.dtype == torch.bool:
-        raise TvaeHipError(f'{what}: candidates must be an [N][M] = [{N}][M] integer array, got {tuple(cand.shape)} '
-                           f'of {cand.dtype}')
+    message = f'{what}: candidates must be an [N][M] = [{N}][M] integer array, got {tuple(cand.shape)} of {cand.dtype}'
+    if cand.dim() != 2 or cand.shape[0] != N:
+        raise TvaeHipError(message)
+    idx = refine.class_index(cand.to(device), message)
     M = cand.shape[1]
     if not 1 <= M <= MAX_CANDIDATES:
         raise TvaeHipError(f'{what}: {M} candidates per image outside [1, {MAX_CANDIDATES}]')
-    lim = torch.iinfo(torch.int32)
-    # (anything negative is outside [0, K) as -1 is)
-    return cand.to(device).to(torch.int64).clamp(-1, lim.max).to(torch.int32).contiguous(), M
+    return idx, M
 
 
 def classify_poses(images, theta, dx, candidates, refs, t_scale=1.0, angle_steps=8, angle_step=None, shift=2, mask_radius=None,
@@ -52,24 +51,9 @@ def classify_poses(images, theta, dx, candidates, refs, t_scale=1.0, angle_steps
     slot-0 value.  angle_steps, angle_step, shift and the mask as in tvae.refine.refine_poses."""
     what = 'classify_poses'
     N, C, n = align._check_stack(images, theta, dx, what)
-    K = refine._check_refs(images, refs, what)
-    cand, M = _as_table(candidates, N, images.device, what)
     A, S = int(angle_steps), int(shift)
-    if n > refine.MAX_SIDE:
-        raise TvaeHipError(f'{what}: n = {n} is above {refine.MAX_SIDE} (one image plane and one extended template must fit the '
-                           'LDS): Fourier-downsample the stack with tvae.image first; poses are in coordinate units and carry '
-                           'over unchanged')
-    if not (C <= refine.MAX_CHANNELS and 0 <= A <= refine.MAX_ANGLE_STEPS and 0 <= S <= refine.MAX_SHIFT):
-        raise TvaeHipError(f'{what}: C={C}, angle_steps={A}, shift={S} outside the supported range (C <= {refine.MAX_CHANNELS}, '
-                           f'0 <= angle_steps <= {refine.MAX_ANGLE_STEPS}, 0 <= shift <= {refine.MAX_SHIFT})')
-    step = math.pi / 8 / max(A, 1) if angle_step is None else float(angle_step)
-    t = float(t_scale)
-    radius = 0.0 if mask_radius is None else float(mask_radius)
-    edge = float(mask_edge)
-    if not (np.isfinite(t) and t > 0 and np.isfinite(step)):
-        raise TvaeHipError(f'{what}: t_scale = {t_scale} must be finite and positive and angle_step = {angle_step} finite')
-    if not (np.isfinite(radius) and np.isfinite(edge) and edge >= 0):
-        raise TvaeHipError(f'{what}: mask_radius = {mask_radius} and mask_edge = {mask_edge} must be finite, the edge not negative')
+    K, step, t, radius, edge = refine.check_search(what, images, refs, A, S, angle_step, t_scale, mask_radius, mask_edge)
+    cand, M = _as_table(candidates, N, images.device, what)
     dev = images.device
     NA, NS = 2 * A + 1, 2 * S + 1
     th_in = theta.reshape(N)
@@ -191,12 +175,8 @@ def classify_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rou
     for j in range(int(rounds)):
         step = float(angle_range) / max(A, 1) / 2 ** j
         cand = candidate_lists(lab64, K, latents, candidates)
-        if cross_halves:
-            refs = align.class_halves(images, th, d, lab64, K, t_scale)[1].reshape(2 * K, C, n, n)
-            slots = cross_half_candidates(lab64, cand, K)
-        else:
-            refs = align.class_averages(images, th, d, lab64, K, t_scale)[0]
-            slots = cand
+        refs = refine.round_references(images, th, d, lab64, K, t_scale, cross_halves)
+        slots = cross_half_candidates(lab64, cand, K) if cross_halves else cand
         new, th, d, sc, best = classify_poses(images, th, d, slots, refs, t_scale, A, step, shift, mask_radius, mask_edge)
         if cross_halves:
             new = torch.where(new >= 0, new % K, new)
@@ -228,56 +208,41 @@ def class_scores(candidates, slot_scores, n_clusters):
 
 # ---- reclassify_particles.py: new labels, poses and averages from the files a clustering run wrote ----------------------------
 def build_parser() -> argparse.ArgumentParser:
-    base = refine.build_parser()
     p = argparse.ArgumentParser('Reassign the images of a clustered stack to their best-matching aligned 2-D class average')
-    for a in base._actions:                                  # the flags of refine_poses.py, as it declares them
-        if a.dest != 'help':
-            p._add_action(a)
-    p.add_argument('--latents', default=None, help='latents.npy of the run: the candidates of an image are the classes '
-                                                    'whose centroid is nearest to it')
-    p.add_argument('--candidates', default=None, type=int, help='candidate classes per image, the current one among them '
-                                                                '(at most 64); default: all classes')
+    stack_cli.add_stack_flags(p)
+    stack_cli.add_grid_flags(p)
+    stack_cli.add_candidate_flags(p)
     return p
+
+
+def save_outputs(out_dir, labels, theta, dx, hist, avg, counts, particles, rot_shape):
+    """clusters_reclassified.npy, rotations_reclassified.npy (in `rot_shape`, the shape of the rotations that came in),
+    translations_reclassified.npy, classify_scores.npy, classify_moved.npy, class_scores.npy ([N][K], class_scores) and
+    class_averages_reclassified.npy (.mrcs, .jpg): reclassify_particles.py and TVAE_RECLASSIFY=1 write these."""
+    save = lambda name, a: np.save(os.path.join(out_dir, name), a)
+    save('clusters_reclassified.npy', stack_cli.host(labels))
+    save('classify_scores.npy', hist['scores'])
+    save('classify_moved.npy', hist['moved'])
+    save('class_scores.npy', class_scores(hist['candidates'], hist['slot_scores'], avg.shape[0]))
+    stack_cli.save_poses(out_dir, 'reclassified', theta, dx, avg, counts, particles, rot_shape)
 
 
 def run(argv=None):
     args = build_parser().parse_args(argv)
-    if not torch.cuda.is_available() or args.device == -1:
-        raise SystemExit('the MI355X build has no CPU compute path')
-    torch.cuda.set_device(args.device)
-    device = torch.device('cuda', args.device)
-    stack = align.load_stack(args.stack, args.crop)
-    particles = args.stack.endswith('mrc') or args.stack.endswith('mrcs')
-    images = torch.from_numpy(stack).to(device)
-    theta = torch.from_numpy(np.asarray(np.load(args.rotations), dtype=np.float32).reshape(-1)).to(device)
-    dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
-    clusters = np.asarray(np.load(args.clusters)).reshape(-1)
-    latents = None if args.latents is None else np.asarray(np.load(args.latents), dtype=np.float64)
-    t = align.translation_scale(args.t_inf)
-    try:
+    inp = stack_cli.open_inputs(args, stack_cli.make_device(args))
+    images, theta, dx, clusters, t = inp.images, inp.theta, inp.dx, inp.clusters, inp.t_scale
+    with stack_cli.hip_errors():
         K = align._check_labels(images, theta, dx, clusters, args.n_clusters, 'classify_rounds')[3]
         before = refine._resolutions(images, theta, dx, clusters, K, t)
         lab, th, d, hist = classify_rounds(images, theta, dx, clusters, K, t, args.rounds, math.radians(args.angle_range),
                                            args.angle_steps, args.shift, args.mask_radius, args.mask_edge, args.cross_halves,
-                                           latents, args.candidates)
+                                           inp.latents, args.candidates)
         new = lab.cpu().numpy()
         avg, counts = align.class_averages(images, th, d, new, K, t)
         after = refine._resolutions(images, th, d, new, K, t)
-    except TvaeHipError as e:
-        raise SystemExit(str(e)) from e
     os.makedirs(args.out_dir, exist_ok=True)
-    save = lambda name, a: np.save(os.path.join(args.out_dir, name), a)
-    save('clusters_reclassified.npy', new)
-    save('rotations_reclassified.npy', th.cpu().numpy().reshape(np.load(args.rotations).shape))
-    save('translations_reclassified.npy', d.cpu().numpy())
-    save('classify_scores.npy', hist['scores'])
-    save('classify_moved.npy', hist['moved'])
-    save('class_scores.npy', class_scores(hist['candidates'], hist['slot_scores'], K))
-    align.save_outputs(args.out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles, 'class_averages_reclassified')
-    print('# class  members before -> after  resolution[px]@0.143 before -> after  resolution[px]@0.5 before -> after')
-    for k in range(K):
-        print('{} {} -> {} {:.4f} -> {:.4f} {:.4f} -> {:.4f}'.format(k, int(hist['counts'][0, k]), int(hist['counts'][-1, k]),
-                                                                    before[k, 0], after[k, 0], before[k, 1], after[k, 1]))
+    save_outputs(args.out_dir, new, th, d, hist, avg, counts, inp.particles, inp.rot_shape)
+    stack_cli.print_resolution_table(before, after, hist['counts'][0], hist['counts'][-1])
     print('# reassigned {} images among {} classes, {} rounds, moved {}, mean score {:.6f} -> {:.6f}: {}'.format(
         images.shape[0], K, args.rounds, hist['moved'].tolist(), hist['scores'][0, 0], hist['scores'][-1, 1], args.out_dir),
         file=sys.stderr)

@@ -205,130 +205,90 @@ def _figures(kind, args, out_dir, z_values, rot_pred, tr_pred, clusters, y_label
         figures.save_histograms(out_dir, rot_pred.cpu().numpy(), tr_pred.cpu().numpy())
 
 
-def _class_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters):
-    """TVAE_CLASS_AVERAGES=1: the aligned class averages of the run (tvae.align), from the preprocessed images the encoder
-    saw and the run's own rotations, translations and clusters."""
+def _step_inputs(switch, args, images, device, rot_pred, tr_pred, clusters):
+    """What every step after the clustering works from: -> (y, theta, dx, clusters, K, t), the preprocessed images the encoder
+    saw on the device and the run's own rotations, translations, clusters, --n-clusters and translation scale."""
+    from . import align
+    if images.shape[-1] != images.shape[-2]:
+        raise SystemExit('{}=1 needs square images, these are {} x {}'.format(switch, *images.shape[-2:]))
+    return (images.to(device).float().contiguous(), rot_pred.float().contiguous(), tr_pred.float().contiguous(),
+            np.asarray(clusters), args.n_clusters, align.translation_scale(args.t_inf))
+
+
+def _class_averages(kind, args, out_dir, *run_):
+    """TVAE_CLASS_AVERAGES=1: the aligned class averages of the run (tvae.align)."""
     from . import align
     print('# saving aligned class averages ... ', file=sys.stderr)
-    if images.shape[-1] != images.shape[-2]:
-        raise SystemExit('TVAE_CLASS_AVERAGES=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
-    y = images.to(device).float().contiguous()
-    avg, counts = align.class_averages(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(),
-                                       np.asarray(clusters), args.n_clusters, align.translation_scale(args.t_inf))
+    y, th, d, lab, K, t = _step_inputs('TVAE_CLASS_AVERAGES', args, *run_)
+    avg, counts = align.class_averages(y, th, d, lab, K, t)
     align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles=kind == 'particles')
 
 
-def _class_frc(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters):
+def _class_frc(kind, args, out_dir, *run_):
     """TVAE_CLASS_FRC=1: half-set averages, variance maps, ring correlation and resolution of the run's classes
-    (tvae.resolution), from the same images, poses and clusters as the class averages."""
-    from . import align, resolution
+    (tvae.resolution)."""
+    from . import resolution
     print('# saving class half sets, variance maps and FRC ({}) ... '.format(resolution.NOTE), file=sys.stderr)
-    if images.shape[-1] != images.shape[-2]:
-        raise SystemExit('TVAE_CLASS_FRC=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
-    y = images.to(device).float().contiguous()
-    res = resolution.class_resolution(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(),
-                                      np.asarray(clusters), args.n_clusters, align.translation_scale(args.t_inf))
-    resolution.save_outputs(out_dir, res)
+    y, th, d, lab, K, t = _step_inputs('TVAE_CLASS_FRC', args, *run_)
+    resolution.save_outputs(out_dir, resolution.class_resolution(y, th, d, lab, K, t))
 
 
-def _class_eigen(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters):
+def _class_eigen(kind, args, out_dir, *run_):
     """TVAE_CLASS_EIGEN=1: eigenimages, coordinates and residual norms of the run's classes (tvae.eigen with the defaults of
-    class_eigenimages.py), from the same images, poses and clusters as the class averages."""
-    from . import align, eigen
+    class_eigenimages.py)."""
+    from . import eigen
     print('# saving class eigenimages, coordinates and residual norms ... ', file=sys.stderr)
-    if images.shape[-1] != images.shape[-2]:
-        raise SystemExit('TVAE_CLASS_EIGEN=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
-    y = images.to(device).float().contiguous()
-    res = eigen.class_eigenimages(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(), np.asarray(clusters),
-                                  args.n_clusters, t_scale=align.translation_scale(args.t_inf))
-    eigen.save_outputs(out_dir, res, particles=kind == 'particles')
+    y, th, d, lab, K, t = _step_inputs('TVAE_CLASS_EIGEN', args, *run_)
+    eigen.save_outputs(out_dir, eigen.class_eigenimages(y, th, d, lab, K, t_scale=t), particles=kind == 'particles')
 
 
-def _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters):
+def _refine_poses(kind, args, out_dir, *run_):
     """TVAE_REFINE_POSES=1: the run's poses refined against its class averages (tvae.refine, three rounds with the defaults
-    of refine_poses.py) and the averages of the refined poses, from the same images, poses and clusters as the class averages."""
+    of refine_poses.py) and the averages of the refined poses.  -> the refined (theta, dx)."""
     from . import align, refine
     print('# refining the poses against the class averages ... ', file=sys.stderr)
-    if images.shape[-1] != images.shape[-2]:
-        raise SystemExit('TVAE_REFINE_POSES=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
-    y = images.to(device).float().contiguous()
-    t = align.translation_scale(args.t_inf)
-    th, d, hist = refine.refine_rounds(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(), np.asarray(clusters),
-                                       args.n_clusters, t)
-    avg, counts = align.class_averages(y, th, d, np.asarray(clusters), args.n_clusters, t)
-    np.save(os.path.join(out_dir, 'rotations_refined.npy'), th.cpu().numpy().reshape(tuple(rot_pred.shape)))
-    np.save(os.path.join(out_dir, 'translations_refined.npy'), d.cpu().numpy())
-    np.save(os.path.join(out_dir, 'refine_scores.npy'), hist['scores'])
-    align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), kind == 'particles', 'class_averages_refined')
+    y, th0, d0, lab, K, t = _step_inputs('TVAE_REFINE_POSES', args, *run_)
+    th, d, hist = refine.refine_rounds(y, th0, d0, lab, K, t)
+    avg, counts = align.class_averages(y, th, d, lab, K, t)
+    refine.save_outputs(out_dir, th, d, hist, avg, counts, kind == 'particles', th0.shape)
     return th, d
 
 
-def _polish_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, start=None):
+def _polish_poses(kind, args, out_dir, *run_, start=None):
     """TVAE_POLISH_POSES=1: the poses polished to sub-pixel accuracy against the class averages (tvae.polish, one round with the
     defaults of polish_poses.py) and the averages of the polished poses.  `start`: the refined poses (theta, dx) where
     TVAE_REFINE_POSES=1 ran before, else the run's own."""
     from . import align, polish
     print('# polishing the poses against the class averages ... ', file=sys.stderr)
-    if images.shape[-1] != images.shape[-2]:
-        raise SystemExit('TVAE_POLISH_POSES=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
-    y = images.to(device).float().contiguous()
-    t = align.translation_scale(args.t_inf)
-    th0, d0 = start if start is not None else (rot_pred.float().contiguous(), tr_pred.float().contiguous())
-    th, d, hist = polish.polish_rounds(y, th0, d0, np.asarray(clusters), args.n_clusters, t)
-    avg, counts = align.class_averages(y, th, d, np.asarray(clusters), args.n_clusters, t)
-    np.save(os.path.join(out_dir, 'rotations_polished.npy'), th.cpu().numpy().reshape(tuple(rot_pred.shape)))
-    np.save(os.path.join(out_dir, 'translations_polished.npy'), d.cpu().numpy())
-    np.save(os.path.join(out_dir, 'polish_scores.npy'), hist['image_scores'])
-    np.save(os.path.join(out_dir, 'polish_steps.npy'), hist['image_steps'])
-    align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), kind == 'particles', 'class_averages_polished')
+    y, th0, d0, lab, K, t = _step_inputs('TVAE_POLISH_POSES', args, *run_)
+    rot_shape = th0.shape                                     # (of the run's rotations, whatever the start is)
+    if start is not None:
+        th0, d0 = start
+    th, d, hist = polish.polish_rounds(y, th0, d0, lab, K, t)
+    avg, counts = align.class_averages(y, th, d, lab, K, t)
+    polish.save_outputs(out_dir, th, d, hist, avg, counts, kind == 'particles', rot_shape)
 
 
-def _reclassify(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values):
+def _reclassify(kind, args, out_dir, *run_, z_values):
     """TVAE_RECLASSIFY=1: the run's images reassigned to their best-matching class average (tvae.classify, three rounds with
     the defaults of reclassify_particles.py, the candidates from the run's latents with m = min(K, 8)) and the averages of the
     new labels and poses."""
     from . import align, classify
     print('# reassigning the images to their best-matching class averages ... ', file=sys.stderr)
-    if images.shape[-1] != images.shape[-2]:
-        raise SystemExit('TVAE_RECLASSIFY=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
-    y = images.to(device).float().contiguous()
-    t = align.translation_scale(args.t_inf)
-    K = args.n_clusters
-    lab, th, d, hist = classify.classify_rounds(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(),
-                                                np.asarray(clusters), K, t, latents=z_values, candidates=min(K, 8))
-    new = lab.cpu().numpy()
-    avg, counts = align.class_averages(y, th, d, new, K, t)
-    np.save(os.path.join(out_dir, 'clusters_reclassified.npy'), new)
-    np.save(os.path.join(out_dir, 'rotations_reclassified.npy'), th.cpu().numpy().reshape(tuple(rot_pred.shape)))
-    np.save(os.path.join(out_dir, 'translations_reclassified.npy'), d.cpu().numpy())
-    np.save(os.path.join(out_dir, 'classify_scores.npy'), hist['scores'])
-    np.save(os.path.join(out_dir, 'classify_moved.npy'), hist['moved'])
-    np.save(os.path.join(out_dir, 'class_scores.npy'), classify.class_scores(hist['candidates'], hist['slot_scores'], K))
-    align.save_outputs(out_dir, avg.cpu().numpy(), counts.cpu().numpy(), kind == 'particles', 'class_averages_reclassified')
+    y, th0, d0, lab, K, t = _step_inputs('TVAE_RECLASSIFY', args, *run_)
+    new, th, d, hist = classify.classify_rounds(y, th0, d0, lab, K, t, latents=z_values, candidates=min(K, 8))
+    avg, counts = align.class_averages(y, th, d, new.cpu().numpy(), K, t)
+    classify.save_outputs(out_dir, new, th, d, hist, avg, counts, kind == 'particles', th0.shape)
 
 
-def _ml_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values):
+def _ml_averages(kind, args, out_dir, *run_, z_values):
     """TVAE_ML_AVERAGES=1: the maximum-likelihood class averages of the run (tvae.ml2d, three rounds with the defaults of
     ml_class_averages.py, the candidates from the run's latents with m = min(K, 8)), the labels and top-1 poses they imply."""
-    from . import align, ml2d
+    from . import ml2d
     print('# maximum-likelihood class averages: soft assignment over classes and poses ... ', file=sys.stderr)
-    if images.shape[-1] != images.shape[-2]:
-        raise SystemExit('TVAE_ML_AVERAGES=1 needs square images, these are {} x {}'.format(*images.shape[-2:]))
-    y = images.to(device).float().contiguous()
-    t = align.translation_scale(args.t_inf)
-    K = args.n_clusters
-    avg, wsum, lab, th, d, hist = ml2d.ml_rounds(y, rot_pred.float().contiguous(), tr_pred.float().contiguous(),
-                                                 np.asarray(clusters), K, t, latents=z_values, candidates=min(K, 8))
-    new = lab.cpu().numpy()
-    np.save(os.path.join(out_dir, 'class_weights.npy'), wsum.cpu().numpy())
-    np.save(os.path.join(out_dir, 'clusters_ml.npy'), new)
-    np.save(os.path.join(out_dir, 'rotations_ml.npy'), th.cpu().numpy().reshape(tuple(rot_pred.shape)))
-    np.save(os.path.join(out_dir, 'translations_ml.npy'), d.cpu().numpy())
-    np.save(os.path.join(out_dir, 'ml_log_likelihood.npy'), hist['log_likelihood'])
-    np.save(os.path.join(out_dir, 'ml_sigma2.npy'), hist['sigma2'])
-    np.save(os.path.join(out_dir, 'ml_entropy.npy'), hist['entropy'].cpu().numpy())
-    counts = np.bincount(new[(new >= 0) & (new < K)], minlength=K)
-    align.save_outputs(out_dir, avg.cpu().numpy(), counts, kind == 'particles', 'class_averages_ml')
+    y, th0, d0, lab, K, t = _step_inputs('TVAE_ML_AVERAGES', args, *run_)
+    avg, wsum, new, th, d, hist = ml2d.ml_rounds(y, th0, d0, lab, K, t, latents=z_values, candidates=min(K, 8))
+    ml2d.save_outputs(out_dir, avg, wsum, new, th, d, hist, kind == 'particles', th0.shape)
 
 
 def run(kind: str, argv=None):
@@ -391,21 +351,22 @@ def run(kind: str, argv=None):
         _figures(kind, args, out_dir, z_values, rot_pred, tr_pred, clusters, y_labels, mapping)
     else:
         print('# the t-SNE, confusion-matrix and histogram figures of the reference are not built', file=sys.stderr)
+    run_ = (images, device, rot_pred, tr_pred, clusters)      # what _step_inputs takes
     if os.environ.get('TVAE_CLASS_AVERAGES', '') == '1':
-        _class_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+        _class_averages(kind, args, out_dir, *run_)
     if os.environ.get('TVAE_CLASS_FRC', '') == '1':
-        _class_frc(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+        _class_frc(kind, args, out_dir, *run_)
     if os.environ.get('TVAE_CLASS_EIGEN', '') == '1':
-        _class_eigen(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+        _class_eigen(kind, args, out_dir, *run_)
     refined = None
     if os.environ.get('TVAE_REFINE_POSES', '') == '1':
-        refined = _refine_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters)
+        refined = _refine_poses(kind, args, out_dir, *run_)
     if os.environ.get('TVAE_POLISH_POSES', '') == '1':
-        _polish_poses(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, refined)
+        _polish_poses(kind, args, out_dir, *run_, start=refined)
     if os.environ.get('TVAE_RECLASSIFY', '') == '1':
-        _reclassify(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values)
+        _reclassify(kind, args, out_dir, *run_, z_values=z_values)
     if os.environ.get('TVAE_ML_AVERAGES', '') == '1':
-        _ml_averages(kind, args, out_dir, images, device, rot_pred, tr_pred, clusters, z_values)
+        _ml_averages(kind, args, out_dir, *run_, z_values=z_values)
 
     np.save(os.path.join(out_dir, 'latents.npy'), z_values.cpu().numpy())
     np.save(os.path.join(out_dir, 'rotations.npy'), rot_pred.cpu().numpy())

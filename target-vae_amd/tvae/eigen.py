@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _cluster_lib as CL
-from . import align, resolution
+from . import align, resolution, stack_cli
 from ._lib import TvaeHipError
 
 MAX_COMPONENTS = 16                # TVAE_EIGEN_MAX_COMPONENTS
@@ -243,23 +243,16 @@ def build_parser(ctf=False) -> argparse.ArgumentParser:
     """The flags of class_resolution.py that mean something here (not --apix and --threshold) and those of the iteration;
     ctf=True adds --ctf, --ctf-correct flip and --scale (what class_eigenimages.py parses)."""
     p = argparse.ArgumentParser('Eigenimages of the aligned 2-D classes, particle coordinates and residual norms')
-    p.add_argument('--stack', required=True, help='the images (.npy, .mrc or .mrcs): [N][n][n] or [N][C][n][n]')
-    p.add_argument('--rotations', required=True, help='rotations.npy of the clustering run')
-    p.add_argument('--translations', required=True, help='translations.npy of the clustering run')
-    p.add_argument('--clusters', required=True, help='clusters.npy of the clustering run')
-    p.add_argument('--t-inf', default='attention', choices=['unimodal', 'attention'],
-                   help='translation inference of the run: chooses the scale of the translations (1 or 0.1)')
-    p.add_argument('--crop', default=0, type=int, help='central crop, as the clustering run applied it')
-    p.add_argument('--n-clusters', default=None, type=int, help='default: the largest label + 1')
-    p.add_argument('--out-dir', default='.', help='where the .npy files, class_eigen.txt and the figure go')
-    p.add_argument('--mask-radius', default=None, type=float, help='soft mask radius in pixels; default (n - 1) / 2 - 4')
-    p.add_argument('--mask-edge', default=resolution.MASK_EDGE, type=float, help='width of the raised-cosine edge in pixels')
-    p.add_argument('--components', default=4, type=int, help='eigenimages per class')
-    p.add_argument('--oversample', default=4, type=int, 
-                   help='extra vectors of the subspace iteration (components + oversample <= 16)')
-    p.add_argument('--power-iterations', default=2, type=int, help='passes of the subspace iteration after the first')
-    p.add_argument('--seed', default=0, type=int, help='seed of the Gaussian start')
-    p.add_argument('-d', '--device', type=int, default=0)
+
+    def own(q):
+        stack_cli.add_mask_flags(q, resolution.MASK_EDGE, 'default (n - 1) / 2 - 4')
+        q.add_argument('--components', default=4, type=int, help='eigenimages per class')
+        q.add_argument('--oversample', default=4, type=int,
+                       help='extra vectors of the subspace iteration (components + oversample <= 16)')
+        q.add_argument('--power-iterations', default=2, type=int, help='passes of the subspace iteration after the first')
+        q.add_argument('--seed', default=0, type=int, help='seed of the Gaussian start')
+
+    stack_cli.add_stack_flags(p, 'where the .npy files, class_eigen.txt and the figure go', own)
     if ctf:
         align.add_ctf_flags(p, ('flip',), wiener=False)
     return p
@@ -267,16 +260,9 @@ def build_parser(ctf=False) -> argparse.ArgumentParser:
 
 def run(argv=None):
     args = build_parser(ctf=True).parse_args(argv)
-    if not torch.cuda.is_available() or args.device == -1:
-        raise SystemExit('the MI355X build has no CPU compute path')
-    torch.cuda.set_device(args.device)
-    device = torch.device('cuda', args.device)
-    images = torch.from_numpy(align.load_stack(args.stack, args.crop)).to(device)
-    particles = args.stack.endswith('mrc') or args.stack.endswith('mrcs')
-    theta = torch.from_numpy(np.asarray(np.load(args.rotations), dtype=np.float32).reshape(-1)).to(device)
-    dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
-    clusters = np.asarray(np.load(args.clusters)).reshape(-1)
-    try:
+    inp = stack_cli.open_inputs(args, stack_cli.make_device(args))
+    images, theta, dx, clusters = inp.images, inp.theta, inp.dx, inp.clusters
+    with stack_cli.hip_errors():
         if args.ctf:
             # phase-flipped in place, in the chunks of tvae.ctf.filter_stack: the averages and the residuals are those of the
             # corrected stack
@@ -284,12 +270,9 @@ def run(argv=None):
             coef = align.load_ctf_coefficients(args.ctf, images.shape[0], args.scale)
             ctf.filter_stack(images, coef=coef, mode='flip', inplace=True)
         res = class_eigenimages(images, theta, dx, clusters, args.n_clusters, args.components, args.oversample,
-                                args.power_iterations, align.translation_scale(args.t_inf), None, args.mask_radius,
-                                args.mask_edge, args.seed)
-    except TvaeHipError as e:
-        raise SystemExit(str(e)) from e
+                                args.power_iterations, inp.t_scale, None, args.mask_radius, args.mask_edge, args.seed)
     os.makedirs(args.out_dir, exist_ok=True)
-    save_outputs(args.out_dir, res, particles)
+    save_outputs(args.out_dir, res, inp.particles)
     print('# class eigenimages of {} images in {} classes, {} components: {}'.format(
         images.shape[0], res['eigenvalues'].shape[0], res['eigenvalues'].shape[1], args.out_dir), file=sys.stderr)
     return res

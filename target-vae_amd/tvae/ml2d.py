@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _cluster_lib as CL
-from . import align, classify, refine
+from . import align, classify, refine, stack_cli
 from ._lib import TvaeHipError
 
 MAX_KEEP = 64                     # TVAE_POSTERIOR_MAX_KEEP
@@ -53,7 +53,7 @@ def pose_posteriors(num, pp, yy, candidates, theta, dx, n, n_clusters, sigma2, l
             and 0 <= S <= refine.MAX_SHIFT and 1 <= N <= CL.MAX_PLANES):
         raise TvaeHipError(f'{what}: N={N}, n={n}, K={K}, keep={P}, angle_steps={A}, shift={S} outside the supported range '
                            f'(1 <= keep <= {MAX_KEEP})')
-    step = math.pi / 8 / max(A, 1) if angle_step is None else float(angle_step)
+    step = refine.angle_step_of(A, angle_step)
     t, s2 = float(t_scale), float(np.float32(sigma2))
     if not (np.isfinite(t) and t > 0 and np.isfinite(step) and np.isfinite(s2) and s2 > 0):
         raise TvaeHipError(f'{what}: t_scale = {t_scale} and sigma2 = {sigma2} must be finite and positive (in fp32) and '
@@ -241,12 +241,10 @@ def ml_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3,
         latents = torch.as_tensor(latents).to(dev)
     step = float(angle_range) / max(A, 1)
     R = 2 * K if cross_halves else K                         # references: [half 0 | half 1] with cross_halves
+    refs = refine.round_references(images, th0, d0, lab64, K, t_scale, cross_halves)
     if cross_halves:
-        refs = align.class_halves(images, th0, d0, lab64, K, t_scale)[1].reshape(R, C, n, n)
         own = refine.cross_half_labels(lab64, K)
         half = ((own >= 0) & (own < K)).to(torch.int64)      # an image at an odd position of its class is in half 1
-    else:
-        refs = align.class_averages(images, th0, d0, lab64, K, t_scale)[0]
     logprior = None
     s2 = None if sigma2 is None else float(np.float32(sigma2))
     hist = dict(log_likelihood=[], sigma2=[], kept=[], pi=[])
@@ -298,57 +296,48 @@ def ml_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3,
 
 # ---- ml_class_averages.py: soft averages, labels and poses from the files a clustering run wrote -----------------------------
 def build_parser() -> argparse.ArgumentParser:
-    base = classify.build_parser()
     p = argparse.ArgumentParser('Maximum-likelihood 2-D class averages of a clustered stack: soft assignment over classes and poses')
-    for a in base._actions:                                  # the flags of reclassify_particles.py, as it declares them
-        if a.dest != 'help':
-            p._add_action(a)
+    stack_cli.add_stack_flags(p)
+    stack_cli.add_grid_flags(p)
+    stack_cli.add_candidate_flags(p)
     p.add_argument('--keep', default=8, type=int, help='(class, pose) entries an image contributes to the averages (at most 64)')
     p.add_argument('--sigma2', default=None, type=float, help='noise variance per pixel of the first round; default: estimated '
                                                               'from the best residuals')
     return p
 
 
+def save_outputs(out_dir, avg, wsum, labels, theta, dx, hist, particles, rot_shape):
+    """class_weights.npy, clusters_ml.npy, rotations_ml.npy (in `rot_shape`, the shape of the rotations that came in),
+    translations_ml.npy, ml_log_likelihood.npy, ml_sigma2.npy, ml_entropy.npy and class_averages_ml.npy (.mrcs, .jpg; the
+    montage counts the members by the new labels): ml_class_averages.py and TVAE_ML_AVERAGES=1 write these.
+    -> those counts, int [K]."""
+    save = lambda name, a: np.save(os.path.join(out_dir, name), stack_cli.host(a))
+    new, K = stack_cli.host(labels), avg.shape[0]
+    save('class_weights.npy', wsum)
+    save('clusters_ml.npy', new)
+    save('ml_log_likelihood.npy', hist['log_likelihood'])
+    save('ml_sigma2.npy', hist['sigma2'])
+    save('ml_entropy.npy', hist['entropy'])
+    counts = np.bincount(new[(new >= 0) & (new < K)], minlength=K)
+    stack_cli.save_poses(out_dir, 'ml', theta, dx, avg, counts, particles, rot_shape)
+    return counts
+
+
 def run(argv=None):
     args = build_parser().parse_args(argv)
-    if not torch.cuda.is_available() or args.device == -1:
-        raise SystemExit('the MI355X build has no CPU compute path')
-    torch.cuda.set_device(args.device)
-    device = torch.device('cuda', args.device)
-    stack = align.load_stack(args.stack, args.crop)
-    particles = args.stack.endswith('mrc') or args.stack.endswith('mrcs')
-    images = torch.from_numpy(stack).to(device)
-    theta = torch.from_numpy(np.asarray(np.load(args.rotations), dtype=np.float32).reshape(-1)).to(device)
-    dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
-    clusters = np.asarray(np.load(args.clusters)).reshape(-1)
-    latents = None if args.latents is None else np.asarray(np.load(args.latents), dtype=np.float64)
-    t = align.translation_scale(args.t_inf)
-    try:
+    inp = stack_cli.open_inputs(args, stack_cli.make_device(args))
+    images, theta, dx, clusters, t = inp.images, inp.theta, inp.dx, inp.clusters, inp.t_scale
+    with stack_cli.hip_errors():
         K = align._check_labels(images, theta, dx, clusters, args.n_clusters, 'ml_rounds')[3]
         before = refine._resolutions(images, theta, dx, clusters, K, t)
         avg, wsum, lab, th, d, hist = ml_rounds(images, theta, dx, clusters, K, t, args.rounds, math.radians(args.angle_range),
                                                 args.angle_steps, args.shift, args.mask_radius, args.mask_edge, args.keep,
-                                                args.sigma2, latents, args.candidates, args.cross_halves)
-        new = lab.cpu().numpy()
-        after = refine._resolutions(images, th, d, new, K, t)
-    except TvaeHipError as e:
-        raise SystemExit(str(e)) from e
+                                                args.sigma2, inp.latents, args.candidates, args.cross_halves)
+        after = refine._resolutions(images, th, d, lab.cpu().numpy(), K, t)
     os.makedirs(args.out_dir, exist_ok=True)
-    save = lambda name, a: np.save(os.path.join(args.out_dir, name), a)
-    save('class_weights.npy', wsum.cpu().numpy())
-    save('clusters_ml.npy', new)
-    save('rotations_ml.npy', th.cpu().numpy().reshape(np.load(args.rotations).shape))
-    save('translations_ml.npy', d.cpu().numpy())
-    save('ml_log_likelihood.npy', hist['log_likelihood'])
-    save('ml_sigma2.npy', hist['sigma2'])
-    save('ml_entropy.npy', hist['entropy'].cpu().numpy())
-    count = lambda l: np.bincount(l[(l >= 0) & (l < K)].astype(np.int64), minlength=K)
-    align.save_outputs(args.out_dir, avg.cpu().numpy(), count(new), particles, 'class_averages_ml')
-    c0, c1 = count(clusters), count(new)
-    print('# class  members before -> after  resolution[px]@0.143 before -> after  resolution[px]@0.5 before -> after')
-    for k in range(K):
-        print('{} {} -> {} {:.4f} -> {:.4f} {:.4f} -> {:.4f}'.format(k, int(c0[k]), int(c1[k]), before[k, 0], after[k, 0],
-                                                                    before[k, 1], after[k, 1]))
+    counts = save_outputs(args.out_dir, avg, wsum, lab, th, d, hist, inp.particles, inp.rot_shape)
+    was = np.bincount(clusters[(clusters >= 0) & (clusters < K)].astype(np.int64), minlength=K)
+    stack_cli.print_resolution_table(before, after, was, counts)
     print('# maximum-likelihood averages of {} images in {} classes, {} rounds, log-likelihood {:.6e} -> {:.6e}, sigma2 {:.6e} '
           '-> {:.6e}: {}'.format(images.shape[0], K, args.rounds, hist['log_likelihood'][0], hist['log_likelihood'][-1],
                                  hist['sigma2'][0], hist['sigma2'][-1], args.out_dir), file=sys.stderr)

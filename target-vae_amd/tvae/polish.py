@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _cluster_lib as CL
-from . import align, refine
+from . import align, refine, stack_cli
 from ._lib import TvaeHipError
 
 MOMENTS = 15
@@ -39,28 +39,13 @@ def polish_poses(images, theta, dx, labels, refs, t_scale=1.0, iterations=8, max
     trust region of max_shift pixels per axis and max_angle radians around its start."""
     what = 'polish_poses'
     N, C, n, _, lab = align._check_labels(images, theta, dx, labels, 1, what)
-    K = refine._check_refs(images, refs, what)
-    if n > refine.MAX_SIDE:
-        raise TvaeHipError(f'{what}: n = {n} is above {refine.MAX_SIDE}: '
-                           'Fourier-downsample the stack with tvae.image first; poses are in coordinate units and carry '
-                           'over unchanged')
-    if not C <= refine.MAX_CHANNELS:
-        raise TvaeHipError(f'{what}: C={C} outside the supported range (C <= {refine.MAX_CHANNELS})')
-    t, its = float(t_scale), int(iterations)
-    shift, angle = float(max_shift), float(max_angle)
-    radius = 0.0 if mask_radius is None else float(mask_radius)
-    edge = float(mask_edge)
-    if not (np.isfinite(t) and t > 0):
-        raise TvaeHipError(f'{what}: t_scale = {t_scale} must be finite and positive')
+    K, _, t, radius, edge = refine.check_search(what, images, refs, t_scale=t_scale, mask_radius=mask_radius, mask_edge=mask_edge,
+                                                side_note='')
+    its, shift, angle = int(iterations), float(max_shift), float(max_angle)
     if not (its >= 0 and np.isfinite(shift) and shift >= 0 and np.isfinite(angle) and angle >= 0):
         raise TvaeHipError(f'{what}: iterations = {iterations}, max_shift = {max_shift} and max_angle = {max_angle} must be '
                            'finite and not negative')
-    if not (np.isfinite(radius) and np.isfinite(edge) and edge >= 0):
-        raise TvaeHipError(f'{what}: mask_radius = {mask_radius} and mask_edge = {mask_edge} must be finite, the edge not negative')
-    if lab.dtype.is_floating_point or lab.dtype == torch.bool:
-        raise TvaeHipError(f'{what}: labels must be a one-dimensional integer array')
-    lim = torch.iinfo(torch.int32)
-    cls = lab.to(torch.int64).clamp(-1, lim.max).to(torch.int32).contiguous()      # (anything negative is outside [0, K) as -1 is)
+    cls = refine.class_index(lab, f'{what}: labels must be a one-dimensional integer array')
     dev = images.device
     f32 = dict(dtype=torch.float32, device=dev)
     th_in = theta.reshape(N)
@@ -105,10 +90,7 @@ def polish_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, round
     cls = refine.cross_half_labels(lab64, K) if cross_halves else lab64
     scores, steps = [], []
     for _ in range(int(rounds)):
-        if cross_halves:
-            refs = align.class_halves(images, th, d, lab64, K, t_scale)[1].reshape(2 * K, C, n, n)
-        else:
-            refs = align.class_averages(images, th, d, lab64, K, t_scale)[0]
+        refs = refine.round_references(images, th, d, lab64, K, t_scale, cross_halves)
         th, d, sc, st = polish_poses(images, th, d, cls, refs, t_scale, iterations, max_shift, max_angle, mask_radius, mask_edge)
         m = sc[member].double()
         scores.append(m.mean(0).cpu().numpy() if m.numel() else np.zeros(2))
@@ -118,15 +100,9 @@ def polish_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, round
 
 # ---- polish_poses.py: polished poses and averages from the files a clustering or refinement run wrote -------------------------
 def build_parser() -> argparse.ArgumentParser:
-    """A parser of its own: the flags of refine_poses.py that still apply, as that script declares them, and the three of the
-    polish.  tvae.refine.build_parser() is left as it is."""
-    base = refine.build_parser()
     p = argparse.ArgumentParser('Polish the poses of a clustered stack to sub-pixel accuracy against its aligned 2-D class averages')
-    keep = {'stack', 'rotations', 'translations', 'clusters', 't_inf', 'crop', 'n_clusters', 'out_dir', 'device', 'mask_radius',
-            'mask_edge', 'cross_halves'}
-    for a in base._actions:
-        if a.dest in keep:
-            p._add_action(a)
+    stack_cli.add_stack_flags(p)
+    stack_cli.add_mask_flags(p, 0.0, 'default: no mask', cross_halves=True)
     p.add_argument('--rounds', default=1, type=int, help='rounds of averaging and polishing')
     p.add_argument('--iterations', default=8, type=int, help='trial poses per image and round')
     p.add_argument('--max-shift', default=1.0, type=float, help='trust region: pixels per axis around the pose a round starts from')
@@ -134,39 +110,29 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def save_outputs(out_dir, theta, dx, hist, avg, counts, particles, rot_shape):
+    """rotations_polished.npy (in `rot_shape`, the shape of the rotations that came in), translations_polished.npy,
+    polish_scores.npy ([N][2] = (start, final) of the last round), polish_steps.npy ([N], its accepted steps) and
+    class_averages_polished.npy (.mrcs, .jpg): polish_poses.py and TVAE_POLISH_POSES=1 write these."""
+    np.save(os.path.join(out_dir, 'polish_scores.npy'), hist['image_scores'])
+    np.save(os.path.join(out_dir, 'polish_steps.npy'), hist['image_steps'])
+    stack_cli.save_poses(out_dir, 'polished', theta, dx, avg, counts, particles, rot_shape)
+
+
 def run(argv=None):
     args = build_parser().parse_args(argv)
-    if not torch.cuda.is_available() or args.device == -1:
-        raise SystemExit('the MI355X build has no CPU compute path')
-    torch.cuda.set_device(args.device)
-    device = torch.device('cuda', args.device)
-    stack = align.load_stack(args.stack, args.crop)
-    particles = args.stack.endswith('mrc') or args.stack.endswith('mrcs')
-    images = torch.from_numpy(stack).to(device)
-    theta = torch.from_numpy(np.asarray(np.load(args.rotations), dtype=np.float32).reshape(-1)).to(device)
-    dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
-    clusters = np.asarray(np.load(args.clusters)).reshape(-1)
-    t = align.translation_scale(args.t_inf)
-    try:
+    inp = stack_cli.open_inputs(args, stack_cli.make_device(args))
+    images, theta, dx, clusters, t = inp.images, inp.theta, inp.dx, inp.clusters, inp.t_scale
+    with stack_cli.hip_errors():
         K = align._check_labels(images, theta, dx, clusters, args.n_clusters, 'polish_poses')[3]
         before = refine._resolutions(images, theta, dx, clusters, K, t)
         th, d, hist = polish_rounds(images, theta, dx, clusters, K, t, args.rounds, args.iterations, args.max_shift,
                                     math.radians(args.max_angle), args.mask_radius, args.mask_edge, args.cross_halves)
         avg, counts = align.class_averages(images, th, d, clusters, K, t)
         after = refine._resolutions(images, th, d, clusters, K, t)
-    except TvaeHipError as e:
-        raise SystemExit(str(e)) from e
     os.makedirs(args.out_dir, exist_ok=True)
-    np.save(os.path.join(args.out_dir, 'rotations_polished.npy'), th.cpu().numpy().reshape(np.load(args.rotations).shape))
-    np.save(os.path.join(args.out_dir, 'translations_polished.npy'), d.cpu().numpy())
-    np.save(os.path.join(args.out_dir, 'polish_scores.npy'), hist['image_scores'])      # [N][2] = (start, final) of the last round
-    np.save(os.path.join(args.out_dir, 'polish_steps.npy'), hist['image_steps'])        # [N] accepted steps of the last round
-    align.save_outputs(args.out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles, 'class_averages_polished')
-    print('# class  members  resolution[px]@0.143 before -> after  resolution[px]@0.5 before -> after')
-    cnt = counts.cpu().numpy()
-    for k in range(K):
-        print('{} {} {:.4f} -> {:.4f} {:.4f} -> {:.4f}'.format(k, int(cnt[k]), before[k, 0], after[k, 0], before[k, 1],
-                                                               after[k, 1]))
+    save_outputs(args.out_dir, th, d, hist, avg, counts, inp.particles, inp.rot_shape)
+    stack_cli.print_resolution_table(before, after, counts.cpu().numpy())
     print('# polished the poses of {} images in {} classes, {} rounds, mean score {:.6f} -> {:.6f}: {}'.format(
         images.shape[0], K, args.rounds, hist['scores'][0, 0], hist['scores'][-1, 1], args.out_dir), file=sys.stderr)
     return th, d, hist

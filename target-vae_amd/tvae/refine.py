@@ -9,6 +9,9 @@ result of an image depends on that image, its pose and its class's reference alo
 plane and one extended template have to fit the LDS): Fourier-downsample the stack with tvae.image first -- poses are in
 coordinate units and carry over unchanged.
 
+This module is also the home of the argument rules that every pose search against references shares (tvae.classify,
+tvae.polish and, for its part, tvae.ml2d): `check_search`, `class_index` and `round_references`.
+
 `refine_rounds` alternates averaging and refining and halves the angle step after every round.  With cross_halves=True
 every image is scored against the half-set average it is NOT a member of, so that no image is aligned to an average that
 contains it.
@@ -24,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _cluster_lib as CL
-from . import align
+from . import align, stack_cli
 from ._lib import TvaeHipError
 
 MAX_SIDE, MAX_CHANNELS, MAX_ANGLE_STEPS, MAX_SHIFT = 128, 16, 32, 8
@@ -43,6 +46,59 @@ def _check_refs(images, refs, what):
     return K
 
 
+def angle_step_of(angle_steps, angle_step=None):
+    """angle_step None: pi / 8 divided by max(A, 1)."""
+    return math.pi / 8 / max(int(angle_steps), 1) if angle_step is None else float(angle_step)
+
+
+LDS_NOTE = ' (one image plane and one extended template must fit the LDS)'
+
+
+def check_search(what, images, refs, angle_steps=None, shift=None, angle_step=None, t_scale=1.0, mask_radius=None,
+                 mask_edge=0.0, side_note=LDS_NOTE):
+    """THE statement of the argument rules of a pose search against references (refine_poses, classify_poses, polish_poses),
+    after the stack has passed tvae.align's checks: the references, the side, the ranges of C, A and S, t_scale, the angle
+    step and the mask.  A search without a grid (the polish) leaves angle_steps, shift and angle_step away, and its messages
+    do not speak of them.  -> (K, step, t, radius, edge), normalised."""
+    K = _check_refs(images, refs, what)
+    C, n = images.shape[1], images.shape[-1]
+    grid = angle_steps is not None
+    A, S = (int(angle_steps), int(shift)) if grid else (0, 0)
+    if n > MAX_SIDE:
+        raise TvaeHipError(f'{what}: n = {n} is above {MAX_SIDE}{side_note}: Fourier-downsample the stack with tvae.image first; '
+                           'poses are in coordinate units and carry over unchanged')
+    if not (C <= MAX_CHANNELS and 0 <= A <= MAX_ANGLE_STEPS and 0 <= S <= MAX_SHIFT):
+        if not grid:
+            raise TvaeHipError(f'{what}: C={C} outside the supported range (C <= {MAX_CHANNELS})')
+        raise TvaeHipError(f'{what}: C={C}, angle_steps={A}, shift={S} outside the supported range (C <= {MAX_CHANNELS}, '
+                           f'0 <= angle_steps <= {MAX_ANGLE_STEPS}, 0 <= shift <= {MAX_SHIFT})')
+    step, t = angle_step_of(A, angle_step), float(t_scale)
+    radius = 0.0 if mask_radius is None else float(mask_radius)
+    edge = float(mask_edge)
+    if not (np.isfinite(t) and t > 0 and np.isfinite(step)):
+        raise TvaeHipError(f'{what}: t_scale = {t_scale} must be finite and positive' +
+                           (f' and angle_step = {angle_step} finite' if grid else ''))
+    if not (np.isfinite(radius) and np.isfinite(edge) and edge >= 0):
+        raise TvaeHipError(f'{what}: mask_radius = {mask_radius} and mask_edge = {mask_edge} must be finite, the edge not negative')
+    return K, step, t, radius, edge
+
+
+def class_index(values, message):
+    """Integer labels or candidates -> contiguous int32 for the kernels, clamped into int32 (anything negative is outside
+    [0, K) as -1 is, anything above int32 as 2^31 - 1 is); floating and bool tensors raise `message`."""
+    if values.dtype.is_floating_point or values.dtype == torch.bool:
+        raise TvaeHipError(message)
+    return values.to(torch.int64).clamp(-1, torch.iinfo(torch.int32).max).to(torch.int32).contiguous()
+
+
+def round_references(images, theta, dx, lab64, K, t_scale, cross_halves):
+    """The references a round scores against, [K][C][n][n] (tvae.align.class_averages of the current poses) or, with
+    cross_halves, [2K][C][n][n] = [half 0 of class 0 .. K - 1, half 1 of class 0 .. K - 1] (tvae.align.class_halves)."""
+    if cross_halves:
+        return align.class_halves(images, theta, dx, lab64, K, t_scale)[1].reshape(2 * K, *images.shape[1:])
+    return align.class_averages(images, theta, dx, lab64, K, t_scale)[0]
+
+
 def refine_poses(images, theta, dx, labels, refs, t_scale=1.0, angle_steps=8, angle_step=None, shift=2, mask_radius=None,
                  mask_edge=0.0, tables=False):
     """images [N][C][n][n], theta [N] or [N][1], dx [N][2], refs [K][C][n][n] (CUDA fp32), labels [N] integers (any device or
@@ -51,27 +107,9 @@ def refine_poses(images, theta, dx, labels, refs, t_scale=1.0, angle_steps=8, an
     angle_steps = A steps of angle_step radians to each side (None: pi / 8 divided by max(A, 1)); shift = S pixels."""
     what = 'refine_poses'
     N, C, n, _, lab = align._check_labels(images, theta, dx, labels, 1, what)
-    K = _check_refs(images, refs, what)
     A, S = int(angle_steps), int(shift)
-    if n > MAX_SIDE:
-        raise TvaeHipError(f'{what}: n = {n} is above {MAX_SIDE} (one image plane and one extended template must fit the LDS): '
-                           'Fourier-downsample the stack with tvae.image first; poses are in coordinate units and carry '
-                           'over unchanged')
-    if not (C <= MAX_CHANNELS and 0 <= A <= MAX_ANGLE_STEPS and 0 <= S <= MAX_SHIFT):
-        raise TvaeHipError(f'{what}: C={C}, angle_steps={A}, shift={S} outside the supported range (C <= {MAX_CHANNELS}, '
-                           f'0 <= angle_steps <= {MAX_ANGLE_STEPS}, 0 <= shift <= {MAX_SHIFT})')
-    step = math.pi / 8 / max(A, 1) if angle_step is None else float(angle_step)
-    t = float(t_scale)
-    radius = 0.0 if mask_radius is None else float(mask_radius)
-    edge = float(mask_edge)
-    if not (np.isfinite(t) and t > 0 and np.isfinite(step)):
-        raise TvaeHipError(f'{what}: t_scale = {t_scale} must be finite and positive and angle_step = {angle_step} finite')
-    if not (np.isfinite(radius) and np.isfinite(edge) and edge >= 0):
-        raise TvaeHipError(f'{what}: mask_radius = {mask_radius} and mask_edge = {mask_edge} must be finite, the edge not negative')
-    if lab.dtype.is_floating_point or lab.dtype == torch.bool:
-        raise TvaeHipError(f'{what}: labels must be a one-dimensional integer array')
-    lim = torch.iinfo(torch.int32)
-    cls = lab.to(torch.int64).clamp(-1, lim.max).to(torch.int32).contiguous()      # (anything negative is outside [0, K) as -1 is)
+    K, step, t, radius, edge = check_search(what, images, refs, A, S, angle_step, t_scale, mask_radius, mask_edge)
+    cls = class_index(lab, f'{what}: labels must be a one-dimensional integer array')
     dev = images.device
     NA, NS = 2 * A + 1, 2 * S + 1
     th_in = theta.reshape(N)
@@ -145,10 +183,7 @@ def refine_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, round
     steps, scores = [], []
     for j in range(int(rounds)):
         step = float(angle_range) / max(A, 1) / 2 ** j
-        if cross_halves:
-            refs = align.class_halves(images, th, d, lab64, K, t_scale)[1].reshape(2 * K, C, n, n)
-        else:
-            refs = align.class_averages(images, th, d, lab64, K, t_scale)[0]
+        refs = round_references(images, th, d, lab64, K, t_scale, cross_halves)
         th, d, sc, _ = refine_poses(images, th, d, cls, refs, t_scale, A, step, shift, mask_radius, mask_edge)
         steps.append(step)
         m = sc[member].double()
@@ -158,20 +193,9 @@ def refine_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, round
 
 # ---- refine_poses.py: refined poses and averages from the files a clustering run wrote ---------------------------------------
 def build_parser() -> argparse.ArgumentParser:
-    base = align.build_parser()
     p = argparse.ArgumentParser('Refine the poses of a clustered stack against its aligned 2-D class averages')
-    keep = {'stack', 'rotations', 'translations', 'clusters', 't_inf', 'crop', 'n_clusters', 'out_dir', 'device'}
-    for a in base._actions:                                  # the flags of class_averages.py, as it declares them
-        if a.dest in keep:
-            p._add_action(a)
-    p.add_argument('--rounds', default=3, type=int, help='rounds of averaging and refining; the angle step halves every round')
-    p.add_argument('--angle-range', default=22.5, type=float, help='degrees searched to each side in the first round')
-    p.add_argument('--angle-steps', default=8, type=int, help='angle steps to each side (at most 32)')
-    p.add_argument('--shift', default=2, type=int, help='shift radius in whole pixels (at most 8)')
-    p.add_argument('--mask-radius', default=None, type=float, help='soft mask radius in pixels; default: no mask')
-    p.add_argument('--mask-edge', default=0.0, type=float, help='width of the raised-cosine edge in pixels')
-    p.add_argument('--cross-halves', action='store_true',
-                   help='score every image against the half-set average it is not a member of')
+    stack_cli.add_stack_flags(p)
+    stack_cli.add_grid_flags(p)
     return p
 
 
@@ -183,38 +207,27 @@ def _resolutions(images, theta, dx, clusters, K, t):
     return np.stack([resolution.resolution(curve, n, thr) for thr in resolution.THRESHOLDS], 1)
 
 
+def save_outputs(out_dir, theta, dx, hist, avg, counts, particles, rot_shape):
+    """rotations_refined.npy (in `rot_shape`, the shape of the rotations that came in), translations_refined.npy,
+    refine_scores.npy and class_averages_refined.npy (.mrcs, .jpg): refine_poses.py and TVAE_REFINE_POSES=1 write these."""
+    np.save(os.path.join(out_dir, 'refine_scores.npy'), hist['scores'])
+    stack_cli.save_poses(out_dir, 'refined', theta, dx, avg, counts, particles, rot_shape)
+
+
 def run(argv=None):
     args = build_parser().parse_args(argv)
-    if not torch.cuda.is_available() or args.device == -1:
-        raise SystemExit('the MI355X build has no CPU compute path')
-    torch.cuda.set_device(args.device)
-    device = torch.device('cuda', args.device)
-    stack = align.load_stack(args.stack, args.crop)
-    particles = args.stack.endswith('mrc') or args.stack.endswith('mrcs')
-    images = torch.from_numpy(stack).to(device)
-    theta = torch.from_numpy(np.asarray(np.load(args.rotations), dtype=np.float32).reshape(-1)).to(device)
-    dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
-    clusters = np.asarray(np.load(args.clusters)).reshape(-1)
-    t = align.translation_scale(args.t_inf)
-    try:
+    inp = stack_cli.open_inputs(args, stack_cli.make_device(args))
+    images, theta, dx, clusters, t = inp.images, inp.theta, inp.dx, inp.clusters, inp.t_scale
+    with stack_cli.hip_errors():
         K = align._check_labels(images, theta, dx, clusters, args.n_clusters, 'refine_poses')[3]
         before = _resolutions(images, theta, dx, clusters, K, t)
         th, d, hist = refine_rounds(images, theta, dx, clusters, K, t, args.rounds, math.radians(args.angle_range),
                                     args.angle_steps, args.shift, args.mask_radius, args.mask_edge, args.cross_halves)
         avg, counts = align.class_averages(images, th, d, clusters, K, t)
         after = _resolutions(images, th, d, clusters, K, t)
-    except TvaeHipError as e:
-        raise SystemExit(str(e)) from e
     os.makedirs(args.out_dir, exist_ok=True)
-    np.save(os.path.join(args.out_dir, 'rotations_refined.npy'), th.cpu().numpy().reshape(np.load(args.rotations).shape))
-    np.save(os.path.join(args.out_dir, 'translations_refined.npy'), d.cpu().numpy())
-    np.save(os.path.join(args.out_dir, 'refine_scores.npy'), hist['scores'])
-    align.save_outputs(args.out_dir, avg.cpu().numpy(), counts.cpu().numpy(), particles, 'class_averages_refined')
-    print('# class  members  resolution[px]@0.143 before -> after  resolution[px]@0.5 before -> after')
-    cnt = counts.cpu().numpy()
-    for k in range(K):
-        print('{} {} {:.4f} -> {:.4f} {:.4f} -> {:.4f}'.format(k, int(cnt[k]), before[k, 0], after[k, 0], before[k, 1],
-                                                               after[k, 1]))
+    save_outputs(args.out_dir, th, d, hist, avg, counts, inp.particles, inp.rot_shape)
+    stack_cli.print_resolution_table(before, after, counts.cpu().numpy())
     print('# refined the poses of {} images in {} classes, {} rounds, mean score {:.6f} -> {:.6f}: {}'.format(
         images.shape[0], K, args.rounds, hist['scores'][0, 0], hist['scores'][-1, 1], args.out_dir), file=sys.stderr)
     return th, d, hist

@@ -20,8 +20,7 @@ import sys
 import numpy as np
 import torch
 
-from . import align
-from ._lib import TvaeHipError
+from . import align, stack_cli
 
 NOTE = ('both halves share one encoder and one set of poses: this is not a gold-standard FRC and the resolutions read '
         'optimistic')
@@ -118,20 +117,13 @@ def build_parser(ctf=False) -> argparse.ArgumentParser:
     """ctf=True adds --ctf, --ctf-correct flip and --scale (what class_resolution.py parses); the default is the parser without
     them."""
     p = argparse.ArgumentParser('Half-set averages, variance maps and FRC resolution of the aligned 2-D class averages')
-    p.add_argument('--stack', required=True, help='the images (.npy, .mrc or .mrcs): [N][n][n] or [N][C][n][n]')
-    p.add_argument('--rotations', required=True, help='rotations.npy of the clustering run')
-    p.add_argument('--translations', required=True, help='translations.npy of the clustering run')
-    p.add_argument('--clusters', required=True, help='clusters.npy of the clustering run')
-    p.add_argument('--t-inf', default='attention', choices=['unimodal', 'attention'],
-                   help='translation inference of the run: chooses the scale of the translations (1 or 0.1)')
-    p.add_argument('--crop', default=0, type=int, help='central crop, as the clustering run applied it')
-    p.add_argument('--n-clusters', default=None, type=int, help='default: the largest label + 1')
-    p.add_argument('--out-dir', default='.', help='where the .npy files, class_resolution.txt and the figures go')
-    p.add_argument('--apix', default=None, type=float, help='Angstrom per pixel; default: resolutions in pixels')
-    p.add_argument('--threshold', default=0.143, type=float, help='FRC threshold (0.5 is reported beside it)')
-    p.add_argument('--mask-radius', default=None, type=float, help='soft mask radius in pixels; default (n - 1) / 2 - 4')
-    p.add_argument('--mask-edge', default=MASK_EDGE, type=float, help='width of the raised-cosine edge in pixels')
-    p.add_argument('-d', '--device', type=int, default=0)
+
+    def own(q):
+        q.add_argument('--apix', default=None, type=float, help='Angstrom per pixel; default: resolutions in pixels')
+        q.add_argument('--threshold', default=0.143, type=float, help='FRC threshold (0.5 is reported beside it)')
+        stack_cli.add_mask_flags(q, MASK_EDGE, 'default (n - 1) / 2 - 4')
+
+    stack_cli.add_stack_flags(p, 'where the .npy files, class_resolution.txt and the figures go', own)
     if ctf:
         align.add_ctf_flags(p, ('flip',), wiener=False)
     return p
@@ -139,24 +131,15 @@ def build_parser(ctf=False) -> argparse.ArgumentParser:
 
 def run(argv=None):
     args = build_parser(ctf=True).parse_args(argv)
-    if not torch.cuda.is_available() or args.device == -1:
-        raise SystemExit('the MI355X build has no CPU compute path')
-    torch.cuda.set_device(args.device)
-    device = torch.device('cuda', args.device)
-    images = torch.from_numpy(align.load_stack(args.stack, args.crop)).to(device)
-    theta = torch.from_numpy(np.asarray(np.load(args.rotations), dtype=np.float32).reshape(-1)).to(device)
-    dx = torch.from_numpy(np.ascontiguousarray(np.asarray(np.load(args.translations), dtype=np.float32))).to(device)
-    clusters = np.asarray(np.load(args.clusters)).reshape(-1)
-    try:
+    inp = stack_cli.open_inputs(args, stack_cli.make_device(args))
+    images, theta, dx, clusters = inp.images, inp.theta, inp.dx, inp.clusters
+    with stack_cli.hip_errors():
         if args.ctf:
             # phase-flipped in place, in the chunks of tvae.ctf.filter_stack, before the one pass over the stack
             from . import ctf
             coef = align.load_ctf_coefficients(args.ctf, images.shape[0], args.scale)
             ctf.filter_stack(images, coef=coef, mode='flip', inplace=True)
-        res = class_resolution(images, theta, dx, clusters, args.n_clusters, align.translation_scale(args.t_inf),
-                               args.mask_radius, args.mask_edge)
-    except TvaeHipError as e:
-        raise SystemExit(str(e)) from e
+        res = class_resolution(images, theta, dx, clusters, args.n_clusters, inp.t_scale, args.mask_radius, args.mask_edge)
     os.makedirs(args.out_dir, exist_ok=True)
     values = save_outputs(args.out_dir, res, args.threshold, args.apix)
     print('# class resolution of {} images in {} classes ({}): {}'.format(images.shape[0], values.shape[0], NOTE,
