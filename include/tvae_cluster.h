@@ -535,6 +535,72 @@ int tvae_fourier_filter(const float* X, long x_stride, const double* coef, const
 int tvae_ctf_power(const double* coef, const int* order, const int* seg, double* D, int* counts, int N, int K, int n,
                    tvae_stream_t stream);
 
+/* ---- Radial spectra: the windowed ring power of a stack, its per-group sums, and a radial filter per group ---------------------
+ *
+ * Ring-indexed quantities of a stack's spectrum: the power is read per ring (a noise model for whitening), the filter is
+ * written per ring (whitening, a low-pass at the FRC crossing, the FRC weight).  Planes, frequencies, ks(ky), the Hermitian
+ * weights w_kx and the transform are those of the CTF section; the kernels run the SAME stage code as tvae_fourier_filter.
+ *
+ * Rings.  The ring of (ky, kx) is the integer rule of tvae_class_frc, (2r - 1)^2 <= 4 (ks^2 + kx^2) < (2r + 1)^2 for r >= 1
+ * and r = 0 for 4 (ks^2 + kx^2) < 1, extended over the WHOLE plane, corners included: Rr = tvae_radial_rings(n) =
+ * 1 + ring(h, h) with h = n / 2 (integer division) rings; 92 for n = 128 and 129, 46 for 64 and 65, 2 for n = 2 and 3.
+ * Rings 0 .. n / 2 are the rings of tvae_class_frc.
+ *
+ * tvae_ring_power.  With m the soft mask of tvae_class_frc (centre ((n - 1) / 2, (n - 1) / 2), the same mask_radius /
+ * mask_edge rules and rejections) the window is w = 1 - m for background = 1 (the noise outside the particle) and w = m for
+ * background = 0; mask_radius <= 0 means w = 1 everywhere for both.  demean = 1: mu = sum w x / sum w in fp64 in a fixed
+ * order (per-thread sums over the pixels tid, tid + 256, ... ascending, then the fixed tree of tvae_image_normalize);
+ * (x - mu) is rounded to fp32 once and multiplied by w in fp32; an all-zero window gives the IEEE result, NaN.  demean = 0:
+ * x w in fp32.  Transform: rows to the half spectrum, then columns (stages 1 and 2 of the filter).
+ *     power[b][r] = sum over ring r of the FULL plane of |F(ky, kx)|^2 = sum over the half spectrum of w_kx |F|^2,
+ * each |F|^2 formed in fp64 from the fp32 coefficient, added in fp64 in ascending ky index, then ascending kx (the order of
+ * tvae_class_frc).  The raw sum: dividing by the coefficients of a ring and by sum w^2 is the caller's (neither depends on the
+ * image; tvae.spectrum.ring_power does it).  No atomics: bitwise reproducible, power[b] depends on plane b only, not on B; a
+ * NaN stays in its plane's row.  One workgroup owns a plane; n <= 128: the spectrum is never in memory; n > 128: it goes
+ * through the plane's own part of the workspace.  Not bit for bit the sums[p][r][1] of tvae_class_frc (another kernel,
+ * another order inside a coefficient).
+ *
+ * tvae_ring_power_groups follows the order / seg rules of tvae_ctf_power word for word: entries of `order` outside [0, N) are
+ * skipped and not counted, seg is replaced on the device by min(max(0, seg[0], ..., seg[k]), N).  sums[k][r] = the fp64 sum
+ * of power[i][r] over the valid members i of group k in ascending position, counts[k] their number.  A thread owns one
+ * (k, r); no atomics; group k is independent of K and of the other groups; a non-finite row stays in its own group.
+ *
+ * tvae_radial_filter is tvae_fourier_filter with a third source of H: g = group ? group[b] : 0 and p = prof + g Rr,
+ *     interp = 0 (nearest):  H(ky, kx) = p[ring(ky, kx)] by the integer rule;
+ *     interp = 1 (linear):   s = sqrt((double)(ks^2 + kx^2)), r0 = min((int)floor(s), Rr - 2), t = s - r0,
+ *                            H = (float)(p[r0] + (p[r0 + 1] - p[r0]) t), one fused multiply-add in fp64, rounded once
+ *                            (Rr = 2: r0 = 0).
+ * H is formed in registers; neither it nor the spectrum is in memory for n <= 128.  Everything else is the filter's: four
+ * stages, H w applied in one rounding, 1 / n^2 at the store.  With interp = 0 the result is bit for bit that of
+ * tvae_fourier_filter given Hp planes expanded from the same profile.  A g outside [0, G) makes that plane's output exact
+ * zeros.  out may be X itself (same base, x_stride = n n); any other overlap of out and X is rejected.
+ *
+ * Supported: 2 <= n <= 1024, 1 <= B, N <= 2^24, 1 <= K, G <= 65535, 1 <= Rr <= tvae_radial_rings(1024) = 725
+ * (tvae_ring_power_groups), x_stride 0 or >= n n, background, demean and interp 0 or 1, a finite mask with mask_edge >= 0,
+ * power, sums and ws 8-byte aligned, ws_floats at least the query's.  Anything else returns hipErrorInvalidValue (1) and
+ * writes nothing, and the queries return 0. */
+
+/* rings of the whole plane, 1 + ring(n / 2, n / 2).  0 for unsupported n. */
+int tvae_radial_rings(int n);
+/* floats of workspace of tvae_ring_power: those of tvae_fourier_filter (n > 128: 4 n (R | 1) B; n <= 128: 2).  0 for
+ * unsupported arguments. */
+long tvae_ring_power_ws_floats(int B, int n);
+
+/* X plane b at X + b * x_stride (0: one plane for all) -> power[B][Rr] fp64 */
+int tvae_ring_power(const float* X, long x_stride, double* power, float* ws, long ws_floats, int B, int n, float mask_radius,
+                    float mask_edge, int background, int demean, tvae_stream_t stream);
+
+/* power[N][Rr] fp64 -> sums[K][Rr] fp64, counts[K] (int32) */
+int tvae_ring_power_groups(const double* power, const int* order, const int* seg, double* sums, int* counts, int N, int K,
+                           int Rr, tvae_stream_t stream);
+
+/* floats of workspace of tvae_radial_filter: those of tvae_fourier_filter.  0 for unsupported arguments. */
+long tvae_radial_filter_ws_floats(int B, int n);
+
+/* prof[G][Rr] fp32, group[B] (int32) or NULL (group 0 for every plane); out[B][n][n] */
+int tvae_radial_filter(const float* X, long x_stride, const float* prof, const int* group, float* out, float* ws,
+                       long ws_floats, int B, int n, int G, int interp, tvae_stream_t stream);
+
 /* ---- Eigenimages of the aligned classes: the class covariance applied to a block of vectors, no aligned copy --------------
  *
  * Shared definitions.  Y[N][C][n][n], theta[N], dx[N][2], t_scale, order[N] and seg[K + 1] exactly as for tvae_class_average

@@ -127,14 +127,7 @@ __global__ __launch_bounds__(ALIGN_TILE) void halves_reduce_kernel(const float* 
     var[at] = v;
 }
 
-// m(i, j): 1 within `radius` of the centre ((n - 1) / 2, (n - 1) / 2), a raised cosine over `edge`, 0 beyond; radius <= 0: no
-// mask.  fp64: what the mask adds to the error of a coefficient is far below the sums' own rounding.
-__device__ __forceinline__ float frc_mask(int i, int j, int n, float radius, float edge) {
-    if (!(radius > 0.f)) return 1.f;
-    const double c = 0.5 * (double)(n - 1);
-    const double di = (double)i - c, dj = (double)j - c;
-    return soft_mask(sqrt(di * di + dj * dj), radius, edge);  // (cluster_common.hpp: shared with the pose refinement)
-}
+// (frc_mask, the mask m(i, j), and frc_first_kx, the kx interval of a ring: cluster_common.hpp, shared with the ring power)
 
 // grid = (ceil(n / FRC_ROWS), P, 2): z = 0 reads a, z = 1 reads b.  G[P][2][n][H] complex, H = n / 2 + 1:
 // G(i, kx) = sum_j x[i][j] m(i, j) exp(-2 pi i kx j / n)
@@ -215,15 +208,6 @@ __global__ __launch_bounds__(FRC_TILE) void frc_cols_kernel(const float2* __rest
         dst[nH + at] = (float)(ar * ar + ai * ai);
         dst[2 * nH + at] = (float)(br * br + bi * bi);
     }
-}
-
-// the least kx >= 0 with 4 kx^2 >= t (t below 2^23: exact in fp32, and the two loops make the estimate exact)
-__device__ __forceinline__ int frc_first_kx(int t) {
-    if (t <= 0) return 0;
-    int kx = (int)ceilf(0.5f * sqrtf((float)t));
-    while (kx > 0 && 4 * (kx - 1) * (kx - 1) >= t) --kx;
-    while (4 * kx * kx < t) ++kx;
-    return kx;
 }
 
 // grid = (ceil(R / FRC_RING_TILE), P), R = n / 2 + 1.  sums[P][R][3] (fp64), frc[P][R].  Ring r holds the (ky, kx) with

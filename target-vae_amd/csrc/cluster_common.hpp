@@ -145,6 +145,33 @@ __device__ __forceinline__ float soft_mask(double d, float radius, float edge) {
     return (float)(0.5 * (1.0 + cospi((d - r) / e)));
 }
 
+// m(i, j): 1 within `radius` of the centre ((n - 1) / 2, (n - 1) / 2), a raised cosine over `edge`, 0 beyond; radius <= 0: no
+// mask.  fp64: what the mask adds to the error of a coefficient is far below the sums' own rounding.
+__device__ __forceinline__ float frc_mask(int i, int j, int n, float radius, float edge) {
+    if (!(radius > 0.f)) return 1.f;
+    const double c = 0.5 * (double)(n - 1);
+    const double di = (double)i - c, dj = (double)j - c;
+    return soft_mask(sqrt(di * di + dj * dj), radius, edge);
+}
+
+// ---- rings of a spectrum: r - 1/2 <= sqrt(ks^2 + kx^2) < r + 1/2, decided in integers -----------------------------------------
+// the least kx >= 0 with 4 kx^2 >= t (t below 2^23: exact in fp32, and the two loops make the estimate exact)
+__device__ __forceinline__ int frc_first_kx(int t) {
+    if (t <= 0) return 0;
+    int kx = (int)ceilf(0.5f * sqrtf((float)t));
+    while (kx > 0 && 4 * (kx - 1) * (kx - 1) >= t) --kx;
+    while (4 * kx * kx < t) ++kx;
+    return kx;
+}
+
+// the ring of s2 = ks^2 + kx^2 (at most 2 * 512^2: exact in fp32): the r with (2r - 1)^2 <= 4 s2 < (2r + 1)^2, 0 for s2 = 0
+__host__ __device__ static inline int ring_of(int s2) {
+    int r = (int)(sqrtf((float)s2) + 0.5f);
+    while ((2 * r + 1) * (2 * r + 1) <= 4 * s2) ++r;
+    while (r > 0 && (2 * r - 1) * (2 * r - 1) > 4 * s2) --r;
+    return r;
+}
+
 // ---- direct DFT --------------------------------------------------------------------------------------------------------------
 // kx = 0 .. n / 2 of a half spectrum; also the number of rings
 __host__ __device__ static inline int half_side(int n) { return n / 2 + 1; }

@@ -28,26 +28,18 @@
 //                       larger n runs the SAME code on the plane's own 4 n ld floats of the caller's workspace (LDS holds the
 //                       table only); a workgroup reads only what it wrote itself, behind workgroup barriers.
 //                       The plane is read completely before the first barrier and written after the last: out may be X.
-// ctf_power_kernel      a thread = one (ky, kx) of class k: the members in ascending position, H_i^2 formed and added in fp64.
+//                       The stages themselves are the __device__ functions of ctf_device.hpp, which the ring-power and
+//                       radial-filter kernels (spectrum_kernels.hpp) call as well: one body of code, the same bits.
+// ctf_power_kernel     a thread = one (ky, kx) of class k: the members in ascending position, H_i^2 formed and added in fp64.
 //                       The cleaned boundaries min(max(0, seg[0 .. k]), N) of its class are found by the workgroup itself (a
 //                       strided maximum and a fixed tree; a maximum does not depend on the order), the rule of avg_seg_kernel.
 // No atomics anywhere; every output is a pure function of its own plane / class.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "cluster_common.hpp"
+#include "ctf_device.hpp"
 
 namespace tvae_cluster {
-
-constexpr int CTF_THREADS = 256;
-constexpr int CTF_ONDIE_MAX = 128;       // the largest n whose two buffers sit in LDS
-
-__host__ __device__ static inline int ctf_ld(int n) { return half_side(n) | 1; }
-// floats of one buffer (re and im plane); x at row stride n | 1 fits: n | 1 <= 2 ld
-__host__ __device__ static inline long ctf_buf_floats(int n) { return 2L * n * ctf_ld(n); }
-static inline size_t ctf_lds_bytes(int n) {
-    return sizeof(float) * (2 * (size_t)n + (n <= CTF_ONDIE_MAX ? 2 * (size_t)ctf_buf_floats(n) : 0));
-}
 
 // H(ky, kx) from cf[5]; ky is the index in fftfreq order.  mode 1: the sign, -1 for H < 0 and +1 for anything else.
 __device__ __forceinline__ float ctf_value(const double* __restrict__ cf, int ky, int kx, int n, int mode) {
@@ -74,51 +66,6 @@ __global__ __launch_bounds__(CTF_THREADS) void ctf_eval_kernel(const double* __r
     H[(size_t)row * n * R + e] = ctf_value(coef + 5 * (size_t)row, ky, kx, n, mode);
 }
 
-// stages 2 and 3: (Or + i Oi)(a, col) = sum_k (c + i SGN s)((a k) mod n) (Ir + i Ii)(k, col); a, k = 0 .. n - 1, col = 0 .. R - 1
-template <int SGN>
-__device__ __forceinline__ void ctf_columns(const float2* tw, const float* in, float* outp, int n, int R, int ld, int wave,
-                                            int l31, int khalf) {
-    const int TA = (n + 31) >> 5, TK = (R + 31) >> 5;
-    const float* ir = in;
-    const float* ii = in + (size_t)n * ld;
-    float* orr = outp;
-    float* oi = outp + (size_t)n * ld;
-    for (int tile = wave; tile < TA * TK; tile += 4) {
-        const int ta = tile / TK, tk = tile - ta * TK;
-        const int a = ta * 32 + l31, col = tk * 32 + l31;
-        const bool aok = a < n, cok = col < R;
-        const int step = aok ? (2 * a) % n : 0;
-        int t = aok ? (a * khalf) % n : 0;
-        f32x16 accr, acci;
-        zero(accr);
-        zero(acci);
-        for (int k0 = 0; k0 < n; k0 += 2) {
-            const int k = k0 + khalf;
-            const bool ok = cok && k < n;
-            float br = 0.f, bi = 0.f;
-            if (ok) {
-                br = ir[(size_t)k * ld + col];
-                bi = ii[(size_t)k * ld + col];
-            }
-            const float2 w = tw[t];
-            const float wc = aok ? w.x : 0.f, wsn = aok ? (SGN > 0 ? w.y : -w.y) : 0.f;
-            accr = __builtin_amdgcn_mfma_f32_32x32x2f32(wc, br, accr, 0, 0, 0);
-            accr = __builtin_amdgcn_mfma_f32_32x32x2f32(-wsn, bi, accr, 0, 0, 0);
-            acci = __builtin_amdgcn_mfma_f32_32x32x2f32(wc, bi, acci, 0, 0, 0);
-            acci = __builtin_amdgcn_mfma_f32_32x32x2f32(wsn, br, acci, 0, 0, 0);
-            tw_advance(t, step, n);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = mfma_row(r, khalf, ta * 32);
-            if (row < n && cok) {
-                orr[(size_t)row * ld + col] = accr[r];
-                oi[(size_t)row * ld + col] = acci[r];
-            }
-        }
-    }
-}
-
 // grid = B.  X plane b at X + b x_stride, out[B][n][n] (may be X); exactly one of coef [B][5] and Hp (plane b at Hp + b h_stride)
 template <bool ONDIE>
 __global__ __launch_bounds__(CTF_THREADS) void ctf_filter_kernel(const float* X, long x_stride,
@@ -127,115 +74,33 @@ __global__ __launch_bounds__(CTF_THREADS) void ctf_filter_kernel(const float* X,
                                                                  float* ws, int n, int mode) {
     extern __shared__ __attribute__((aligned(16))) float ctf_sm[];
     float2* const tw = reinterpret_cast<float2*>(ctf_sm);
-    const int R = half_side(n), ld = ctf_ld(n), ldx = n | 1;
+    const int R = half_side(n), ld = ctf_ld(n);
     const long buf = ctf_buf_floats(n);
     const size_t b = blockIdx.x;
     float* const buf0 = ONDIE ? ctf_sm + 2 * n : ws + b * 2 * buf;
     float* const buf1 = buf0 + buf;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, khalf = lane >> 5;
-    const int TI = (n + 31) >> 5, TK = (R + 31) >> 5;
-    const size_t pl = (size_t)n * ld;                         // floats of a re or im plane
+    const CtfLane L = ctf_lane();
 
     dft_twiddles(tw, n, CTF_THREADS);
-    {
-        const float* x = X + b * x_stride;
-        for (int e = tid; e < n * n; e += CTF_THREADS) {
-            const int i = e / n, j = e - i * n;
-            buf0[i * ldx + j] = x[e];
-        }
-    }
+    ctf_load_plane(X + b * x_stride, buf0, n, L.tid);
     __syncthreads();
-
-    // ---- stage 1: rows.  A = x(i, j), B = (c, -s)((kx j) mod n) ----------------------------------------------------------------
-    for (int tile = wave; tile < TI * TK; tile += 4) {
-        const int ti = tile / TK, tk = tile - ti * TK;
-        const int i = ti * 32 + l31, kx = tk * 32 + l31;
-        const bool iok = i < n, kok = kx < R;
-        const int step = kok ? (2 * kx) % n : 0;
-        int t = kok ? (kx * khalf) % n : 0;
-        f32x16 accr, acci;
-        zero(accr);
-        zero(acci);
-        for (int j0 = 0; j0 < n; j0 += 2) {
-            const int j = j0 + khalf;
-            float a = 0.f;
-            if (iok && j < n) a = buf0[i * ldx + j];
-            const float2 w = tw[t];
-            accr = __builtin_amdgcn_mfma_f32_32x32x2f32(a, kok ? w.x : 0.f, accr, 0, 0, 0);
-            acci = __builtin_amdgcn_mfma_f32_32x32x2f32(a, kok ? -w.y : 0.f, acci, 0, 0, 0);
-            tw_advance(t, step, n);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = mfma_row(r, khalf, ti * 32);
-            if (row < n && kok) {
-                buf1[(size_t)row * ld + kx] = accr[r];
-                buf1[pl + (size_t)row * ld + kx] = acci[r];
-            }
-        }
-    }
+    ctf_rows(tw, buf0, buf1, n, R, ld, L.wave, L.l31, L.khalf);                  // stage 1: x (buffer 0) -> G (buffer 1)
     __syncthreads();
-
-    // ---- stage 2: columns, G (buffer 1) -> F (buffer 0, x is no longer needed) -----------------------------------------------
-    ctf_columns<-1>(tw, buf1, buf0, n, R, ld, wave, l31, khalf);
+    ctf_columns<-1>(tw, buf1, buf0, n, R, ld, L.wave, L.l31, L.khalf);           // stage 2: G -> F (buffer 0, x is no longer needed)
     __syncthreads();
-
-    // ---- F *= H w: an element is read and written by one thread ----------------------------------------------------------------
     {
         const double* cf = coef ? coef + 5 * b : nullptr;
         const float* hp = Hp ? Hp + b * h_stride : nullptr;
-        for (int e = tid; e < n * R; e += CTF_THREADS) {
-            const int ky = e / R, kx = e - ky * R;
-            float h;
-            if (cf) {
-                h = ctf_value(cf, ky, kx, n, mode);
-            } else {
-                h = hp[e];
-                if (mode == 1) h = h < 0.f ? -1.f : 1.f;
-            }
-            h *= (kx == 0 || 2 * kx == n) ? 1.f : 2.f;        // exact
-            const size_t at = (size_t)ky * ld + kx;
-            buf0[at] *= h;
-            buf0[pl + at] *= h;
-        }
+        ctf_multiply(buf0, n, R, ld, L.tid, [=](int ky, int kx, int e) {
+            if (cf) return ctf_value(cf, ky, kx, n, mode);
+            const float h = hp[e];
+            return mode == 1 ? (h < 0.f ? -1.f : 1.f) : h;
+        });
     }
     __syncthreads();
-
-    // ---- stage 3: columns back, F (buffer 0) -> P (buffer 1) -------------------------------------------------------------------
-    ctf_columns<1>(tw, buf0, buf1, n, R, ld, wave, l31, khalf);
+    ctf_columns<1>(tw, buf0, buf1, n, R, ld, L.wave, L.l31, L.khalf);            // stage 3: F -> P (buffer 1)
     __syncthreads();
-
-    // ---- stage 4: rows back.  A = (Pr, -Pi)(i, kx), B = (c, s)((kx j) mod n) -----------------------------------------------------
-    const float scale = 1.f / ((float)n * (float)n);
-    float* o = out + b * (size_t)n * n;
-    for (int tile = wave; tile < TI * TI; tile += 4) {
-        const int ti = tile / TI, tj = tile - ti * TI;
-        const int i = ti * 32 + l31, j = tj * 32 + l31;
-        const bool iok = i < n, jok = j < n;
-        const int step = jok ? (2 * j) % n : 0;
-        int t = jok ? (j * khalf) % n : 0;
-        f32x16 acc;
-        zero(acc);
-        for (int k0 = 0; k0 < R; k0 += 2) {
-            const int k = k0 + khalf;
-            float ar = 0.f, ai = 0.f;
-            if (iok && k < R) {
-                ar = buf1[(size_t)i * ld + k];
-                ai = buf1[pl + (size_t)i * ld + k];
-            }
-            const float2 w = tw[t];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, jok ? w.x : 0.f, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(-ai, jok ? w.y : 0.f, acc, 0, 0, 0);
-            tw_advance(t, step, n);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = mfma_row(r, khalf, ti * 32);
-            if (row < n && jok) o[(size_t)row * n + j] = scale * acc[r];
-        }
-    }
+    ctf_rows_back(tw, buf1, out + b * (size_t)n * n, n, R, ld, L.wave, L.l31, L.khalf);     // stage 4
 }
 
 // grid = K * tiles (tile fastest), tiles = ceil(n R / 256).  D[K][n][R] (fp64), counts[K] (written by tile 0)

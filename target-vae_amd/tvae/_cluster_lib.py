@@ -47,6 +47,11 @@ SIGNATURES = {
     # X, x_stride, coef (fp64, or None), Hp (or None), h_stride, out, ws, ws_floats, B, n, mode
     'tvae_fourier_filter': 'plpplppliii',
     'tvae_ctf_power': 'pppppiii',             # coef (fp64), order, seg, D (fp64), counts (int32), N, K, n
+    # X, x_stride, power (fp64), ws, ws_floats, B, n, mask_radius, mask_edge, background, demean
+    'tvae_ring_power': 'plppliiffii',
+    'tvae_ring_power_groups': 'pppppiii',     # power (fp64), order, seg, sums (fp64), counts (int32), N, K, Rr
+    # X, x_stride, prof, group (int32, or None), out, ws, ws_floats, B, n, G, interp
+    'tvae_radial_filter': 'plpppp' 'l' 'iiii',
     # Y, theta, dx, cls (int32), ref, theta_out, dx_out, score, best (int32), num, pp, yy (or None all three), ws, ws_floats,
     # N, C, n, K, A, S, t_scale, dtheta, mask_radius, mask_edge
     'tvae_pose_refine': 'ppppp' 'pppp' 'ppp' 'p' 'l' 'iiiiii' 'ffff',
@@ -86,6 +91,9 @@ QUERIES = {
     'tvae_class_frc_ws_floats': ('ii', 'l'),
     'tvae_image_normalize_ws_floats': ('iii', 'l'),
     'tvae_fourier_filter_ws_floats': ('ii', 'l'),
+    'tvae_radial_rings': ('i', 'i'),
+    'tvae_ring_power_ws_floats': ('ii', 'l'),
+    'tvae_radial_filter_ws_floats': ('ii', 'l'),
     'tvae_pose_refine_ws_floats': ('iiiii', 'l'),
     'tvae_pose_classify_ws_floats': ('iiiiii', 'l'),
     'tvae_class_project_ws_floats': ('iiiii', 'l'),

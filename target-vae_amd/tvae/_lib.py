@@ -309,6 +309,8 @@ _F64_OK |= {('tvae_ctf_eval', 0), ('tvae_fourier_filter', 2), ('tvae_ctf_power',
 _F64_OK |= {('tvae_pose_posterior', 4), ('tvae_pose_posterior', 13), ('tvae_pose_posterior', 14), ('tvae_class_average_weighted', 7)}
 # ... and the damping factors of tvae_pose_polish_step
 _F64_OK |= {('tvae_pose_polish_step', 10)}
+# ... and the ring powers of tvae_ring_power and both sides of tvae_ring_power_groups
+_F64_OK |= {('tvae_ring_power', 2), ('tvae_ring_power_groups', 0), ('tvae_ring_power_groups', 3)}
 
 
 def _ptr(t, name, pos):
