@@ -52,9 +52,21 @@ int tvae_conv1_fwd(const float* y, const float* bank, const float* bias, float* 
                    int pad, int C, int R, int act, float slope, tvae_stream_t stream);
 /* weight gradient of the same convolution (autograd of F.conv2d, models.py:215): dbank [C*R][Cin*k*k] =
  * sum over (img, position) of dpre[c][img][r][p] * window(y).  dpre is the PRE-activation gradient in the layout
- * of `out`.  ws: split-K workspace of ws_floats floats (>= 2*C*R*Cin*k*k recommended; fewer disables split-K). */
+ * of `out`.  ws: split-K workspace of ws_floats floats (>= 2*C*R*Cin*k*k recommended; fewer disables split-K).
+ * Both entry points return hipErrorInvalidValue, before any launch, for Ho <= 0 and for an R that is not a power of two. */
 int tvae_conv1_wgrad(const float* y, const float* dpre, float* dbank, float* ws, long ws_floats, int B, int Cin,
                      int n, int ksz, int pad, int C, int R, tvae_stream_t stream);
+/* tvae_conv1_f32_route: the kernel instance the pair above launches for this geometry and workspace size (ws_floats: 0 without
+ * a workspace), -1 where the entry point refuses (Ho <= 0, R not a power of two).  Host arithmetic only (no device call); the
+ * launchers execute the same plan (csrc/abi_conv_f32.hip: conv_fwd_plan / conv_wgrad_plan).
+ *   which = 0, forward:          0 generic implicit im2col (gemm_f32_kernel<LoadKContig, LoadConvPatchFwd>)
+ *                                1 / 2 / 3  conv1_fwd_img_kernel<false, 1> / <true, 1> / <true, 2>
+ *   which = 1, weight gradient:  0 generic (gemm_f32_kernel<LoadConvDY, LoadConvPatchWgrad>, split-K)
+ *                                1 / 2 / 3  conv1_wgrad_img_kernel<1, 16, 1> / <1, 32, 1> / <1, 32, 2>
+ *   which = 2, slices of the weight gradient's reduction (image slices; generic: split-K count after the workspace cap; 1: no
+ *              workspace pass, direct store)
+ *   which = 3, images per slice (generic: 0, its slices are k-chunks) */
+int tvae_conv1_f32_route(int B, int Cin, int n, int ksz, int pad, int C, int R, long ws_floats, int which);
 
 /* ---- dense layers (nn.Conv3d(.,.,1) src/models.py:347-351,356-358,390-392; nn.Linear src/models.py:107-121) ----
  * fwd:   Y[M][N] = act( W[M][K] X[K][N] + bias[m] + gbias[(n/group)][m] + res[m][n] )   (NULL terms skipped)
@@ -67,6 +79,18 @@ int tvae_linear_dgrad(const float* W, const float* dpre, const float* add, const
                       int K, long ldd, long ldx, int mask, float slope, tvae_stream_t stream);
 int tvae_linear_wgrad(const float* dpre, const float* X, float* dW, float* ws, long ws_floats, int M, int N, int K,
                       long ldd, long ldx, int accumulate, tvae_stream_t stream);
+/* tvae_linear_f32_route: what the three entry points above launch (csrc/abi_linear_f32.hip: linear_plan, which the launchers
+ * execute).  Host arithmetic only.  op: 0 fwd, 1 dgrad, 2 wgrad; M, N, K as the entry point takes them; ld_a, ld_b: its two
+ * leading dimensions in header order (fwd ldx, ldy; dgrad ldd, ldx; wgrad ldd, ldx); align_mask: bit i = the i-th POINTER
+ * argument in header order is 16-byte aligned (fwd W X bias gbias res Y; dgrad W dpre add aux dX; wgrad dpre X dW ws);
+ * flags: 1 gbias given, 2 res / add given, 4 mask != 0 AND aux given, 8 accumulate; ws_floats: 0 without a workspace.
+ *   which = 0, main loop: 0 gemm_f32_kernel with guarded loaders, 1 gemm_f32_glds_kernel (fwd), 2 gemm_f32_glds2_kernel (dgrad),
+ *              3 gemm_f32_kernel with the float4 loaders (wgrad), 4 empty output: nothing is launched
+ *   which = 1, epilogue: 0 scalar (tile_epilogue), 1 float4 (tile_epilogue_v4; only behind main loop 1 / 2)
+ *   which = 2, final split-K count (0: nothing launched; > 1: slabs in ws, then splitk_finalize_kernel)
+ * -1: unknown op or which. */
+int tvae_linear_f32_route(int op, int M, int N, int K, long ld_a, long ld_b, int align_mask, int flags, long ws_floats,
+                          int which);
 
 /* ---- reductions / skinny products used by bias grads, coordinate layer, last decoder layer ----
  * rowdot_seg: out[seg][m][o] = sum_{n in seg} X[m][n] * V[n][o]   (V NULL -> ones, no = 1; no in {1,2,3,4});

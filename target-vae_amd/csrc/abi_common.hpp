@@ -95,28 +95,38 @@ static const size_t X6_LDS_MAX = 160 * 1024;       // whole LDS of a CU (one wor
 // splitk_finalize_kernel (compiled in abi_linear_f32.hip alone) over the M x N outputs of `splits` slabs; the launch's error
 TVAE_INTERNAL int splitk_finalize(const float* ws, int splits, int M, int N, const Epilogue& ep, hipStream_t stream);
 
-// Host-side launcher.  `splits_wanted` <= 1 means no split-K.  `ws_floats` is the capacity of ws.
-template <class AL, class BL>
-static hipError_t launch_gemm(AL al, BL bl, const Epilogue& ep, int M, int N, int K, int splits_wanted,
-                              float* ws, long ws_floats, hipStream_t stream) {
-    if (M <= 0 || N <= 0) return hipSuccess;
-    const int tilesM = cdiv(M, BM), tilesN = cdiv(N, BN);
+// Split-K of the generic GEMM, decided on the host from shapes and workspace alone (the launcher below and the route queries
+// tvae_conv1_f32_route / tvae_linear_f32_route both read it): `splits_wanted` <= 1 means no split-K, `ws_floats` is the capacity
+// of the workspace (0 without one); fewer than two slabs of M x N floats -> no split; k-chunks are whole k-steps, and the
+// count is what those chunks need.  splits == 0: an empty output, nothing to launch.
+struct GemmSplit {
+    int splits, kchunk;
+};
+static inline GemmSplit gemm_split_plan(int M, int N, int K, int splits_wanted, long ws_floats) {
+    if (M <= 0 || N <= 0) return {0, 0};
     int splits = splits_wanted < 1 ? 1 : splits_wanted;
     if (splits > 1) {
         const long per = (long)M * N;
-        const long cap = ws ? ws_floats / per : 0;
+        const long cap = ws_floats / per;
         if (cap < 2) splits = 1; else if (splits > cap) splits = (int)cap;
         if (splits > 65535) splits = 65535;
     }
-    int kchunk = cdiv(cdiv(K > 0 ? K : 1, splits), BK) * BK;
-    splits = cdiv(K > 0 ? K : 1, kchunk);
-    const TileMap tm{tilesM, tilesN, splits};
-    float* wsp = splits > 1 ? ws : nullptr;
+    const int kchunk = cdiv(cdiv(K > 0 ? K : 1, splits), BK) * BK;
+    return {cdiv(K > 0 ? K : 1, kchunk), kchunk};
+}
+
+// Host-side launcher of a planned generic GEMM (gemm_split_plan of the same M, N, K; ws: the workspace the plan counted).
+template <class AL, class BL>
+static hipError_t launch_gemm(AL al, BL bl, const Epilogue& ep, int M, int N, int K, const GemmSplit& sp, float* ws,
+                              hipStream_t stream) {
+    if (sp.splits < 1) return hipSuccess;
+    const TileMap tm{cdiv(M, BM), cdiv(N, BN), sp.splits};
+    float* wsp = sp.splits > 1 ? ws : nullptr;
     hipLaunchKernelGGL((gemm_f32_kernel<AL, BL>), dim3(tm.grid()), dim3(GEMM_THREADS), 0, stream, al, bl, ep, M, N, K,
-                       kchunk, wsp, tm);
+                       sp.kchunk, wsp, tm);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (splits > 1) e = (hipError_t)splitk_finalize(ws, splits, M, N, ep, stream);
+    if (sp.splits > 1) e = (hipError_t)splitk_finalize(ws, sp.splits, M, N, ep, stream);
     return e;
 }
 

@@ -87,6 +87,8 @@ QUERIES = {
     'tvae_conv1_dft_frame': ('iiiiiii', 'i'),
     'tvae_conv1_dft_ring': ('iiiiiii', 'i'),
     'tvae_conv1_dft_route': ('iiiiiiiii', 'i'),
+    'tvae_conv1_f32_route': ('iiiiiiili', 'i'),
+    'tvae_linear_f32_route': ('iiiilliili', 'i'),
     'tvae_enc_tail_wgrad_x6_ws_floats': ('l', 'l'),
     'tvae_enc_tail_wide_max_rows': ('', 'i'),
     'tvae_linear_wgrad_x6_ws_floats': ('iii', 'l'),
