@@ -737,6 +737,70 @@ int tvae_class_average_weighted(const float* Y, const int* img, const float* the
                                 const int* seg, float* avg, double* wsum, int* counts, float* ws, long ws_floats, int N, int E,
                                 int C, int n, int K, float t_scale, tvae_stream_t stream);
 
+/* ---- CTF in the template: the norm of the CTF-filtered template and the weighted per-class power of the CTF ------------------
+ *
+ * The pose searches above score an image against the rendered class average as if no transfer function lay between them.
+ * Under the model Y_i = H_i (*) P_j + noise, H_i the real, radially symmetric transfer function of tvae_ctf_eval (mode 0) of
+ * image i and (*) the circular convolution of the CTF section's filter, the squared residual is
+ *     |Y_i - H_i (*) P_j|^2 = |Y_i|^2 - 2 <H_i (*) Y_i, P_j> + |H_i (*) P_j|^2.
+ * H_i is real and even, so the filter is self-adjoint: the middle term is the num table of tvae_pose_classify run on the
+ * stack that tvae_fourier_filter (coef, mode 0) has already filtered.  The last term is what tvae_template_ctf_power forms;
+ * the M-step of the soft average under this model is a Wiener form whose denominator tvae_ctf_power_entries forms.
+ * The shift of a candidate enters num through windows of the extended template but enters the last term circularly (a
+ * circular shift is a phase factor, which |.|^2 drops): the two agree exactly while the masked support of the template moved
+ * by the shift stays inside the frame, and differ by what leaves the frame otherwise.
+ *
+ * tvae_template_ctf_power.  theta[N], dx[N][2], cand[N][M], ref[K][C][n][n], A, t_scale, dtheta, mask_radius and mask_edge as
+ * for tvae_pose_classify; coef[N][5] as for tvae_ctf_eval.  For image i, slot m with k = cand[i][m] and angle index
+ * a' = 0 .. 2A (NA = 2A + 1), T is the template of tvae_pose_refine of reference k at the angle theta[i] + (a' - A) dtheta on
+ * the frame r, q = 0 .. n - 1, its mask included: the same device functions build it, so its pixels are bit for bit the centre
+ * window of that kernel's extended template.  Per channel F = DFT(T) by stages 1 and 2 of the filter (rows to the half
+ * spectrum, then columns: the code of tvae_ring_power, fp32 chains on the matrix pipe), H = H_i(ky, kx) the fp32 value of
+ * tvae_ctf_eval, mode 0, formed in registers, and
+ *     ppc[i][m][a'] = (float)( (1 / n^2) sum_ch sum_ky sum_kx w_kx (double)H^2 (double)|F|^2 ).
+ * Order: (double)H (double)H is exact, |F|^2 = re re + im im is formed in fp64 from the fp32 coefficient (the squares are
+ * exact, the sum is one rounding), their product is one rounding and w_kx is exact.  Thread t of 256 adds the coefficients
+ * e = ky R + kx = t, t + 256, ... (ascending ky index, then kx) of channel 0, then of channel 1, ... in ONE fp64 chain from 0; the
+ * 256 chains are added by the fixed tree of tvae_ring_power's demean (s[t] += s[t + w] for w = 128, 64, ..., 1); the total is
+ * divided by (double)(n n) and rounded to fp32 once.
+ * One workgroup owns one (image, slot, angle) from template to sum; the template plane and the half spectrum stay in LDS (the
+ * budget of tvae_ring_power: 134 144 bytes at n = 128), and neither H, T nor the spectrum is ever in memory.  The workspace is
+ * the 2-float word of tvae_fourier_filter and is never touched.  No atomics: bitwise reproducible; row i depends on image i's
+ * pose, its row of candidates, coef[i] and the references that row names only: not on N, K or the launch.
+ * A slot outside [0, K) gives zeros and nothing of ref is read for it.  A pose that puts every sample out of frame (NaN, +-inf
+ * and huge poses among them) gives exact 0 (for a finite H).  A non-finite coef row gives that image's IEEE results and touches
+ * no other row.
+ *
+ * Supported: 1 <= N <= 2^24, 1 <= C <= 16, 2 <= n <= 128, 1 <= K <= 65535, 1 <= M <= 64, 0 <= A <= 32 (the range of
+ * tvae_pose_classify without S), N M NA < 2^31, t_scale finite and > 0, dtheta finite, the mask rules of tvae_class_frc, coef
+ * and ws 8-byte aligned, ws_floats at least the query's, no output overlapping an input.  Anything else returns
+ * hipErrorInvalidValue (1) and writes nothing, and the query returns 0.
+ *
+ * tvae_ctf_power_entries.  E entries grouped by class with img[e], w[e] and seg[K + 1] exactly as for
+ * tvae_class_average_weighted: seg is cleaned on the device with E as the bound, min(max(0, seg[0], ..., seg[k]), E), and an
+ * entry is LIVE if img[e] is inside [0, N) and w[e] is finite and > 0.
+ *     D[k][ky][kx] = sum over the live entries of class k in ascending e of (double)w_e (double)H^2,
+ * H the fp32 value of tvae_ctf_eval (mode 0) of image img[e], (double)H (double)H exact, its product with the weight one
+ * rounding, the sum fp64; wsum[k] = the fp64 sum of the live weights in ascending e and counts[k] their number.  A thread owns
+ * one (k, coefficient).  No atomics; class k is independent of K and of the other classes.  With unit weights over a partition
+ * D is bit for bit that of tvae_ctf_power.
+ *
+ * Supported: the range of tvae_ctf_power (2 <= n <= 1024, 1 <= N <= 2^24, 1 <= K <= 65535, K ceil(n R / 256) < 2^31) with
+ * 1 <= E <= 2^30, coef, D and wsum 8-byte aligned, no output overlapping an input or another output.  Anything else returns
+ * hipErrorInvalidValue (1) and writes nothing. */
+
+/* floats of workspace of tvae_template_ctf_power: 2 (one 8-byte word that is never touched).  0 for unsupported arguments. */
+long tvae_template_ctf_power_ws_floats(int N, int C, int n, int M, int A);
+
+/* ppc[N][M][NA] */
+int tvae_template_ctf_power(const float* theta, const float* dx, const int* cand, const float* ref, const double* coef,
+                            float* ppc, float* ws, long ws_floats, int N, int C, int n, int K, int M, int A, float t_scale,
+                            float dtheta, float mask_radius, float mask_edge, tvae_stream_t stream);
+
+/* D[K][n][R] (fp64), wsum[K] (fp64), counts[K] (int32) */
+int tvae_ctf_power_entries(const double* coef, const int* img, const float* w, const int* seg, double* D, double* wsum,
+                           int* counts, int N, int E, int K, int n, tvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,20 @@ static inline size_t ctf_lds_bytes(int n) {
     return sizeof(float) * (2 * (size_t)n + (n <= CTF_ONDIE_MAX ? 2 * (size_t)ctf_buf_floats(n) : 0));
 }
 
+// H(ky, kx) from cf[5] (ctf_kernels.hpp states the arithmetic); ky is the index in fftfreq order.  mode 1: the sign, -1 for H < 0 and +1 for anything else.
+__device__ __forceinline__ float ctf_value(const double* __restrict__ cf, int ky, int kx, int n, int mode) {
+    const int ks = ky < (n + 1) / 2 ? ky : ky - n;
+    const double q = (double)(ks * ks + kx * kx) / (double)(n * n);
+    double t = cf[2] * q + cf[3] * (q * q);
+    t -= rint(t);
+    double s, c;
+    sincospi(2.0 * t, &s, &c);
+    const float osc = (float)(cf[0] * s + cf[1] * c);
+    const float h = osc * expf((float)(-cf[4] * q));
+    if (mode == 1) return h < 0.f ? -1.f : 1.f;
+    return h;
+}
+
 // the lane's place in its wave and the wave's in the workgroup
 struct CtfLane {
     int tid, wave, l31, khalf;

@@ -41,20 +41,7 @@
 
 namespace tvae_cluster {
 
-// H(ky, kx) from cf[5]; ky is the index in fftfreq order.  mode 1: the sign, -1 for H < 0 and +1 for anything else.
-__device__ __forceinline__ float ctf_value(const double* __restrict__ cf, int ky, int kx, int n, int mode) {
-    const int ks = ky < (n + 1) / 2 ? ky : ky - n;
-    const double q = (double)(ks * ks + kx * kx) / (double)(n * n);
-    double t = cf[2] * q + cf[3] * (q * q);
-    t -= rint(t);
-    double s, c;
-    sincospi(2.0 * t, &s, &c);
-    const float osc = (float)(cf[0] * s + cf[1] * c);
-    const float h = osc * expf((float)(-cf[4] * q));
-    if (mode == 1) return h < 0.f ? -1.f : 1.f;
-    return h;
-}
-
+// (ctf_value itself is defined in ctf_device.hpp: tvae_template_ctf_power, another unit, forms the same H)
 // grid = N * tiles (tile fastest), tiles = ceil(n R / 256).  H[N][n][R]
 __global__ __launch_bounds__(CTF_THREADS) void ctf_eval_kernel(const double* __restrict__ coef, float* __restrict__ H, int n,
                                                                int tiles, int mode) {

@@ -74,6 +74,10 @@ SIGNATURES = {
     'tvae_pose_posterior': 'ppppp' 'pp' 'ppppp' 'pppp' 'iiiiiii' 'fff',
     # Y, img (int32), theta_e, dx_e, w, seg (int32), avg, wsum (fp64), counts (int32), ws, ws_floats, N, E, C, n, K, t_scale
     'tvae_class_average_weighted': 'pppppp' 'pppp' 'l' 'iiiii' 'f',
+    # theta, dx, cand (int32), ref, coef (fp64), ppc, ws, ws_floats, N, C, n, K, M, A, t_scale, dtheta, mask_radius, mask_edge
+    'tvae_template_ctf_power': 'ppppp' 'pp' 'l' 'iiiiii' 'ffff',
+    # coef (fp64), img (int32), w, seg (int32), D, wsum (fp64 both), counts (int32), N, E, K, n
+    'tvae_ctf_power_entries': 'pppp' 'ppp' 'iiii',
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {
@@ -101,6 +105,7 @@ QUERIES = {
     'tvae_class_eigen_chunk': ('iiiii', 'i'),
     'tvae_class_average_weighted_ws_floats': ('iiii', 'l'),
     'tvae_class_average_weighted_chunk': ('iiii', 'i'),
+    'tvae_template_ctf_power_ws_floats': ('iiiii', 'l'),
 }
 
 # the shape limits every image family shares (SIDE_MAX, PLANES_MAX, CLASSES_MAX of csrc/cluster_common.hpp)

@@ -313,6 +313,9 @@ _F64_OK |= {('tvae_pose_posterior', 4), ('tvae_pose_posterior', 13), ('tvae_pose
 _F64_OK |= {('tvae_pose_polish_step', 10)}
 # ... and the ring powers of tvae_ring_power and both sides of tvae_ring_power_groups
 _F64_OK |= {('tvae_ring_power', 2), ('tvae_ring_power_groups', 0), ('tvae_ring_power_groups', 3)}
+# ... and the coefficient rows of tvae_template_ctf_power and tvae_ctf_power_entries, and the sums of the latter
+_F64_OK |= {('tvae_template_ctf_power', 4), ('tvae_ctf_power_entries', 0), ('tvae_ctf_power_entries', 4),
+            ('tvae_ctf_power_entries', 5)}
 
 
 def _ptr(t, name, pos):

@@ -205,10 +205,12 @@ def save_outputs(out_dir, avg, counts, particles=False, stem='class_averages'):
 
 # ---- class_averages.py: the averages from the files a clustering run wrote ------------------------------------------------
 def add_ctf_flags(p, corrections, wiener=True):
-    """--ctf, --ctf-correct and --scale (and --wiener-tau): the CTF correction of class_averages.py and class_resolution.py."""
+    """--ctf, --ctf-correct and --scale (and --wiener-tau): the CTF correction of class_averages.py and class_resolution.py.
+    Empty `corrections`: no --ctf-correct (ml_class_averages.py, whose model fixes the correction)."""
     p.add_argument('--ctf', default=None, help='CTF parameters, one row per image (the eight-column table of training): '
                                                'also write the CTF-corrected results')
-    p.add_argument('--ctf-correct', default=corrections[0], choices=list(corrections), help='phase flipping or Wiener weights')
+    if corrections:
+        p.add_argument('--ctf-correct', default=corrections[0], choices=list(corrections), help='phase flipping or Wiener weights')
     if wiener:
         p.add_argument('--wiener-tau', default=0.1, type=float, help='regularisation of the Wiener weights, 1 / SNR')
     p.add_argument('--scale', default=1, type=float, help='downsampling factor of the stack against the pixel size in --ctf')

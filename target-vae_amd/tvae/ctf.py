@@ -189,6 +189,81 @@ def power(coef, labels, n, n_clusters=None, device=None):
     return D, counts
 
 
+def template_power(theta, dx, slots, refs, coef, t_scale=1.0, angle_steps=8, angle_step=None, mask_radius=None, mask_edge=0.0):
+    """|H_i (*) T|^2 of every (image, slot, angle): theta [N] or [N][1], dx [N][2], refs [K][C][n][n] (CUDA fp32), slots [N][M]
+    integers (a value outside [0, K) gives zeros), coef [N][5] -> ppc fp32 [N][M][NA], NA = 2 angle_steps + 1.  T is the template
+    of tvae.classify.classify_poses of the slot's reference at the angle theta + a angle_step, a = -A .. A, H_i the transfer
+    function of coef[i] (tvae_template_ctf_power).  The shift of a candidate does not enter: it is a phase factor."""
+    from . import classify, refine
+    what = 'template_power'
+    CL.require_f32(refs, what, 'refs')
+    CL.require_f32(theta, what, 'theta')
+    CL.require_f32(dx, what, 'dx')
+    if refs.dim() != 4 or refs.shape[-1] != refs.shape[-2]:
+        raise TvaeHipError(f'{what}: refs must be [K][C][n][n] (square), got {tuple(refs.shape)}')
+    K, C, n, _ = refs.shape
+    dev = refs.device
+    N = theta.numel()
+    if tuple(dx.shape) != (N, 2) or theta.device != dev or dx.device != dev:
+        raise TvaeHipError(f'{what}: theta must hold N = {N} angles and dx must be [N][2], on the device of refs')
+    cand, M = classify._as_table(slots, N, dev, what)
+    c = _coef_tensor(coef, dev, what)
+    if c.shape[0] != N:
+        raise TvaeHipError(f'{what}: coef must hold N = {N} rows, got {c.shape[0]}')
+    A = int(angle_steps)
+    step, t = refine.angle_step_of(A, angle_step), float(t_scale)
+    radius, edge = 0.0 if mask_radius is None else float(mask_radius), float(mask_edge)
+    if not (np.isfinite(t) and t > 0 and np.isfinite(step)):
+        raise TvaeHipError(f'{what}: t_scale = {t_scale} must be finite and positive and angle_step = {angle_step} finite')
+    if not (np.isfinite(radius) and np.isfinite(edge) and edge >= 0):
+        raise TvaeHipError(f'{what}: mask_radius = {mask_radius} and mask_edge = {mask_edge} must be finite, the edge not negative')
+    if not (1 <= K <= CL.MAX_CLASSES and CL.query('tvae_template_ctf_power_ws_floats', 1, C, n, M, A) > 0):
+        raise TvaeHipError(f'{what}: K={K}, C={C}, n={n}, M={M}, angle_steps={A} outside the supported range (2 <= n <= '
+                           f'{refine.MAX_SIDE}, C <= {refine.MAX_CHANNELS}, M <= {classify.MAX_CANDIDATES}, 0 <= angle_steps <= '
+                           f'{refine.MAX_ANGLE_STEPS})')
+    NA = 2 * A + 1
+    th = theta.reshape(N)
+    ppc = torch.empty(N, M, NA, dtype=torch.float32, device=dev)
+    stepN = CL.slice_step(N, MAX_PLANES, (2 ** 31 - 1) // (M * NA))       # one workgroup per (image, slot, angle)
+    wsf = CL.query('tvae_template_ctf_power_ws_floats', stepN, C, n, M, A)
+    ws = CL.workspace(wsf, dev)
+    with torch.cuda.device(dev):
+        for i0 in range(0, N, stepN):
+            i1 = min(i0 + stepN, N)
+            sl = slice(i0, i1)
+            CL.call('tvae_template_ctf_power', th[sl], dx[sl], cand[sl], refs, c[sl], ppc[sl], ws, wsf, i1 - i0, C, n, K, M, A,
+                    t, step, radius, edge)
+    return ppc
+
+
+def power_weighted(coef, entries, n, n_clusters):
+    """coef [N][5], entries as tvae.ml2d.entries_by_class returns them (img, w, seg on one CUDA device) -> (D fp64 [K][n][R],
+    wsum fp64 [K], counts int32 [K]): D[k] = sum w_e H_img[e]^2 over the live entries of class k (tvae_ctf_power_entries), the
+    denominator of the Wiener M-step beside tvae.ml2d.weighted_class_averages of the filtered stack."""
+    what = 'power_weighted'
+    img, w, seg = (entries[k] for k in ('img', 'w', 'seg'))
+    K, n = int(n_clusters), int(n)
+    if not (torch.is_tensor(img) and img.is_cuda):
+        raise TvaeHipError(f'{what}: entries must be CUDA tensors (no CPU fallback)')
+    dev = img.device
+    E = img.numel()
+    for nm, t, dt, shape in (('img', img, torch.int32, (E,)), ('w', w, torch.float32, (E,)), ('seg', seg, torch.int32, (K + 1,))):
+        if not (torch.is_tensor(t) and t.device == dev and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+            raise TvaeHipError(f'{what}: entries[{nm!r}] must be a contiguous {dt} tensor of shape {shape} on one device')
+    c = _coef_tensor(coef, dev, what)
+    N = c.shape[0]
+    if not (1 <= K <= CL.MAX_CLASSES and 2 <= n <= CL.MAX_SIDE and N <= MAX_PLANES and E <= 1 << 30):
+        raise TvaeHipError(f'{what}: N={N}, E={E}, K={K}, n={n} outside the supported range')
+    D = torch.zeros(K, n, n // 2 + 1, dtype=torch.float64, device=dev)
+    wsum = torch.zeros(K, dtype=torch.float64, device=dev)
+    counts = torch.zeros(K, dtype=torch.int32, device=dev)
+    if E == 0:                                                # nothing to add: every class is empty
+        return D, wsum, counts
+    with torch.cuda.device(dev):
+        CL.call('tvae_ctf_power_entries', c, img, w, seg, D, wsum, counts, N, E, K, n)
+    return D, wsum, counts
+
+
 def class_averages_ctf(images, theta, dx, labels, coef, n_clusters=None, t_scale=1.0, correct='wiener', tau=0.1):
     """CTF-corrected aligned class averages -> (avg fp32 [K][C][n][n], counts int32 [K], D fp64 [K][n][R]).
     images [N][C][n][n], theta, dx, labels, n_clusters, t_scale as tvae.align.class_averages; coef [N][5].

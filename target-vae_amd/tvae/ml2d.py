@@ -24,6 +24,7 @@ import torch
 
 from . import _cluster_lib as CL
 from . import align, classify, refine, stack_cli
+from . import ctf as ctf_mod
 from ._lib import TvaeHipError
 
 MAX_KEEP = 64                     # TVAE_POSTERIOR_MAX_KEEP
@@ -188,18 +189,35 @@ def _slices(N, M, A, S):
     return CL.slice_step(N, CL.MAX_PLANES, refine.WS_FLOATS // per)
 
 
-def e_step(images, theta, dx, slots, refs, sigma2, logprior, keep, t_scale, A, step, S, mask_radius, mask_edge):
+def raw_sum_squares(images, chunk=4096):
+    """images [N][C][n][n] -> fp32 [N]: the fp64 sum of squares of every image, rounded to fp32 once (torch, slice by slice)."""
+    N = images.shape[0]
+    out = torch.empty(N, dtype=torch.float32, device=images.device)
+    for i0 in range(0, N, chunk):
+        out[i0:i0 + chunk] = images[i0:i0 + chunk].double().pow(2).reshape(min(chunk, N - i0), -1).sum(1).to(torch.float32)
+    return out
+
+
+def e_step(images, theta, dx, slots, refs, sigma2, logprior, keep, t_scale, A, step, S, mask_radius, mask_edge, ctf=None):
     """classify_poses(tables=True) -> pose_posteriors, slice by slice over the stack: the tables never exist for more than a
     slice.  -> the dict of pose_posteriors for the whole stack.  sigma2 None: only dict(rmin) is returned, the smallest live
-    residual of every image."""
+    residual of every image.
+    ctf = (coef [N][5] on the device, yy fp32 [N] of the RAW images): `images` is the stack filtered with H_i already, so num is
+    <H_i (*) Y_i, P_j>; pp is tvae.ctf.template_power expanded over the NS^2 shifts and yy the raw images': the three tables of
+    the residual |Y_i - H_i (*) P_j|^2."""
     N, n, K = images.shape[0], images.shape[-1], refs.shape[0]
     M = slots.shape[1]
+    NS = 2 * S + 1
     stepN = _slices(N, M, A, S)
     parts = []
     for i0 in range(0, N, stepN):
         sl = slice(i0, min(i0 + stepN, N))
         num, pp, yy = classify.classify_poses(images[sl], theta[sl], dx[sl], slots[sl], refs, t_scale, A, step, S, mask_radius,
                                               mask_edge, tables=True)[5:]
+        if ctf is not None:
+            ppc = ctf_mod.template_power(theta[sl], dx[sl], slots[sl], refs, ctf[0][sl], t_scale, A, step, mask_radius, mask_edge)
+            pp = ppc[:, :, :, None, None].expand(-1, -1, -1, NS, NS).contiguous()
+            yy = ctf[1][sl].contiguous()
         if sigma2 is None:
             parts.append(dict(rmin=min_residuals(num, pp, yy, slots[sl], K)))
         else:
@@ -211,7 +229,7 @@ def e_step(images, theta, dx, slots, refs, sigma2, logprior, keep, t_scale, A, s
 
 def ml_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3, angle_range=math.pi / 8, angle_steps=8,
               shift=2, mask_radius=None, mask_edge=0.0, keep=8, sigma2=None, latents=None, candidates=None,
-              cross_halves=False):
+              cross_halves=False, ctf=None, wiener_tau=0.1):
     """Expectation-maximisation over a fixed discrete set of poses.  The references start as the hard class averages of
     (labels, theta, dx); the pose grid stays centred on the INPUT poses in every round and the angle step angle_range /
     angle_steps is fixed.  Per round: candidate_lists of the current labels -> classify_poses(tables=True) ->
@@ -222,6 +240,14 @@ def ml_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3,
     sigma2 to avoid it).  cross_halves: the images are split by the parity of their
     position in their starting class, the M-step fills the two half-set averages and every image is scored against the half
     it is not in.
+    ctf: coef rows [N][5] (tvae.ctf.coefficients) or None.  With them the model is Y_i = H_i (*) P_j + noise: the E-step takes
+    num from the stack filtered with H_i (formed once), pp from tvae.ctf.template_power and yy from the raw images; the M-step is
+    the Wiener form of tvae.ctf.class_averages_ctf with posterior weights, mean_k = weighted_class_averages of the filtered
+    stack, D_k = tvae.ctf.power_weighted, G_k = 1 / (D_k / W_k + wiener_tau) in fp64 rounded once (zeros where W_k = 0) and the
+    reference filter_stack(mean, planes=G); the start references are class_averages_ctf(..., 'wiener', wiener_tau).  The shift
+    of a candidate enters num by windows of the extended template and pp circularly: the two agree exactly while the masked
+    support moved by `shift` stays inside the frame.  history['ctf_power'] is then D [K][n][R] of the returned averages.
+    ctf None: every line runs as without the argument.
     -> (avg fp32 [K][C][n][n], wsum fp64 [K], labels' int64 [N] = the arg-max of the slot posterior mapped through the
     candidates (ties to the lowest slot; an image with no live candidate keeps its label), theta' [N], dx' [N][2] the top-1
     poses, history): history['log_likelihood'], ['sigma2'] (the value each round's E-step used), ['kept'] per round,
@@ -241,10 +267,37 @@ def ml_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3,
         latents = torch.as_tensor(latents).to(dev)
     step = float(angle_range) / max(A, 1)
     R = 2 * K if cross_halves else K                         # references: [half 0 | half 1] with cross_halves
-    refs = refine.round_references(images, th0, d0, lab64, K, t_scale, cross_halves)
+    coef = tau = Dk = None
+    scored, extra = images, None                              # what num is formed from, and the tables that replace pp and yy
+    if ctf is not None:
+        coef, tau = ctf_mod._coef_tensor(ctf, dev, what), float(wiener_tau)
+        if coef.shape[0] != N:
+            raise TvaeHipError(f'{what}: ctf must hold N = {N} rows, got {coef.shape[0]}')
+        if not tau > 0:
+            raise TvaeHipError(f'{what}: wiener_tau = {wiener_tau} must be positive')
+        scored = ctf_mod.filter_stack(images, coef=coef, mode='multiply')
+        extra = (coef, raw_sum_squares(images))
     if cross_halves:
         own = refine.cross_half_labels(lab64, K)
         half = ((own >= 0) & (own < K)).to(torch.int64)      # an image at an odd position of its class is in half 1
+    if ctf is None:
+        refs = refine.round_references(images, th0, d0, lab64, K, t_scale, cross_halves)
+    elif cross_halves:                                        # the half-set split of refine.round_references: half h of class k
+        inside = torch.where(own >= 0, (own + K) % (2 * K), own)          # is the label h K + k of the half the image is IN
+        refs = ctf_mod.class_averages_ctf(images, th0, d0, inside, coef, R, t_scale, 'wiener', tau)[0]
+    else:
+        refs = ctf_mod.class_averages_ctf(images, th0, d0, lab64, coef, K, t_scale, 'wiener', tau)[0]
+
+    def m_step(entries, classes):
+        """-> (references [classes][C][n][n], wsum fp64 [classes], D or None)"""
+        if ctf is None:
+            avg_, wsum_, _ = weighted_class_averages(images, entries, classes, t_scale)
+            return avg_, wsum_, None
+        mean, wsum_, _ = weighted_class_averages(scored, entries, classes, t_scale)
+        D, W, _ = ctf_mod.power_weighted(coef, entries, n, classes)
+        Wc = W[:, None, None]
+        G = torch.where(Wc > 0, 1.0 / (D / torch.where(Wc > 0, Wc, torch.ones_like(Wc)) + tau), torch.zeros_like(D))
+        return ctf_mod.filter_stack(mean, planes=G.to(torch.float32).contiguous()), wsum_, D
     logprior = None
     s2 = None if sigma2 is None else float(np.float32(sigma2))
     hist = dict(log_likelihood=[], sigma2=[], kept=[], pi=[])
@@ -254,24 +307,25 @@ def ml_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3,
         cand = classify.candidate_lists(cur, K, latents, candidates)
         slots = classify.cross_half_candidates(lab64, cand, K) if cross_halves else cand
         if s2 is None:
-            rmin = e_step(images, th0, d0, slots, refs, None, None, P, t_scale, A, step, S, mask_radius, mask_edge)['rmin']
+            rmin = e_step(scored, th0, d0, slots, refs, None, None, P, t_scale, A, step, S, mask_radius, mask_edge,
+                          extra)['rmin']
             ok = torch.isfinite(rmin)
             if not bool(ok.any()):
                 raise TvaeHipError(f'{what}: no image has a live candidate: sigma2 cannot be estimated')
             s2 = float(np.float32(float(rmin[ok].mean() / (C * n * n))))     # the fp32 value the kernel gets
         lp = logprior if (logprior is None or not cross_halves) else torch.cat([logprior, logprior])
-        post = e_step(images, th0, d0, slots, refs, s2, lp, P, t_scale, A, step, S, mask_radius, mask_edge)
+        post = e_step(scored, th0, d0, slots, refs, s2, lp, P, t_scale, A, step, S, mask_radius, mask_edge, extra)
         live = post['kept'] > 0
         cls = post['cls'].to(torch.int64)
         if cross_halves:                                      # an entry of class k goes to the half its image is in
             fill = torch.where(cls >= 0, cls % K + K * half[:, None], cls)
             ent = entries_by_class(fill, post['w'], post['theta'], post['dx'], R)
-            refs, wsum2, _ = weighted_class_averages(images, ent, R, t_scale)
+            refs, wsum2, Dk = m_step(ent, R)
             wsum = wsum2[:K] + wsum2[K:]
             cls = torch.where(cls >= 0, cls % K, cls)
         else:
             ent = entries_by_class(cls, post['w'], post['theta'], post['dx'], K)
-            refs, wsum, _ = weighted_class_averages(images, ent, K, t_scale)
+            refs, wsum, Dk = m_step(ent, K)
         hist['log_likelihood'].append(log_likelihood(post['lse'], live, C, n, s2, A, S))
         hist['sigma2'].append(s2)
         hist['kept'].append(float(post['kept'][live].double().mean()) if bool(live.any()) else 0.0)
@@ -285,17 +339,21 @@ def ml_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3,
         cur = torch.where(live, won, cur)
     if cross_halves:                                          # the averages of the whole classes from the last entries
         ent = entries_by_class(cls, post['w'], post['theta'], post['dx'], K)
-        avg, wsum, _ = weighted_class_averages(images, ent, K, t_scale)
+        avg, wsum, Dk = m_step(ent, K)
     else:
         avg = refs
     hist = dict(log_likelihood=np.asarray(hist['log_likelihood']), sigma2=np.asarray(hist['sigma2']),
                 kept=np.asarray(hist['kept']), pi=np.stack(hist['pi']), sigma2_next=s2, entropy=class_entropy(post['resp']),
                 resp=post['resp'], candidates=cand, entries=ent, posterior=post)
+    if ctf is not None:
+        hist['ctf_power'] = Dk
     return avg, wsum, cur, post['theta'][:, 0].contiguous(), post['dx'][:, 0].contiguous(), hist
 
 
 # ---- ml_class_averages.py: soft averages, labels and poses from the files a clustering run wrote -----------------------------
-def build_parser() -> argparse.ArgumentParser:
+def build_parser(ctf=False) -> argparse.ArgumentParser:
+    """ctf=True adds --ctf, --wiener-tau and --scale (what ml_class_averages.py parses; no --ctf-correct: the model fixes the
+    correction); the default is the parser without them."""
     p = argparse.ArgumentParser('Maximum-likelihood 2-D class averages of a clustered stack: soft assignment over classes and poses')
     stack_cli.add_stack_flags(p)
     stack_cli.add_grid_flags(p)
@@ -303,13 +361,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument('--keep', default=8, type=int, help='(class, pose) entries an image contributes to the averages (at most 64)')
     p.add_argument('--sigma2', default=None, type=float, help='noise variance per pixel of the first round; default: estimated '
                                                               'from the best residuals')
+    if ctf:
+        align.add_ctf_flags(p, ())
     return p
 
 
 def save_outputs(out_dir, avg, wsum, labels, theta, dx, hist, particles, rot_shape):
     """class_weights.npy, clusters_ml.npy, rotations_ml.npy (in `rot_shape`, the shape of the rotations that came in),
     translations_ml.npy, ml_log_likelihood.npy, ml_sigma2.npy, ml_entropy.npy and class_averages_ml.npy (.mrcs, .jpg; the
-    montage counts the members by the new labels): ml_class_averages.py and TVAE_ML_AVERAGES=1 write these.
+    montage counts the members by the new labels): ml_class_averages.py and TVAE_ML_AVERAGES=1 write these; and
+    class_ctf_power_ml.npy, the weighted per-class sums of H^2, when the rounds ran with a CTF.
     -> those counts, int [K]."""
     save = lambda name, a: np.save(os.path.join(out_dir, name), stack_cli.host(a))
     new, K = stack_cli.host(labels), avg.shape[0]
@@ -318,21 +379,25 @@ def save_outputs(out_dir, avg, wsum, labels, theta, dx, hist, particles, rot_sha
     save('ml_log_likelihood.npy', hist['log_likelihood'])
     save('ml_sigma2.npy', hist['sigma2'])
     save('ml_entropy.npy', hist['entropy'])
+    if hist.get('ctf_power') is not None:
+        save('class_ctf_power_ml.npy', hist['ctf_power'])
     counts = np.bincount(new[(new >= 0) & (new < K)], minlength=K)
     stack_cli.save_poses(out_dir, 'ml', theta, dx, avg, counts, particles, rot_shape)
     return counts
 
 
 def run(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser(ctf=True).parse_args(argv)
     inp = stack_cli.open_inputs(args, stack_cli.make_device(args))
     images, theta, dx, clusters, t = inp.images, inp.theta, inp.dx, inp.clusters, inp.t_scale
     with stack_cli.hip_errors():
+        coef = align.load_ctf_coefficients(args.ctf, images.shape[0], args.scale) if args.ctf else None
         K = align._check_labels(images, theta, dx, clusters, args.n_clusters, 'ml_rounds')[3]
         before = refine._resolutions(images, theta, dx, clusters, K, t)
         avg, wsum, lab, th, d, hist = ml_rounds(images, theta, dx, clusters, K, t, args.rounds, math.radians(args.angle_range),
                                                 args.angle_steps, args.shift, args.mask_radius, args.mask_edge, args.keep,
-                                                args.sigma2, inp.latents, args.candidates, args.cross_halves)
+                                                args.sigma2, inp.latents, args.candidates, args.cross_halves, coef,
+                                                args.wiener_tau)
         after = refine._resolutions(images, th, d, lab.cpu().numpy(), K, t)
     os.makedirs(args.out_dir, exist_ok=True)
     counts = save_outputs(args.out_dir, avg, wsum, lab, th, d, hist, inp.particles, inp.rot_shape)
