@@ -801,6 +801,46 @@ int tvae_template_ctf_power(const float* theta, const float* dx, const int* cand
 int tvae_ctf_power_entries(const double* coef, const int* img, const float* w, const int* seg, double* D, double* wsum,
                            int* counts, int N, int E, int K, int n, tvae_stream_t stream);
 
+/* ---- Selection of a hard pose search from its tables: the template power per candidate or per angle ---------------------------
+ *
+ * tvae_pose_classify forms the tables num, pp, yy and selects from them in one call.  Under the model of the section above the
+ * three terms come from three places -- num from tvae_pose_classify (or tvae_pose_refine, the M = 1 layout) on the stack
+ * filtered with H_i, the template power from tvae_template_ctf_power, which does not depend on the shift, and yy from the raw
+ * stack -- so the selection is an entry point of its own that takes the template power per angle as it is written, without a
+ * copy expanded over the NS^2 shifts.  theta[N], dx[N][2], cand[N][M] (int32), n, K, M, A, S, t_scale and dtheta as for
+ * tvae_pose_classify; num[N][M][NA][NS][NS]; yy[N]; pp[N][M][NA] when pp_per_shift = 0 and [N][M][NA][NS][NS] when it is 1.
+ *
+ * Per candidate.  The candidate with the flat index e = (a' NS + sy') NS + sx' of slot m (a' = 0 .. 2A, sy', sx' = 0 .. 2S; the
+ * centre is a' = A, sy' = sx' = S) has the score of tvae_pose_refine from num[i][m][e], p and yy[i]: num / sqrt(p yy) in fp64
+ * from the three fp32 words (product, square root and quotient each correctly rounded), rounded to fp32 once; exactly 0 where
+ * p or yy is 0.  p = pp[i][m][a'] when pp_per_shift = 0 and pp[i][m][e] when it is 1.
+ *
+ * Per slot.  The rule of tvae_pose_refine, stated without an order of visits: among the candidates whose score is finite the
+ * largest score wins; among equal largest scores the centre wins if it is one of them, and otherwise the lowest flat index
+ * (+0 and -0 are equal).  score[i][m] = (sc, sb): sb the winner's score, sc the centre's, -inf if the centre's is not finite.
+ * If no candidate is finite the slot reports (0, 0) and the centre.  Any parallel reduction under this order gives the same
+ * bits as the serial visit of tvae_pose_refine.
+ *
+ * Across slots and outputs.  Those of tvae_pose_classify: the valid slots in ascending m, a later one wins only with a strictly
+ * greater sb; cls_out[i] = cand[i][m*], best[i] = (m*, a, sy, sx) = (m*, a' - A, sy' - S, sx' - S), theta_out and dx_out by the
+ * pose update of tvae_pose_refine (an index that is 0 copies its part of the pose bit for bit).  A slot outside [0, K) is
+ * skipped: its scores are (0, 0) and nothing of its rows of num and pp is read.  An image with no valid slot keeps its pose bit
+ * for bit and gets cls_out = cand[i][0], best = 0 and zero scores.  With pp_per_shift = 1 on the tables of one
+ * tvae_pose_classify call every output is that call's bit for bit.
+ *
+ * One wavefront owns an image, four images a workgroup of 256; the lanes stride over the candidates of a slot, so the loads of
+ * num are contiguous, and reduce with cross-lane shuffles.  No LDS, no atomics, no workspace: bitwise reproducible, and every
+ * output of image i depends on row i of the inputs only: not on N or the launch.
+ *
+ * Supported: 1 <= N <= 2^24, 2 <= n <= 128, 1 <= K <= 65535, 1 <= M <= 64, 0 <= A <= 32, 0 <= S <= 8 (the range of
+ * tvae_pose_classify without its channels), pp_per_shift 0 or 1, N M NA NS^2 < 2^40, t_scale finite and > 0, dtheta finite, no
+ * output overlapping an input or another output.  Anything else returns hipErrorInvalidValue (1) and writes nothing. */
+
+/* cls_out[N] (int32), best[N][4] = (m*, a, sy, sx) (int32), theta_out[N], dx_out[N][2], score[N][M][2] = (centre, best) */
+int tvae_pose_select(const float* theta, const float* dx, const int* cand, const float* num, const float* pp, const float* yy,
+                     int* cls_out, int* best, float* theta_out, float* dx_out, float* score, int N, int n, int K, int M, int A,
+                     int S, int pp_per_shift, float t_scale, float dtheta, tvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,9 @@ SIGNATURES = {
     'tvae_template_ctf_power': 'ppppp' 'pp' 'l' 'iiiiii' 'ffff',
     # coef (fp64), img (int32), w, seg (int32), D, wsum (fp64 both), counts (int32), N, E, K, n
     'tvae_ctf_power_entries': 'pppp' 'ppp' 'iiii',
+    # theta, dx, cand (int32), num, pp, yy, cls_out, best (int32 both), theta_out, dx_out, score, N, n, K, M, A, S, pp_per_shift,
+    # t_scale, dtheta
+    'tvae_pose_select': 'pppppp' 'ppppp' 'iiiiiii' 'ff',
 }
 # pure host queries: name -> (argument codes, return code)
 QUERIES = {

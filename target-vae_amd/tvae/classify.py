@@ -43,13 +43,20 @@ def _as_table(candidates, N, device, what):
 
 
 def classify_poses(images, theta, dx, candidates, refs, t_scale=1.0, angle_steps=8, angle_step=None, shift=2, mask_radius=None,
-                   mask_edge=0.0, tables=False):
+                   mask_edge=0.0, tables=False, ctf=None):
     """images [N][C][n][n], theta [N] or [N][1], dx [N][2], refs [K][C][n][n] (CUDA fp32), candidates [N][M] integers (any
     device or numpy; slot 0 by convention the image's current class, a value outside [0, K) is skipped) -> (labels' int64 [N],
     theta' [N], dx' [N][2], scores [N][M][2] = (centre, best) of every slot, best int32 [N][4] = (m*, a, sy, sx)) and with
     tables=True also (num, pp [N][M][NA][NS][NS], yy [N]), the raw sums.  An image with no valid slot keeps its pose and its
-    slot-0 value.  angle_steps, angle_step, shift and the mask as in tvae.refine.refine_poses."""
+    slot-0 value.  angle_steps, angle_step, shift and the mask as in tvae.refine.refine_poses.
+    ctf = (coef [N][5] on the device, yy fp32 [N] of the RAW images), the record of tvae.ml2d.e_step: `images` is the stack
+    filtered with H_i already, and the score of a candidate is num / sqrt(ppc yy) with num from these images, ppc =
+    tvae.ctf.template_power [N][M][NA] and yy the raw images' (tvae.ctf.search_poses: tvae_pose_classify for the tables, then
+    tvae_pose_select).  Labels, poses, scores and best are that kernel's; with tables=True pp is ppc and yy the raw one."""
     what = 'classify_poses'
+    if ctf is not None:
+        return _classify_poses_ctf(what, images, theta, dx, candidates, refs, t_scale, angle_steps, angle_step, shift, mask_radius,
+                                   mask_edge, tables, ctf)
     N, C, n = align._check_stack(images, theta, dx, what)
     A, S = int(angle_steps), int(shift)
     K, step, t, radius, edge = refine.check_search(what, images, refs, A, S, angle_step, t_scale, mask_radius, mask_edge)
@@ -85,6 +92,19 @@ def classify_poses(images, theta, dx, candidates, refs, t_scale=1.0, angle_steps
                     None if yy is None else yy[sl], ws, wsf, i1 - i0, C, n, K, M, A, S, t, step, radius, edge)
     out = (cls_out.to(torch.int64), th_out, dx_out, score, best)
     return out + (num, pp, yy) if tables else out
+
+
+def _classify_poses_ctf(what, images, theta, dx, candidates, refs, t_scale, angle_steps, angle_step, shift, mask_radius, mask_edge,
+                        tables, ctf):
+    from . import ctf as ctf_mod
+    N, C, n = align._check_stack(images, theta, dx, what)
+    A, S = int(angle_steps), int(shift)
+    step = refine.check_search(what, images, refs, A, S, angle_step, t_scale, mask_radius, mask_edge)[1]
+    cand, _ = _as_table(candidates, N, images.device, what)
+    th = theta.reshape(N)
+    num_of = lambda sl: classify_poses(images[sl], th[sl], dx[sl], cand[sl], refs, t_scale, A, step, S, mask_radius, mask_edge,
+                                       tables=True)[5]
+    return ctf_mod.search_poses(what, num_of, th, dx, cand, refs, ctf, n, t_scale, A, step, S, mask_radius, mask_edge, tables)
 
 
 def candidate_lists(labels, n_clusters, latents=None, m=None):
@@ -148,7 +168,8 @@ def cross_half_candidates(labels, candidates, n_clusters):
 
 
 def classify_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3, angle_range=math.pi / 8, angle_steps=8,
-                    shift=2, mask_radius=None, mask_edge=0.0, cross_halves=False, latents=None, candidates=None):
+                    shift=2, mask_radius=None, mask_edge=0.0, cross_halves=False, latents=None, candidates=None, ctf=None,
+                    wiener_tau=0.1):
     """`rounds` times: the class averages of the current labels and poses (tvae.align.class_averages; with cross_halves=True
     the two half-set averages of tvae.align.class_halves as 2K references, see cross_half_candidates), the candidate lists
     of the current labels (candidate_lists with `latents` and m = `candidates`), classify_poses, the labels and poses set to
@@ -159,7 +180,13 @@ def classify_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rou
     history['scores'] fp64 [rounds][2] the mean incumbent-centre score (slot 0) and the mean winning score over the images
     that were members of a class when the round began, history['moved'] int [rounds] the images whose label changed,
     history['counts'] int [rounds + 1][K] the class sizes before the first round and after each, and the last round's
-    history['candidates'] int64 [N][M] (classes) with their history['slot_scores'] fp32 [N][M][2]."""
+    history['candidates'] int64 [N][M] (classes) with their history['slot_scores'] fp32 [N][M][2].
+    ctf: coef rows [N][5] (tvae.ctf.coefficients) or None.  With them the score is that of the model Y_i = H_i (*) P_j + noise
+    (classify_poses(ctf=...)): the stack filtered with H_i and the raw sums of squares are formed once, and every round's
+    references are tvae.ctf.class_averages_ctf(..., 'wiener', wiener_tau) of the current labels and poses -- with cross_halves of
+    the 2K half-set labels of tvae.refine.half_set_labels.  The history then also holds 'averages', 'members' and 'ctf_power', the
+    Wiener averages of the returned labels and poses with their members and D [K][n][R], and the last round's 'references' with
+    the reference index of every slot, 'slots' int64 [N][M].  ctf None: every line runs as without the argument."""
     what = 'classify_rounds'
     N, C, n, K, lab = align._check_labels(images, theta, dx, labels, n_clusters, what)
     A = int(angle_steps)
@@ -171,13 +198,23 @@ def classify_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rou
         latents = torch.as_tensor(latents).to(images.device)
     count = lambda l: torch.bincount(l[(l >= 0) & (l < K)], minlength=K).cpu().numpy()
     steps, scores, moved, counts = [], [], [], [count(lab64)]
-    cand = sc = None
+    cand = sc = refs = slots = None
+    if ctf is not None:                                       # the stack num is formed from, and the record of classify_poses
+        from . import ctf as ctf_mod
+        coef, tau, scored, extra = ctf_mod.search_record(what, images, ctf, wiener_tau)
     for j in range(int(rounds)):
         step = float(angle_range) / max(A, 1) / 2 ** j
         cand = candidate_lists(lab64, K, latents, candidates)
-        refs = refine.round_references(images, th, d, lab64, K, t_scale, cross_halves)
+        if ctf is None:
+            refs = refine.round_references(images, th, d, lab64, K, t_scale, cross_halves)
+        else:
+            refs = refine.round_references_ctf(images, th, d, lab64, K, t_scale, cross_halves, coef, tau)
         slots = cross_half_candidates(lab64, cand, K) if cross_halves else cand
-        new, th, d, sc, best = classify_poses(images, th, d, slots, refs, t_scale, A, step, shift, mask_radius, mask_edge)
+        if ctf is None:
+            new, th, d, sc, best = classify_poses(images, th, d, slots, refs, t_scale, A, step, shift, mask_radius, mask_edge)
+        else:
+            new, th, d, sc, best = classify_poses(scored, th, d, slots, refs, t_scale, A, step, shift, mask_radius, mask_edge,
+                                                  ctf=extra)
         if cross_halves:
             new = torch.where(new >= 0, new % K, new)
         member = (lab64 >= 0) & (lab64 < K)
@@ -190,6 +227,9 @@ def classify_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rou
         counts.append(count(lab64))
     hist = dict(steps=steps, scores=np.stack(scores), moved=np.asarray(moved, dtype=np.int64), counts=np.stack(counts),
                 candidates=cand, slot_scores=sc)
+    if ctf is not None:
+        avg, members, D = ctf_mod.class_averages_ctf(images, th, d, lab64, coef, K, t_scale, 'wiener', tau)
+        hist.update(averages=avg, members=members, ctf_power=D, references=refs, slots=slots)
     return lab64, th, d, hist
 
 
@@ -207,20 +247,27 @@ def class_scores(candidates, slot_scores, n_clusters):
 
 
 # ---- reclassify_particles.py: new labels, poses and averages from the files a clustering run wrote ----------------------------
-def build_parser() -> argparse.ArgumentParser:
+def build_parser(ctf=False) -> argparse.ArgumentParser:
+    """ctf=True adds --ctf, --wiener-tau and --scale (what reclassify_particles.py parses); the default is the parser without
+    them."""
     p = argparse.ArgumentParser('Reassign the images of a clustered stack to their best-matching aligned 2-D class average')
     stack_cli.add_stack_flags(p)
     stack_cli.add_grid_flags(p)
     stack_cli.add_candidate_flags(p)
+    if ctf:
+        align.add_ctf_flags(p, ())
     return p
 
 
 def save_outputs(out_dir, labels, theta, dx, hist, avg, counts, particles, rot_shape):
     """clusters_reclassified.npy, rotations_reclassified.npy (in `rot_shape`, the shape of the rotations that came in),
     translations_reclassified.npy, classify_scores.npy, classify_moved.npy, class_scores.npy ([N][K], class_scores) and
-    class_averages_reclassified.npy (.mrcs, .jpg): reclassify_particles.py and TVAE_RECLASSIFY=1 write these."""
+    class_averages_reclassified.npy (.mrcs, .jpg): reclassify_particles.py and TVAE_RECLASSIFY=1 write these; and
+    class_ctf_power_reclassified.npy, the per-class sums of H^2, when the rounds ran with a CTF."""
     save = lambda name, a: np.save(os.path.join(out_dir, name), a)
     save('clusters_reclassified.npy', stack_cli.host(labels))
+    if hist.get('ctf_power') is not None:
+        save('class_ctf_power_reclassified.npy', stack_cli.host(hist['ctf_power']))
     save('classify_scores.npy', hist['scores'])
     save('classify_moved.npy', hist['moved'])
     save('class_scores.npy', class_scores(hist['candidates'], hist['slot_scores'], avg.shape[0]))
@@ -228,17 +275,18 @@ def save_outputs(out_dir, labels, theta, dx, hist, avg, counts, particles, rot_s
 
 
 def run(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser(ctf=True).parse_args(argv)
     inp = stack_cli.open_inputs(args, stack_cli.make_device(args))
     images, theta, dx, clusters, t = inp.images, inp.theta, inp.dx, inp.clusters, inp.t_scale
     with stack_cli.hip_errors():
+        coef = align.load_ctf_coefficients(args.ctf, images.shape[0], args.scale) if args.ctf else None
         K = align._check_labels(images, theta, dx, clusters, args.n_clusters, 'classify_rounds')[3]
         before = refine._resolutions(images, theta, dx, clusters, K, t)
         lab, th, d, hist = classify_rounds(images, theta, dx, clusters, K, t, args.rounds, math.radians(args.angle_range),
                                            args.angle_steps, args.shift, args.mask_radius, args.mask_edge, args.cross_halves,
-                                           inp.latents, args.candidates)
+                                           inp.latents, args.candidates, coef, args.wiener_tau)
         new = lab.cpu().numpy()
-        avg, counts = align.class_averages(images, th, d, new, K, t)
+        avg, counts = (hist['averages'], hist['members']) if args.ctf else align.class_averages(images, th, d, new, K, t)
         after = refine._resolutions(images, th, d, new, K, t)
     os.makedirs(args.out_dir, exist_ok=True)
     save_outputs(args.out_dir, new, th, d, hist, avg, counts, inp.particles, inp.rot_shape)

@@ -236,6 +236,88 @@ def template_power(theta, dx, slots, refs, coef, t_scale=1.0, angle_steps=8, ang
     return ppc
 
 
+def select_poses(num, pp, yy, candidates, theta, dx, n, n_clusters, t_scale=1.0, angle_steps=8, angle_step=None, shift=2):
+    """The hard selection from the three tables of a pose search (tvae_pose_select): num [N][M][NA][NS][NS], yy [N], and pp
+    either [N][M][NA] -- tvae.ctf.template_power, the template power per angle -- or [N][M][NA][NS][NS] (CUDA fp32), with the
+    candidates [N][M] the tables were made for, the poses theta [N] or [N][1] and dx [N][2] the grid is centred on and the side n
+    of the images -> the tuple of tvae.classify.classify_poses: (labels' int64 [N], theta' [N], dx' [N][2], scores [N][M][2],
+    best int32 [N][4]).  angle_steps, angle_step and shift as they were given to the search that wrote num."""
+    from . import classify, refine
+    what = 'select_poses'
+    for nm, t in (('num', num), ('pp', pp), ('yy', yy), ('theta', theta), ('dx', dx)):
+        CL.require_f32(t, what, nm)
+    N = yy.numel()
+    dev = yy.device
+    cand, M = classify._as_table(candidates, N, dev, what)
+    A, S, K, n = int(angle_steps), int(shift), int(n_clusters), int(n)
+    NA, NS = 2 * A + 1, 2 * S + 1
+    if yy.dim() != 1 or tuple(num.shape) != (N, M, NA, NS, NS):
+        raise TvaeHipError(f'{what}: yy must be [N] and num [N][M][NA][NS][NS] = {(N, M, NA, NS, NS)}, got {tuple(yy.shape)} and '
+                           f'{tuple(num.shape)}')
+    if tuple(pp.shape) not in ((N, M, NA), (N, M, NA, NS, NS)):
+        raise TvaeHipError(f'{what}: pp must be [N][M][NA] = {(N, M, NA)} or [N][M][NA][NS][NS], got {tuple(pp.shape)}')
+    if theta.numel() != N or theta.dim() > 2 or tuple(dx.shape) != (N, 2):
+        raise TvaeHipError(f'{what}: theta must hold N = {N} angles and dx must be [N][2]')
+    if any(t.device != dev for t in (num, pp, theta, dx)):
+        raise TvaeHipError(f'{what}: num, pp, yy, theta and dx must live on one device')
+    if not (1 <= K <= CL.MAX_CLASSES and 2 <= n <= refine.MAX_SIDE and 0 <= A <= refine.MAX_ANGLE_STEPS
+            and 0 <= S <= refine.MAX_SHIFT and 1 <= N <= MAX_PLANES and num.numel() < 2 ** 40):
+        raise TvaeHipError(f'{what}: N={N}, n={n}, K={K}, angle_steps={A}, shift={S} outside the supported range')
+    step, t = refine.angle_step_of(A, angle_step), float(t_scale)
+    if not (np.isfinite(t) and t > 0 and np.isfinite(step)):
+        raise TvaeHipError(f'{what}: t_scale = {t_scale} must be finite and positive and angle_step = {angle_step} finite')
+    cls_out = torch.empty(N, dtype=torch.int32, device=dev)
+    best = torch.empty(N, 4, dtype=torch.int32, device=dev)
+    th_out = torch.empty(N, dtype=torch.float32, device=dev)
+    dx_out = torch.empty(N, 2, dtype=torch.float32, device=dev)
+    score = torch.empty(N, M, 2, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        CL.call('tvae_pose_select', theta.reshape(N), dx, cand, num, pp, yy, cls_out, best, th_out, dx_out, score, N, n, K, M, A, S,
+                int(pp.dim() == 5), t, step)
+    return cls_out.to(torch.int64), th_out, dx_out, score, best
+
+
+def search_record(what, images, ctf, wiener_tau):
+    """What the rounds of a hard search form once from the coef rows `ctf` [N][5]: -> (coef fp64 on the device, tau, the stack
+    filtered with H_i, (coef, yy of the raw images)), the last the `ctf` record of refine_poses and classify_poses."""
+    from . import ml2d
+    coef, tau = _coef_tensor(ctf, images.device, what), float(wiener_tau)
+    if coef.shape[0] != images.shape[0]:
+        raise TvaeHipError(f'{what}: ctf must hold N = {images.shape[0]} rows, got {coef.shape[0]}')
+    if not tau > 0:
+        raise TvaeHipError(f'{what}: wiener_tau = {wiener_tau} must be positive')
+    return coef, tau, filter_stack(images, coef=coef, mode='multiply'), (coef, ml2d.raw_sum_squares(images))
+
+
+def search_poses(what, tables_of, theta, dx, slots, refs, ctf, n, t_scale, A, step, S, mask_radius, mask_edge, tables=False):
+    """The hard pose search under Y_i = H_i (*) P_j + noise, slice by slice so that the tables never exceed the workspace bound
+    of tvae.refine (tvae.ml2d._slices): num = tables_of(slice) [N'][M][NA][NS][NS], the num table of the plain search on the
+    stack filtered with H_i already; template_power; select_poses with the power per angle.  ctf = (coef [N][5], yy fp32 [N] of
+    the RAW images), theta [N], slots [N][M] on the device.
+    -> (labels' int64 [N], theta' [N], dx' [N][2], scores [N][M][2], best int32 [N][4]) and with tables=True also
+    (num, ppc [N][M][NA], yy)."""
+    from . import ml2d
+    N, M, K = theta.numel(), slots.shape[1], refs.shape[0]
+    if not (isinstance(ctf, (tuple, list)) and len(ctf) == 2):
+        raise TvaeHipError(f'{what}: ctf must be (coef [N][5], yy [N] of the raw images)')
+    coef = _coef_tensor(ctf[0], refs.device, what)
+    yy_raw = ctf[1]
+    CL.require_f32(yy_raw, what, 'ctf[1]')
+    if coef.shape[0] != N or tuple(yy_raw.shape) != (N,) or yy_raw.device != refs.device:
+        raise TvaeHipError(f'{what}: ctf must hold N = {N} rows of coefficients and N sums of squares on the device of the images')
+    stepN = ml2d._slices(N, M, A, S)
+    parts = []
+    for i0 in range(0, N, stepN):
+        sl = slice(i0, min(i0 + stepN, N))
+        num = tables_of(sl)
+        ppc = template_power(theta[sl], dx[sl], slots[sl], refs, coef[sl], t_scale, A, step, mask_radius, mask_edge)
+        yy = yy_raw[sl].contiguous()
+        out = select_poses(num, ppc, yy, slots[sl], theta[sl], dx[sl], n, K, t_scale, A, step, S)
+        parts.append(out + (num, ppc, yy) if tables else out)
+        del num, ppc, yy
+    return tuple(torch.cat([p[j] for p in parts]) for j in range(len(parts[0])))
+
+
 def power_weighted(coef, entries, n, n_clusters):
     """coef [N][5], entries as tvae.ml2d.entries_by_class returns them (img, w, seg on one CUDA device) -> (D fp64 [K][n][R],
     wsum fp64 [K], counts int32 [K]): D[k] = sum w_e H_img[e]^2 over the live entries of class k (tvae_ctf_power_entries), the

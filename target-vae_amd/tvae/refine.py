@@ -99,13 +99,37 @@ def round_references(images, theta, dx, lab64, K, t_scale, cross_halves):
     return align.class_averages(images, theta, dx, lab64, K, t_scale)[0]
 
 
+def half_set_labels(lab64, K):
+    """labels int64 [N] -> int64 [N]: the label h K + k among the 2K half-set classes [half 0 of class 0 .. K - 1, half 1 of
+    class 0 .. K - 1] of the half the image is IN (cross_half_labels names the other one); -1 outside [0, K).  A class average
+    over these labels with 2K classes has the layout of round_references(cross_halves=True)."""
+    own = cross_half_labels(lab64, K)
+    return torch.where(own >= 0, (own + K) % (2 * K), own)
+
+
+def round_references_ctf(images, theta, dx, lab64, K, t_scale, cross_halves, coef, tau):
+    """round_references under a CTF: the Wiener averages tvae.ctf.class_averages_ctf of the RAW images, [K][C][n][n] or, with
+    cross_halves, those of half_set_labels, [2K][C][n][n]."""
+    from . import ctf
+    if cross_halves:
+        return ctf.class_averages_ctf(images, theta, dx, half_set_labels(lab64, K), coef, 2 * K, t_scale, 'wiener', tau)[0]
+    return ctf.class_averages_ctf(images, theta, dx, lab64, coef, K, t_scale, 'wiener', tau)[0]
+
+
 def refine_poses(images, theta, dx, labels, refs, t_scale=1.0, angle_steps=8, angle_step=None, shift=2, mask_radius=None,
-                 mask_edge=0.0, tables=False):
+                 mask_edge=0.0, tables=False, ctf=None):
     """images [N][C][n][n], theta [N] or [N][1], dx [N][2], refs [K][C][n][n] (CUDA fp32), labels [N] integers (any device or
     numpy; a label outside [0, K) leaves its image alone) -> (theta' [N], dx' [N][2], scores [N][2] = (centre, best),
     best int32 [N][3] = (a, sy, sx)) and with tables=True also (num, pp [N][NA][NS][NS], yy [N]), the raw sums.
-    angle_steps = A steps of angle_step radians to each side (None: pi / 8 divided by max(A, 1)); shift = S pixels."""
+    angle_steps = A steps of angle_step radians to each side (None: pi / 8 divided by max(A, 1)); shift = S pixels.
+    ctf = (coef [N][5] on the device, yy fp32 [N] of the RAW images): `images` is the stack filtered with H_i already and the
+    score of a candidate is num / sqrt(ppc yy), ppc = tvae.ctf.template_power of the image's class (tvae.ctf.search_poses with
+    one slot per image: tvae_pose_refine for num, then tvae_pose_select).  With tables=True pp is ppc [N][NA] and yy the raw
+    one."""
     what = 'refine_poses'
+    if ctf is not None:
+        return _refine_poses_ctf(what, images, theta, dx, labels, refs, t_scale, angle_steps, angle_step, shift, mask_radius,
+                                 mask_edge, tables, ctf)
     N, C, n, _, lab = align._check_labels(images, theta, dx, labels, 1, what)
     A, S = int(angle_steps), int(shift)
     K, step, t, radius, edge = check_search(what, images, refs, A, S, angle_step, t_scale, mask_radius, mask_edge)
@@ -142,6 +166,24 @@ def refine_poses(images, theta, dx, labels, refs, t_scale=1.0, angle_steps=8, an
     return th_out, dx_out, score, best
 
 
+def _refine_poses_ctf(what, images, theta, dx, labels, refs, t_scale, angle_steps, angle_step, shift, mask_radius, mask_edge,
+                      tables, ctf):
+    from . import ctf as ctf_mod
+    N, C, n, _, lab = align._check_labels(images, theta, dx, labels, 1, what)
+    A, S = int(angle_steps), int(shift)
+    step = check_search(what, images, refs, A, S, angle_step, t_scale, mask_radius, mask_edge)[1]
+    cls = class_index(lab, f'{what}: labels must be a one-dimensional integer array')
+    th = theta.reshape(N)
+    # (the tables of tvae_pose_refine have the layout of one slot)
+    num_of = lambda sl: refine_poses(images[sl], th[sl], dx[sl], cls[sl], refs, t_scale, A, step, S, mask_radius, mask_edge,
+                                     tables=True)[4].unsqueeze(1)
+    out = ctf_mod.search_poses(what, num_of, th, dx, cls[:, None], refs, ctf, n, t_scale, A, step, S, mask_radius, mask_edge, tables)
+    th_out, dx_out, score, best = out[1], out[2], out[3].reshape(N, 2), out[4][:, 1:].contiguous()
+    if tables:
+        return th_out, dx_out, score, best, out[5].squeeze(1), out[6].squeeze(1), out[7]
+    return th_out, dx_out, score, best
+
+
 def cross_half_labels(labels, n_clusters):
     """labels [N] (integers, any device) -> int64 [N] on the same device: the index among the 2K references
     [half 0 of class 0 .. K - 1, half 1 of class 0 .. K - 1] of the half-set average that does NOT contain the image.  Half
@@ -165,12 +207,18 @@ def cross_half_labels(labels, n_clusters):
 
 
 def refine_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, rounds=3, angle_range=math.pi / 8, angle_steps=8,
-                  shift=2, mask_radius=None, mask_edge=0.0, cross_halves=False):
+                  shift=2, mask_radius=None, mask_edge=0.0, cross_halves=False, ctf=None, wiener_tau=0.1):
     """`rounds` times: the class averages of the current poses (tvae.align.class_averages; with cross_halves=True the two
     half-set averages of tvae.align.class_halves as 2K references, every image scored against the half it is not in), then
     refine_poses, then half the angle step: round j searches angle_range / 2^j to each side in angle_steps steps, inside the
     cell that the previous round chose.  -> (theta' [N], dx' [N][2], history): history['steps'] the angle step of every round
-    and history['scores'] fp64 [rounds][2], the mean centre and best score over the images of a class in each round."""
+    and history['scores'] fp64 [rounds][2], the mean centre and best score over the images of a class in each round.
+    ctf: coef rows [N][5] (tvae.ctf.coefficients) or None.  With them the score is that of the model Y_i = H_i (*) P_j + noise
+    (refine_poses(ctf=...)): the stack filtered with H_i and the raw sums of squares are formed once, and every round's
+    references are round_references_ctf, the Wiener averages (wiener_tau) of the current poses.  The history then also holds
+    'averages', 'members' and 'ctf_power' -- the Wiener averages of the returned poses, their members and D [K][n][R] -- and the
+    last round's 'references' with 'slots' int64 [N], the reference every image was scored against.  ctf None: every line runs
+    as without the argument."""
     what = 'refine_rounds'
     N, C, n, K, lab = align._check_labels(images, theta, dx, labels, n_clusters, what)
     A = int(angle_steps)
@@ -181,21 +229,36 @@ def refine_rounds(images, theta, dx, labels, n_clusters=None, t_scale=1.0, round
     member = (lab64 >= 0) & (lab64 < K)
     cls = cross_half_labels(lab64, K) if cross_halves else lab64
     steps, scores = [], []
+    refs = None
+    if ctf is not None:                                       # the stack num is formed from, and the record of refine_poses
+        from . import ctf as ctf_mod
+        coef, tau, scored, extra = ctf_mod.search_record(what, images, ctf, wiener_tau)
     for j in range(int(rounds)):
         step = float(angle_range) / max(A, 1) / 2 ** j
-        refs = round_references(images, th, d, lab64, K, t_scale, cross_halves)
-        th, d, sc, _ = refine_poses(images, th, d, cls, refs, t_scale, A, step, shift, mask_radius, mask_edge)
+        if ctf is None:
+            refs = round_references(images, th, d, lab64, K, t_scale, cross_halves)
+            th, d, sc, _ = refine_poses(images, th, d, cls, refs, t_scale, A, step, shift, mask_radius, mask_edge)
+        else:
+            refs = round_references_ctf(images, th, d, lab64, K, t_scale, cross_halves, coef, tau)
+            th, d, sc, _ = refine_poses(scored, th, d, cls, refs, t_scale, A, step, shift, mask_radius, mask_edge, ctf=extra)
         steps.append(step)
         m = sc[member].double()
         scores.append(m.mean(0).cpu().numpy() if m.numel() else np.zeros(2))
-    return th, d, dict(steps=steps, scores=np.stack(scores))
+    hist = dict(steps=steps, scores=np.stack(scores))
+    if ctf is not None:
+        avg, counts, D = ctf_mod.class_averages_ctf(images, th, d, lab64, coef, K, t_scale, 'wiener', tau)
+        hist.update(averages=avg, members=counts, ctf_power=D, references=refs, slots=cls)
+    return th, d, hist
 
 
 # ---- refine_poses.py: refined poses and averages from the files a clustering run wrote ---------------------------------------
-def build_parser() -> argparse.ArgumentParser:
+def build_parser(ctf=False) -> argparse.ArgumentParser:
+    """ctf=True adds --ctf, --wiener-tau and --scale (what refine_poses.py parses); the default is the parser without them."""
     p = argparse.ArgumentParser('Refine the poses of a clustered stack against its aligned 2-D class averages')
     stack_cli.add_stack_flags(p)
     stack_cli.add_grid_flags(p)
+    if ctf:
+        align.add_ctf_flags(p, ())
     return p
 
 
@@ -209,21 +272,26 @@ def _resolutions(images, theta, dx, clusters, K, t):
 
 def save_outputs(out_dir, theta, dx, hist, avg, counts, particles, rot_shape):
     """rotations_refined.npy (in `rot_shape`, the shape of the rotations that came in), translations_refined.npy,
-    refine_scores.npy and class_averages_refined.npy (.mrcs, .jpg): refine_poses.py and TVAE_REFINE_POSES=1 write these."""
+    refine_scores.npy and class_averages_refined.npy (.mrcs, .jpg): refine_poses.py and TVAE_REFINE_POSES=1 write these; and
+    class_ctf_power_refined.npy, the per-class sums of H^2, when the rounds ran with a CTF."""
     np.save(os.path.join(out_dir, 'refine_scores.npy'), hist['scores'])
+    if hist.get('ctf_power') is not None:
+        np.save(os.path.join(out_dir, 'class_ctf_power_refined.npy'), stack_cli.host(hist['ctf_power']))
     stack_cli.save_poses(out_dir, 'refined', theta, dx, avg, counts, particles, rot_shape)
 
 
 def run(argv=None):
-    args = build_parser().parse_args(argv)
+    args = build_parser(ctf=True).parse_args(argv)
     inp = stack_cli.open_inputs(args, stack_cli.make_device(args))
     images, theta, dx, clusters, t = inp.images, inp.theta, inp.dx, inp.clusters, inp.t_scale
     with stack_cli.hip_errors():
+        coef = align.load_ctf_coefficients(args.ctf, images.shape[0], args.scale) if args.ctf else None
         K = align._check_labels(images, theta, dx, clusters, args.n_clusters, 'refine_poses')[3]
         before = _resolutions(images, theta, dx, clusters, K, t)
         th, d, hist = refine_rounds(images, theta, dx, clusters, K, t, args.rounds, math.radians(args.angle_range),
-                                    args.angle_steps, args.shift, args.mask_radius, args.mask_edge, args.cross_halves)
-        avg, counts = align.class_averages(images, th, d, clusters, K, t)
+                                    args.angle_steps, args.shift, args.mask_radius, args.mask_edge, args.cross_halves, coef,
+                                    args.wiener_tau)
+        avg, counts = (hist['averages'], hist['members']) if args.ctf else align.class_averages(images, th, d, clusters, K, t)
         after = _resolutions(images, th, d, clusters, K, t)
     os.makedirs(args.out_dir, exist_ok=True)
     save_outputs(args.out_dir, th, d, hist, avg, counts, inp.particles, inp.rot_shape)
